@@ -9,31 +9,42 @@ A "step" = one forward + one backward of the op over the synthetic batch, issued
 drop-in dispatcher ops torch.ops.torchshifts._shift2d_forward/_backward (allocation of the outputs
 and the workspace included).  Inputs are resident in HBM before the timed region.
 
-The JSON line also carries
+A plain run sets up, warms up, times --steps steps, writes the last timed step's outputs when --dump-outputs is given and prints
+its JSON line (headline fields, no per-kernel figures).  --full adds what needs runs of its own, measured after the timed region or,
+for the child processes, before this process touches the GPU:
   roofline      the dominant kernel (step_backward on C2): algorithmic bytes (3*s per element, SURVEY
                 section 8d) / average launch duration measured with HIP events on the launch
-                stream, against the 8 TB/s HBM peak
-  cpu_baseline  the REAL reference CPU kernels (oracle/_ref, built from /root/reference) timed on
-                this host in a child process on a bounded sample (rank 0, --gpus 1 only)
+                stream, against the 8 TB/s HBM peak; `kernels` holds every kernel of the step timed the same way
+  ms_per_step_median / ms_per_step_min   the spread of up to 50 single steps
+  cpu_baseline  the REAL reference CPU kernels (oracle/_ref, built by oracle/build_ref.sh from the reference's sources)
+                timed on this host in a child process on a bounded sample (rank 0, --gpus 1, workload c2 only)
 
   roofline.box_stream / frac_of_box   the same box's plain 1R1W / 2R1W float4 streams (tools/stream_probe, a child
                 process that has exited before this one touches the GPU) and the dominant kernel's rate against them
 
-  configs       (default run only: --gpus 1, workload c2, padding 0) AFTER the headline's timed region, in the same
+  configs       (--full default run only: --gpus 1, workload c2, padding 0) AFTER the headline's timed region, in the same
                 process, every other BASELINE config (C2 paddings 1-4, C3 paddings 0-4, C4, C5 per GPU) and the round's
                 other workloads are built, timed for >= 20 steps through the same dispatcher ops, measured kernel by
                 kernel with HIP events and freed again.  --no-configs skips it.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what its last timed step returned -- `out`, and for fwd+bwd workloads
+`grad_x` and `grad_w` (quantized outputs: `out_int_repr`, the stored integers) -- as DIR/<name>.npy in float32 (exact for
+every dtype the workloads use), in the output's logical shape.  An output of more than DUMP_SAMPLE elements is written as a
+flat, fixed, seeded sample of at most DUMP_SAMPLE of its elements in logical (NCHW / NCDHW) order, ascending flat index, the
+same for every run of the same shape: at most 48 MB in all.
+The inputs are a fixed integer hash of the element index (synth_tensor), identical from run to run.
 
 OUTPUT (rank 0), in this order:
   1. `{"bench_detail": ...}`    one line: everything measured (per-kernel medians, the box calibration, every rank's device,
                                 the whole cpu_baseline record, every config's record); also written to
                                 gpurun_out/bench_detail.json when that directory exists
   2. the RESULT line, LAST and never longer than HEADLINE_MAX_BYTES (a consumer that keeps only a few KB of the
-     tail of stdout must still find one whole line): the contract's fields + `roofline` + `cpu_baseline` (trimmed; with
+     tail of stdout must still find one whole line): the contract's fields; with --full + `roofline` + `cpu_baseline` (trimmed; with
      `own_cpu_key` = this repo's CPU dispatch key timed beside the reference) + `configs` = {name: [ms_per_step,
      dominant kernel, its fraction of 8 TB/s, counter traffic / algorithmic bytes or null]}
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--pad 0..4]      (NAME: see WORKLOADS)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--pad 0..4] [--full] [--dump-outputs DIR]
+                                                                                              (NAME: see WORKLOADS)
 
 Multi-GPU: `python bench.py --gpus N` starts the N rank processes itself (one per GPU; the parent never
 touches the GPU); under a launcher (`python -m torch.distributed.run --nproc-per-node N bench.py --gpus N`)
@@ -112,6 +123,8 @@ EXTRA_CONFIGS = ([("c2_pad%d" % p, "c2", p) for p in (1, 2, 3, 4)] + [("c3_pad%d
 BASELINE_CONFIGS = [c[0] for c in EXTRA_CONFIGS[:11]]  # what BASELINE.json's `configs` list beyond the headline
 HEADLINE_MAX_BYTES = 4000  # the RESULT line is the last line of stdout and fits a small tail (round-5 verdict: a 24 KB line was lost)
 ESIZE = {"float32": 4, "bfloat16": 2, "float16": 2, "quint8": 1}
+DUMP_SAMPLE = 4 << 20  # --dump-outputs: elements kept of a larger output (16 MB of float32; at most three outputs per step)
+DUMP_SEED = 20240601
 
 # user `borders` of the cropped workloads ([nD, 2] cut-left / cut-right amounts, functional.py:22,32-35)
 CUTS = {"c2crop": [[1, 1], [1, 1]], "c2acrop": [[1, 1], [1, 1]], "t1": [[1, 1], [1, 1]], "t1a": [[1, 1], [1, 1]],
@@ -429,6 +442,23 @@ def synth_tensor(torch, shape, seed, device, dtype, lo=0.0, hi=1.0):
     return out.view(*shape)
 
 
+def dump_outputs(torch, outs, names, ddir):
+    """--dump-outputs: the step's outputs as DIR/<name>.npy in float32, in their logical shape; more than DUMP_SAMPLE elements ->
+    a flat array of the elements at a fixed, seeded set of flat indices (logical order, ascending), drawn from the element count
+    alone"""
+    import numpy as np
+    os.makedirs(ddir, exist_ok=True)
+    for name, t in zip(names, outs):
+        t = t.detach()
+        if t.is_quantized:
+            t = t.int_repr()
+        n = t.numel()
+        if n > DUMP_SAMPLE:
+            idx = np.unique(np.random.RandomState(DUMP_SEED).randint(0, n, size=DUMP_SAMPLE, dtype=np.int64))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(ddir, name + ".npy"), np.ascontiguousarray(t.to(torch.float32).cpu().numpy()))
+
+
 def parse_args(argv):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -452,6 +482,12 @@ def parse_args(argv):
     ap.add_argument("--force-process-group", action="store_true",
                     help="initialise the process group (RCCL on a GPU box) even for --gpus 1: exercises the rendezvous, "
                          "barrier, all_gather and all_reduce(MAX) calls of the multi-GPU path on a 1-GPU box (tests)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what needs runs of its own: per-kernel times and the roofline, the spread of single steps, "
+                         "the same-box stream calibration, the reference's CPU baseline and (default run) every other config")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last timed step's outputs as DIR/<name>.npy (float32; seeded sample "
+                         "of a large output)")
     ap.add_argument("--device", default="cuda", choices=("cuda", "cpu"),
                     help="cpu = run the rank/launcher plumbing on the CPU dispatch key with gloo (tests only; "
                          "no roofline, never a result)")
@@ -472,9 +508,9 @@ def main(argv=None):
         raise SystemExit("bench.py: --gpus %d but WORLD_SIZE=%d (launch with `python bench.py --gpus N`, or "
                          "`python -m torch.distributed.run --nproc-per-node N bench.py --gpus N`)" % (a.gpus, world))
 
-    default_run = rank == 0 and world == 1 and a.workload == "c2" and a.pad == 0 and a.shape is None and a.device == "cuda"
+    default_run = a.full and rank == 0 and world == 1 and a.workload == "c2" and a.pad == 0 and a.shape is None and a.device == "cuda"
     base = None
-    if rank == 0 and world == 1 and a.workload == "c2" and a.shape is None and a.device == "cuda" \
+    if a.full and rank == 0 and world == 1 and a.workload == "c2" and a.shape is None and a.device == "cuda" \
             and not a.no_cpu_baseline:
         base = cpu_baseline(a.pad)  # child process, before any GPU initialisation in this process
         base["own_cpu_key"] = own_cpu_key(a.pad)
@@ -491,7 +527,7 @@ def main(argv=None):
             _n *= _s
         return _n * ESIZE[_dt]
 
-    if rank == 0 and world == 1 and a.device == "cuda" and not a.no_probe:
+    if a.full and rank == 0 and world == 1 and a.device == "cuda" and not a.no_probe:
         # child process too: it has left the GPU before this process initialises it.  Streams of THIS workload's tensor size
         # (a 0.2 ms kernel over 0.4 GB tensors pays launch ramp and tail that a 1.5 ms kernel over 3.3 GB does not); the
         # default run also calibrates at the tensor sizes of the BASELINE configs it times after the headline
@@ -763,11 +799,17 @@ def main(argv=None):
     for _ in range(a.warmup):
         step()
     barrier()
+    last = None
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        step()
+        last = None   # (the previous step's outputs go back to the allocator before the next step, as when they are dropped)
+        last = step()
     barrier()
     dt = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0 and last is not None:
+        dump_outputs(torch, (last,) if torch.is_tensor(last) else last,
+                     ("out_int_repr",) if quant else ("out", "grad_x", "grad_w"), a.dump_outputs)
+    del last
     per_rank_ms = [dt / a.steps * 1e3]
     if use_pg:
         t = torch.tensor([dt], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
@@ -809,7 +851,7 @@ def main(argv=None):
 
     # ---- per-step spread (median / min over single steps; outside the contract's timed region) -----------
     singles = []
-    for _ in range(min(a.steps, 50)):
+    for _ in range(min(a.steps, 50) if a.full else 0):
         sync()
         t1 = time.perf_counter()
         step()
@@ -820,7 +862,7 @@ def main(argv=None):
     kiters = max(5, a.steps)
     kernels = {}
     dom_name = dom_ms = dom_bytes = None
-    if on_gpu:
+    if on_gpu and a.full:
         kernels, (dom_name, dom_ms, dom_bytes, dom_kind) = wl.kernel_times(kiters, probe)
     path = "+".join(sorted(set(k.split("_")[0] for k in kernels))) or "cpu key"
 
@@ -849,8 +891,6 @@ def main(argv=None):
             "steps": a.steps,
             "warmup": a.warmup,
             "ms_per_step": ms_per_step,
-            "ms_per_step_median": singles[len(singles) // 2],
-            "ms_per_step_min": singles[0],
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -858,8 +898,8 @@ def main(argv=None):
             "data": "synthetic",
             "config": {"workload": desc + ", padding %d, per GPU; batch sharded over %d GPU(s), no collectives"
                                    % (a.pad, world),
-                       "path": ("torch.ops.torchshifts._shift%dd_forward/_backward -> libshiftnd_hip.so (%s kernels)"
-                                % (nd, path)) if on_gpu else "torch.ops.torchshifts (CPU dispatch key of _C.so)",
+                       "path": ("torch.ops.torchshifts._shift%dd_forward/_backward -> libshiftnd_hip.so" % nd
+                                + (" (%s kernels)" % path if kernels else "")) if on_gpu else "torch.ops.torchshifts (CPU dispatch key of _C.so)",
                        "ranks": {"world": world, "backend": backend if use_pg else None, "devices": ndev,
                                  "oversubscribed": oversubscribed,
                                  "device_name": torch.cuda.get_device_name(dev) if on_gpu else None,
@@ -868,6 +908,8 @@ def main(argv=None):
             "achieved_hbm_GBps_step": step_bytes / (ms_per_step * 1e-3) / 1e9,
             "kernels": kernels,
         }
+        if singles:
+            result["ms_per_step_median"], result["ms_per_step_min"] = singles[len(singles) // 2], singles[0]
         if dom_name is not None:
             result["roofline"] = roofline_of(a.workload, a.pad, (dom_name, dom_ms, dom_bytes, dom_kind), probe, a.shape)
             if probe is not None:

@@ -118,7 +118,7 @@ def test_self_launch_two_ranks_on_this_gpu_box():
     if torch.cuda.device_count() < 2:
         refused = _run(["--gpus", "2", "--shape", "8,32,56,56", "--steps", "1", "--warmup", "0"], timeout=120)
         assert refused.returncode != 0 and "--allow-oversubscribe" in refused.stderr  # never a silent degradation
-    r = _run(["--gpus", "2", "--shape", "8,32,56,56", "--steps", "3", "--warmup", "1", "--allow-oversubscribe"])
+    r = _run(["--gpus", "2", "--shape", "8,32,56,56", "--steps", "3", "--warmup", "1", "--allow-oversubscribe", "--full"])
     assert r.returncode == 0, r.stderr[-2000:]
     j = _json_lines(r.stdout)
     assert len(j) == 1 and j[0]["n_gpus"] == 2
@@ -142,6 +142,52 @@ def test_rccl_calls_of_the_rank_code_on_one_gpu():
     pr = _detail(r.stdout)["config"]["ranks"]["per_rank"]
     assert len(pr) == 1 and pr[0]["device_index"] == 0 and pr[0]["pg_backend"] == "nccl" and pr[0]["pg_world_size"] == 1
     assert pr[0]["device_name"] and pr[0]["pci_bus_id"] and pr[0]["hbm_bytes"] > 2 ** 37
+
+
+def test_dump_outputs_of_the_last_timed_step_cpu(tmp_path):
+    """--dump-outputs DIR: the last timed step's out / grad_x / grad_w as float32 .npy in their logical shapes, identical from run to
+    run (the inputs are a fixed hash); the plain run times exactly --steps steps and measures nothing beyond them"""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d = tmp_path / ("run%d" % i)
+        r = _run(["--device", "cpu", "--shape", "4,8,16,16", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        j = _last_line_is_the_result(r.stdout)
+        assert j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0
+        assert j["kernels"] == {} and j["roofline"] is None and "ms_per_step_median" not in j and "cpu_baseline" not in j
+        assert sorted(os.listdir(d)) == ["grad_w.npy", "grad_x.npy", "out.npy"]
+        dumps.append({n: np.load(str(d / (n + ".npy"))) for n in ("out", "grad_x", "grad_w")})
+    for n, shape in (("out", (4, 8, 16, 16)), ("grad_x", (4, 8, 16, 16)), ("grad_w", (8, 2))):
+        assert dumps[0][n].dtype == np.float32 and dumps[0][n].shape == shape, n
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n
+    # the forward of the synthetic input: the sparse shift moves values, it never invents them
+    scaled = dumps[0]["out"].astype(np.float64) * (1 << 24)
+    assert (scaled == np.round(scaled)).all() and (dumps[0]["out"] >= 0).all() and (dumps[0]["out"] < 1).all()
+
+
+def test_dump_outputs_samples_a_large_output(tmp_path, monkeypatch):
+    """an output above DUMP_SAMPLE elements is written as the elements at a fixed, seeded set of ascending flat indices"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 100)
+    t = torch.arange(6 * 7 * 8, dtype=torch.float32).reshape(6, 7, 8)
+    q = torch.quantize_per_tensor(torch.rand(3, 4), 0.1, 3, torch.quint8)
+    bench.dump_outputs(torch, (t, q), ("big", "q"), str(tmp_path / "a"))
+    bench.dump_outputs(torch, (t.permute(0, 2, 1).contiguous().permute(0, 2, 1), q), ("big", "q"), str(tmp_path / "b"))
+    a, b = np.load(str(tmp_path / "a" / "big.npy")), np.load(str(tmp_path / "b" / "big.npy"))
+    assert a.dtype == np.float32 and a.ndim == 1 and 50 < a.size <= 100
+    assert np.array_equal(a, b) and (np.diff(a) > 0).all()   # logical order whatever the strides; ascending flat indices
+    assert np.array_equal(np.load(str(tmp_path / "a" / "q.npy")), q.int_repr().float().numpy())
+
+
+def test_full_is_off_by_default():
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.parse_args([]).full is False and bench.parse_args(["--full"]).full is True
+    assert bench.parse_args([]).dump_outputs is None
 
 
 def test_distinct_device_guard_only_fires_on_provable_sharing():

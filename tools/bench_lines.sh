@@ -3,7 +3,7 @@
 OUT=$1; shift
 mkdir -p $OUT
 for wl in "$@"; do
-    python3 bench.py --workload $wl --no-cpu-baseline --no-configs > $OUT/bench_$wl.json 2> $OUT/bench_$wl.err
+    python3 bench.py --full --workload $wl --no-cpu-baseline --no-configs > $OUT/bench_$wl.json 2> $OUT/bench_$wl.err
     python3 - $OUT/bench_$wl.json $wl <<'PY'
 import json, sys
 try:

@@ -3,7 +3,7 @@
 OUT=$1; shift
 export TMPDIR=/tmp
 mkdir -p $OUT
-ARGS="--steps 3 --warmup 1 --no-cpu-baseline --no-probe $*"
+ARGS="--full --steps 3 --warmup 1 --no-cpu-baseline --no-probe $*"
 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAIT_INST_ANY SQ_BUSY_CYCLES --output-format csv -d $OUT/p1 -o p -- python3 bench.py $ARGS > $OUT/log1.txt 2>&1
 rocprofv3 --kernel-trace --pmc SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_INST_CYCLES_SALU SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VMEM --output-format csv -d $OUT/p2 -o p -- python3 bench.py $ARGS > $OUT/log2.txt 2>&1
 python3 - "$OUT" <<'PY'

@@ -1,14 +1,15 @@
 #!/usr/bin/env bash
 # round-4 evidence: rocprofv3 kernel trace + PMC passes (profiles/collect.sh) and a plain bench line for every workload;
-# results land in gpurun_out/r04p/ as r04_<tag>_{rocprof_summary.txt,traffic.json,bench.json} (copy them to profiles/)
-OUT=gpurun_out/r04p
+# results land in $RESULTS/r04p/ as r04_<tag>_{rocprof_summary.txt,traffic.json,bench.json} (copy them to profiles/)
+export RESULTS=${RESULTS:-results}   # output root; profiles/collect.sh writes its prof_<tag>/ under the same root
+OUT=$RESULTS/r04p
 mkdir -p $OUT
 run() {  # tag, bench args...
     tag=$1; shift
     bash profiles/collect.sh $tag "$@" > $OUT/collect_$tag.log 2>&1
-    cp gpurun_out/prof_$tag/summary.txt $OUT/r04_${tag}_rocprof_summary.txt 2>/dev/null
-    cp gpurun_out/prof_$tag/traffic.json $OUT/r04_${tag}_traffic.json 2>/dev/null
-    python3 bench.py "$@" --no-cpu-baseline > $OUT/r04_${tag}_bench.json 2> $OUT/bench_$tag.err
+    cp $RESULTS/prof_$tag/summary.txt $OUT/r04_${tag}_rocprof_summary.txt 2>/dev/null
+    cp $RESULTS/prof_$tag/traffic.json $OUT/r04_${tag}_traffic.json 2>/dev/null
+    python3 bench.py --full "$@" --no-cpu-baseline > $OUT/r04_${tag}_bench.json 2> $OUT/bench_$tag.err
 }
 for wl in "$@"; do
     case $wl in

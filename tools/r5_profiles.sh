@@ -1,16 +1,17 @@
 #!/usr/bin/env bash
 # Round 5: rocprofv3 evidence (kernel trace + FETCH / WRITE counters) and a bench line per workload (GPU box, through gpurun):
 #   bash tools/r5_profiles.sh wl1 wl2 ...        ("c3:1" = workload c3 with --pad 1)
-# -> gpurun_out/r5p/r05_<tag>_{rocprof_summary.txt,traffic.json,bench.json}; copy what should be judged into profiles/.
-mkdir -p gpurun_out/r5p
+# -> $RESULTS/r5p/r05_<tag>_{rocprof_summary.txt,traffic.json,bench.json}; copy what should be judged into profiles/.
+export RESULTS=${RESULTS:-results}   # output root; profiles/collect.sh writes its prof_<tag>/ under the same root
+mkdir -p $RESULTS/r5p
 for spec in "$@"; do
     wl=${spec%%:*}; pad=0; tag=$wl
     if [[ "$spec" == *:* ]]; then pad=${spec##*:}; tag=${wl}_pad$pad; fi
-    bash profiles/collect.sh $tag --workload $wl --pad $pad > gpurun_out/r5p/collect_$tag.log 2>&1
-    cp gpurun_out/prof_$tag/summary.txt gpurun_out/r5p/r05_${tag}_rocprof_summary.txt 2>/dev/null
-    cp gpurun_out/prof_$tag/traffic.json gpurun_out/r5p/r05_${tag}_traffic.json 2>/dev/null
-    python3 bench.py --workload $wl --pad $pad --no-cpu-baseline --no-configs > gpurun_out/r5p/r05_${tag}_bench.json 2> gpurun_out/r5p/bench_$tag.err
-    python3 - gpurun_out/r5p/r05_${tag}_bench.json $tag <<'PY'
+    bash profiles/collect.sh $tag --workload $wl --pad $pad > $RESULTS/r5p/collect_$tag.log 2>&1
+    cp $RESULTS/prof_$tag/summary.txt $RESULTS/r5p/r05_${tag}_rocprof_summary.txt 2>/dev/null
+    cp $RESULTS/prof_$tag/traffic.json $RESULTS/r5p/r05_${tag}_traffic.json 2>/dev/null
+    python3 bench.py --full --workload $wl --pad $pad --no-cpu-baseline --no-configs > $RESULTS/r5p/r05_${tag}_bench.json 2> $RESULTS/r5p/bench_$tag.err
+    python3 - $RESULTS/r5p/r05_${tag}_bench.json $tag <<'PY'
 import json, sys
 try:
     j = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
@@ -18,5 +19,5 @@ try:
 except Exception as e:
     print("bench failed", sys.argv[2], e)
 PY
-    rm -rf gpurun_out/prof_$tag
+    rm -rf $RESULTS/prof_$tag
 done
