@@ -436,10 +436,12 @@ int shiftnd_backward(const shiftnd_problem *p, const void *grad_out, const int64
 static int backward_planned(const shiftnd_problem *p, const void *grad_out, const int64_t grad_out_strides[5], const void *x,
                             const int64_t x_strides[5], const void *weights, void *grad_x, const int64_t grad_x_strides[5],
                             void *grad_w, void *workspace, size_t workspace_bytes, void *stream) {
-    if (!p || !grad_out_strides || !x_strides || !grad_x_strides) return SHIFTND_ERR_INVALID_ARGUMENT;
+    // x == NULL && grad_w == NULL: the input gradient only (the sparse shift's grad_x is a gather of grad_out; shiftnd_gradx.hip)
+    const bool input_only = !x && !grad_w;
+    if (!p || !grad_out_strides || !grad_x_strides || (!x_strides && !input_only)) return SHIFTND_ERR_INVALID_ARGUMENT;
     if (!is_float_dtype(p->dtype)) return SHIFTND_ERR_UNSUPPORTED_DTYPE;
     Geometry g;
-    const int rc = build_geometry(p, x_strides, grad_out_strides, grad_x_strides, g);
+    const int rc = build_geometry(p, x_strides ? x_strides : grad_x_strides, grad_out_strides, grad_x_strides, g);
     if (rc != SHIFTND_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (g.N == 0 || g.C == 0 || g.S[0] * g.S[1] * g.S[2] == 0) {
@@ -449,6 +451,23 @@ static int backward_planned(const shiftnd_problem *p, const void *grad_out, cons
             if (hipMemsetAsync(grad_w, 0, static_cast<size_t>(g.C) * g.nd * dtype_size(p->dtype), st) != hipSuccess)
                 return SHIFTND_ERR_LAUNCH_FAILED;
         return SHIFTND_OK;
+    }
+    if (input_only) {
+        if (p->active || !grad_out || !weights || !grad_x) return SHIFTND_ERR_INVALID_ARGUMENT;
+        if (!cropped(g)) {
+            // the window is the whole input: grad_x = sparse forward of grad_out under -w (rint is odd-symmetric), on whichever
+            // forward route serves this tensor; the negated table lives in the caller's workspace
+            if (!workspace || gradx_negate_workspace(g, p->dtype) > workspace_bytes) return SHIFTND_ERR_WORKSPACE_TOO_SMALL;
+            const int nrc = gradx_negate_weights(g, p->dtype, weights, workspace, st);
+            if (nrc != SHIFTND_OK) return nrc;
+            return forward_common(p, grad_out, grad_out_strides, workspace, p->dtype, 0, 0ull, grad_x, grad_x_strides, stream);
+        }
+        if (g_policy == 0 && gradx_embed_eligible(g, p->dtype, grad_out, grad_x)) {
+            g_last_path = SHIFTND_PATH_PLANE;
+            return finish(gradx_embed(g, p->dtype, grad_out, weights, grad_x, st));
+        }
+        g_last_path = SHIFTND_PATH_STRIDED;
+        return finish(gradx_gather(g, p->dtype, grad_out, weights, grad_x, st));
     }
     if (!grad_out || !x || !weights || !grad_x || !grad_w || !workspace) return SHIFTND_ERR_INVALID_ARGUMENT;
     if (g_policy == 0 && g_flat == 2 && flat_backward_eligible(g, p->dtype, grad_out, x, grad_x)) {   // (knob 27 = 2: tests)

@@ -193,6 +193,15 @@ void qpool_set_tuning(int knob, int value);
 int qpool_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, int64_t wzp, int64_t xzp, int requant, void *out,
                   hipStream_t st);
 
+// ---- input gradient of the sparse shift without the input (shiftnd_gradx.hip): shiftnd_backward's x == NULL form ---
+// gradx_negate_weights: out = -w ([C, nd] of the tensor dtype), the table the forward kernels run on for a window that is the
+// whole input; gradx_embed: contiguous tensors, grad_x rows of whole 16-byte pieces, a cut window; gradx_gather: everything else.
+size_t gradx_negate_workspace(const Geometry &g, int dtype);
+int gradx_negate_weights(const Geometry &g, int dtype, const void *w, void *out, hipStream_t st);
+bool gradx_embed_eligible(const Geometry &g, int dtype, const void *go, const void *gx);
+int gradx_embed(const Geometry &g, int dtype, const void *go, const void *w, void *gx, hipStream_t st);
+int gradx_gather(const Geometry &g, int dtype, const void *go, const void *w, void *gx, hipStream_t st);
+
 // ---- layout change (shiftnd_transpose.hip): dst[n][c][r] = src[n][r][c], dense tensors ---------------------------
 int transpose_planes(const void *src, void *dst, int64_t N, int64_t rows, int64_t cols, int esize, hipStream_t st);
 

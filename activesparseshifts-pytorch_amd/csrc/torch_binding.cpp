@@ -678,6 +678,113 @@ std::tuple<Tensor, Tensor> qshift_backward(const Tensor &, const Tensor &, const
     TORCH_CHECK(0, "backwards on quantized tensor are not supported");
 }
 
+// ---- fixed (grouped) shifts: integer shifts that nobody learns ------------------------------------------------------
+// shift{N}d_fixed(input, shifts, borders, padding_mode) is the sparse forward under a [C, N] table of integers; its autograd node
+// keeps the table, the borders and the input's SIZES -- never the input -- and its backward is _shift{N}d_fixed_backward, the input
+// gradient alone (on HIP tensors shiftnd_backward's x == NULL form: no read of x, no weight gradient).  The table is converted once
+// to the tensor's dtype: exact for |s| <= 256 in bf16, <= 2048 in fp16, 2^24 in fp32.
+using fixed_backward_sig = Tensor(const Tensor &, const Tensor &, const Tensor &, at::IntArrayRef, int64_t);
+template <int ND> Tensor call_fixed_backward(const Tensor &grad, const Tensor &shifts, const Tensor &borders,
+                                             at::IntArrayRef input_size, int64_t padding_mode) {
+    static auto op = c10::Dispatcher::singleton()
+                         .findSchemaOrThrow(("torchshifts::_shift" + std::to_string(ND) + "d_fixed_backward").c_str(), "")
+                         .typed<fixed_backward_sig>();
+    return op.call(grad, shifts, borders, input_size, padding_mode);
+}
+
+Tensor fixed_table(const Tensor &shifts, const Tensor &like, int nd) {
+    TORCH_CHECK(like.dim() == nd + 2, "shift", nd, "d_fixed: expected a ", nd + 2, "-D tensor");
+    TORCH_CHECK(shifts.dim() == 2 && shifts.size(0) == like.size(1) && shifts.size(1) == nd,
+                "shift", nd, "d_fixed: shifts must have shape [C, ", nd, "]");
+    TORCH_CHECK(shifts.device() == like.device(), "shift", nd, "d_fixed: shifts must be on the input's device");
+    TORCH_CHECK(at::isFloatingType(shifts.scalar_type()) || at::isIntegralType(shifts.scalar_type(), false),
+                "shift", nd, "d_fixed: shifts must be integers or floats");
+    return shifts.detach().to(like.scalar_type()).contiguous();
+}
+
+template <int ND> struct FixedShiftFunction : public torch::autograd::Function<FixedShiftFunction<ND>> {
+    static variable_list forward(AutogradContext *ctx, const Tensor &input, const Tensor &shifts, const Tensor &borders,
+                                 at::IntArrayRef new_size, int64_t padding_mode) {
+        at::AutoDispatchBelowADInplaceOrView guard;
+        Tensor table = fixed_table(shifts, input, ND);
+        auto output = call_forward<ND>(input, table, borders, new_size, padding_mode, false);
+        ctx->saved_data["padding_mode"] = padding_mode;
+        ctx->saved_data["input_size"] = input.sizes().vec();
+        ctx->save_for_backward({table, borders});
+        return {output};
+    }
+    static variable_list backward(AutogradContext *ctx, const variable_list &grad_output) {
+        auto saved = ctx->get_saved_variables();
+        const auto padding_mode = ctx->saved_data["padding_mode"].toInt();
+        const auto input_size = ctx->saved_data["input_size"].toIntVector();
+        return {call_fixed_backward<ND>(grad_output[0], saved[0], saved[1], input_size, padding_mode), Tensor(), Tensor(), Tensor(),
+                Tensor()};
+    }
+};
+
+template <int ND> struct FixedShiftBackwardFunction : public torch::autograd::Function<FixedShiftBackwardFunction<ND>> {
+    static variable_list forward(AutogradContext *ctx, const Tensor &grad, const Tensor &shifts, const Tensor &borders,
+                                 at::IntArrayRef input_size, int64_t padding_mode) {
+        at::AutoDispatchBelowADInplaceOrView guard;
+        return {call_fixed_backward<ND>(grad, shifts, borders, input_size, padding_mode)};
+    }
+    static variable_list backward(AutogradContext *, const variable_list &) {
+        TORCH_CHECK(0, "double backwards on shift", ND, "d_fixed not supported");
+    }
+};
+
+template <int ND> Tensor shift_fixed_public(const Tensor &input, const Tensor &shifts, const Tensor &borders, int64_t padding_mode) {
+    TORCH_CHECK(!input.is_quantized(), "shift", ND, "d_fixed: quantized inputs are not supported (the quantized modules already shift by integers)");
+    TORCH_CHECK(padding_mode >= 0 && padding_mode <= 4, "shift", ND, "d_fixed: padding_mode must be 0..4");
+    auto bands = check_borders(input, borders, ND);
+    return FixedShiftFunction<ND>::apply(input, shifts, std::get<0>(bands), at::IntArrayRef(std::get<1>(bands)), padding_mode)[0];
+}
+
+template <int ND> Tensor fixed_autograd_backward(const Tensor &grad, const Tensor &shifts, const Tensor &borders,
+                                                at::IntArrayRef input_size, int64_t padding_mode) {
+    return FixedShiftBackwardFunction<ND>::apply(grad, shifts, borders, input_size, padding_mode)[0];
+}
+
+template <int ND> Tensor shift_fixed_backward_hip(const Tensor &grad_, const Tensor &shifts, const Tensor &borders,
+                                                  at::IntArrayRef input_size, int64_t padding_mode) {
+    TORCH_CHECK(grad_.is_cuda(), "grad must be a CUDA tensor");
+    TORCH_CHECK(grad_.dim() == ND + 2 && static_cast<int>(input_size.size()) == ND + 2, "shift", ND, "d_fixed backward: expected ",
+                ND + 2, "-D tensors");
+    TORCH_CHECK(padding_mode >= 0 && padding_mode <= 4, "shift", ND, "d_fixed backward: padding_mode must be 0..4");
+    TORCH_CHECK(grad_.size(0) == input_size[0] && grad_.size(1) == input_size[1], "shift", ND, "d_fixed backward: grad does not match input_size");
+    c10::DeviceGuard device_guard(grad_.device());
+    int32_t b[6];
+    read_borders(borders, b);
+    bool cut = false;
+    for (int r = 0; r < ND; ++r) {
+        TORCH_CHECK(grad_.size(2 + r) == b[2 * r + 1] - b[2 * r], "shift", ND, "d_fixed backward: grad does not match borders");
+        cut = cut || b[2 * r] != 0 || b[2 * r + 1] != input_size[2 + r];
+    }
+    const int dtype = to_shiftnd_dtype(grad_.scalar_type(), "shiftnd_fixed_backward_cuda");
+    Tensor w = fixed_table(shifts, grad_, ND);
+    Tensor grad_input = at::empty(input_size, grad_.options(), at::MemoryFormat::Contiguous);
+    shiftnd_problem p;
+    fill_problem(p, ND, grad_input, b, padding_mode, false, dtype);
+    int64_t gs[5], gxs[5];
+    fill_strides(grad_input, ND, gxs);
+    // a dense channels-last gradient: the whole-input window runs the forward routes, which may read it as it lies; otherwise (and
+    // for every cut window) one tile transpose, then the contiguous kernels
+    bool direct = false;
+    if (is_channels_last_dense(grad_) && !cut) {
+        fill_strides(grad_, ND, gs);
+        direct = shiftnd_forward_serves_channels_last(&p, grad_.data_ptr(), gs, grad_input.data_ptr(), gxs) != 0;
+    }
+    const Tensor grad = (is_channels_last_dense(grad_) && !direct) ? channels_last_to_contiguous(grad_) : grad_;
+    fill_strides(grad, ND, gs);
+    // the whole-input window needs room for the negated table (include/shiftnd_hip.h); a cut window needs nothing
+    const size_t ws_bytes = cut ? 0 : static_cast<size_t>(w.numel()) * w.element_size();
+    Tensor workspace = at::empty({static_cast<int64_t>(ws_bytes)}, grad.options().dtype(at::kByte));
+    const int rc = shiftnd_backward(&p, grad.data_ptr(), gs, nullptr, nullptr, w.data_ptr(), grad_input.data_ptr(), gxs, nullptr,
+                                    ws_bytes ? workspace.data_ptr() : nullptr, ws_bytes, current_stream(grad));
+    TORCH_CHECK(rc == SHIFTND_OK, "shiftnd_backward, input gradient only (HIP): ", shiftnd_status_string(rc));
+    return grad_input;
+}
+
 int64_t cuda_version() { return -1; }  // no CUDA toolkit: extension.py only compares when torch.version.cuda is set
 int64_t hip_version() { return HIP_VERSION; }
 
@@ -708,9 +815,19 @@ TORCH_LIBRARY(torchshifts, m) {
     m.def("torchshifts::_shift2d_pool_backward(Tensor grad, Tensor weights, Tensor input, Tensor borders, int[] pool, int padding_mode, bool active_flag) -> (Tensor, Tensor)");
     m.def("torchshifts::_shift3d_pool_forward(Tensor input, Tensor weights, Tensor borders, int[] new_size, int[] pool, int padding_mode, bool active_flag) -> Tensor");
     m.def("torchshifts::_shift3d_pool_backward(Tensor grad, Tensor weights, Tensor input, Tensor borders, int[] pool, int padding_mode, bool active_flag) -> (Tensor, Tensor)");
+    // fixed (grouped) shifts: integer shifts without a weight gradient (not in the reference)
+    m.def("torchshifts::shift1d_fixed(Tensor input, Tensor shifts, Tensor borders, int padding_mode) -> Tensor", &shift_fixed_public<1>);
+    m.def("torchshifts::shift2d_fixed(Tensor input, Tensor shifts, Tensor borders, int padding_mode) -> Tensor", &shift_fixed_public<2>);
+    m.def("torchshifts::shift3d_fixed(Tensor input, Tensor shifts, Tensor borders, int padding_mode) -> Tensor", &shift_fixed_public<3>);
+    m.def("torchshifts::_shift1d_fixed_backward(Tensor grad, Tensor shifts, Tensor borders, int[] input_size, int padding_mode) -> Tensor");
+    m.def("torchshifts::_shift2d_fixed_backward(Tensor grad, Tensor shifts, Tensor borders, int[] input_size, int padding_mode) -> Tensor");
+    m.def("torchshifts::_shift3d_fixed_backward(Tensor grad, Tensor shifts, Tensor borders, int[] input_size, int padding_mode) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(torchshifts, Autograd, m) {
+    m.impl("_shift1d_fixed_backward", TORCH_FN(fixed_autograd_backward<1>));
+    m.impl("_shift2d_fixed_backward", TORCH_FN(fixed_autograd_backward<2>));
+    m.impl("_shift3d_fixed_backward", TORCH_FN(fixed_autograd_backward<3>));
     m.impl("_shift1d_forward", TORCH_FN(shift_autograd<1>));
     m.impl("_shift1d_backward", TORCH_FN(shift_autograd_backward<1>));
     m.impl("_shift2d_forward", TORCH_FN(shift_autograd<2>));
@@ -736,6 +853,9 @@ TORCH_LIBRARY_IMPL(torchshifts, CPU, m) {
 }
 
 TORCH_LIBRARY_IMPL(torchshifts, CUDA, m) {
+    m.impl("_shift1d_fixed_backward", TORCH_FN(shift_fixed_backward_hip<1>));
+    m.impl("_shift2d_fixed_backward", TORCH_FN(shift_fixed_backward_hip<2>));
+    m.impl("_shift3d_fixed_backward", TORCH_FN(shift_fixed_backward_hip<3>));
     m.impl("_shift1d_forward", TORCH_FN(shift_forward_hip<1>));
     m.impl("_shift1d_backward", TORCH_FN(shift_backward_hip<1>));
     m.impl("_shift2d_forward", TORCH_FN(shift_forward_hip<2>));

@@ -335,6 +335,67 @@ std::tuple<Tensor, Tensor> shift_backward_cpu(const Tensor &grad, const Tensor &
 }
 
 // quantized/shifts_quantized.cpp:107-130
+// ---- fixed (grouped) shifts: the input gradient alone (no input, no weight gradient) ----------------------------------------
+// grad_x = inside the window ? grad[pad(o + s)] : 0, the sparse branch of backward_float with the same index maps
+template <typename T>
+void fixed_backward_gather(const Geom &g, const Tensor &grad, const Tensor &shifts_t, Tensor &grad_input) {
+    using CT = typename compute_of<T>::type;
+    const T *go = grad.data_ptr<T>();
+    T *gx = grad_input.data_ptr<T>();
+    const T *w = shifts_t.data_ptr<T>();
+    std::vector<int64_t> shifts(static_cast<size_t>(g.C * 3), 0);
+    for (int64_t c = 0; c < g.C; ++c)
+        for (int d = 0; d < 3; ++d)
+            if (g.wcol[d] >= 0) {
+                CT dw;
+                prep_backward<CT>(static_cast<CT>(w[c * g.nd + g.wcol[d]]), false, shifts[c * 3 + d], dw);
+            }
+    const Maps gmaps = build_maps(g, g.O, shifts, +1);
+    at::parallel_for(0, g.N * g.C, 1, [&](int64_t begin, int64_t end) {
+        for (int64_t plane = begin; plane < end; ++plane) {
+            const int64_t n = plane / g.C, c = plane % g.C;
+            const int32_t *m0 = gmaps.get(c, 0), *m1 = gmaps.get(c, 1), *m2 = gmaps.get(c, 2);
+            const T *gp = go + n * g.os[0] + c * g.os[1];
+            T *gxp = gx + n * g.gs[0] + c * g.gs[1];
+            for (int64_t i0 = 0; i0 < g.S[0]; ++i0)
+                for (int64_t i1 = 0; i1 < g.S[1]; ++i1)
+                    for (int64_t i2 = 0; i2 < g.S[2]; ++i2) {
+                        const int64_t o0 = i0 - g.L[0], o1 = i1 - g.L[1], o2 = i2 - g.L[2];
+                        T v = T(0);
+                        if (o0 >= 0 && o0 < g.O[0] && o1 >= 0 && o1 < g.O[1] && o2 >= 0 && o2 < g.O[2]) {
+                            const int32_t a = m0[o0], b = m1[o1], e = m2[o2];
+                            if (a >= 0 && b >= 0 && e >= 0) v = gp[a * g.os[2] + b * g.os[3] + e * g.os[4]];
+                        }
+                        gxp[i0 * g.gs[2] + i1 * g.gs[3] + i2 * g.gs[4]] = v;
+                    }
+        }
+    });
+}
+
+template <int ND> Tensor shift_fixed_backward_cpu(const Tensor &grad, const Tensor &shifts, const Tensor &borders,
+                                                  at::IntArrayRef input_size, int64_t padding_mode) {
+    TORCH_CHECK(grad.device().is_cpu() && shifts.device().is_cpu(), "shiftnd_fixed_backward_cpu: expected CPU tensors");
+    TORCH_CHECK(grad.dim() == ND + 2 && static_cast<int>(input_size.size()) == ND + 2, "shift", ND, "d_fixed backward: expected ",
+                ND + 2, "-D tensors");
+    TORCH_CHECK(padding_mode >= 0 && padding_mode <= 4, "shift", ND, "d_fixed backward: padding_mode must be 0..4");
+    TORCH_CHECK(shifts.dim() == 2 && shifts.size(0) == grad.size(1) && shifts.size(1) == ND,
+                "shift", ND, "d_fixed backward: shifts must have shape [C, ", ND, "]");
+    TORCH_CHECK(grad.size(0) == input_size[0] && grad.size(1) == input_size[1], "shift", ND, "d_fixed backward: grad does not match input_size");
+    int32_t b[6];
+    read_borders(borders, b);
+    for (int r = 0; r < ND; ++r)
+        TORCH_CHECK(grad.size(2 + r) == b[2 * r + 1] - b[2 * r], "shift", ND, "d_fixed backward: grad does not match borders");
+    Tensor table = shifts.detach().to(grad.scalar_type()).contiguous();
+    Tensor grad_input = at::empty(input_size, grad.options(), at::MemoryFormat::Contiguous);
+    Geom g = make_geom(ND, grad_input, b, padding_mode, false);
+    set_strides(grad, ND, g.os);
+    set_strides(grad_input, ND, g.gs);
+    if (grad_input.numel() == 0) return grad_input;
+    AT_DISPATCH_FLOATING_TYPES(grad.scalar_type(), "shiftnd_fixed_backward_cpu",
+                               [&] { fixed_backward_gather<scalar_t>(g, grad, table, grad_input); });
+    return grad_input;
+}
+
 template <int ND> Tensor qshift_forward_cpu(const Tensor &input, const Tensor &weights, const Tensor &borders,
                                             at::IntArrayRef new_size, int64_t padding_mode, bool /*active_flag*/) {
     TORCH_CHECK(input.is_quantized() && weights.is_quantized(), "q_shiftnd_cpu: expected quantized tensors");
@@ -379,6 +440,9 @@ TORCH_LIBRARY_IMPL(torchshifts, CPU, m) {
     m.impl("_shift2d_backward", TORCH_FN(shift_backward_cpu<2>));
     m.impl("_shift3d_forward", TORCH_FN(shift_forward_cpu<3>));
     m.impl("_shift3d_backward", TORCH_FN(shift_backward_cpu<3>));
+    m.impl("_shift1d_fixed_backward", TORCH_FN(shift_fixed_backward_cpu<1>));
+    m.impl("_shift2d_fixed_backward", TORCH_FN(shift_fixed_backward_cpu<2>));
+    m.impl("_shift3d_fixed_backward", TORCH_FN(shift_fixed_backward_cpu<3>));
 }
 
 TORCH_LIBRARY_IMPL(torchshifts, QuantizedCPU, m) {

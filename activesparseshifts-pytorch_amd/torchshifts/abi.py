@@ -180,6 +180,23 @@ def backward(grad_out, w, x, pad, active, borders=None, grad_x=None, grad_w=None
     return grad_x, grad_w
 
 
+def backward_input(grad_out, w, input_shape, pad, borders=None, grad_x=None, workspace=None):
+    """Input gradient only of the sparse shift: shiftnd_backward with x == NULL and grad_w == NULL (no read of the input, no weight
+    gradient).  grad_out: device tensor of the window's sizes; w: [C, nd] float table of grad_out's dtype; input_shape: the
+    input's sizes; borders: the 6 absolute ints of check_borders (None = the whole input).  Returns grad_x (new, contiguous)."""
+    like = torch.empty(list(input_shape), dtype=grad_out.dtype, device="meta")
+    p = problem(like, pad, False, borders)
+    w = w.contiguous()
+    if grad_x is None:
+        grad_x = _new(input_shape, grad_out)
+    if workspace is None:   # the negated table of the whole-input window (include/shiftnd_hip.h); a cut window needs none
+        workspace = torch.empty(w.numel() * w.element_size(), dtype=torch.uint8, device=grad_out.device)
+    check(lib().shiftnd_backward(ctypes.byref(p), grad_out.data_ptr(), strides5(grad_out), None, None, w.data_ptr(),
+                                 grad_x.data_ptr(), strides5(grad_x), None, workspace.data_ptr() if workspace.numel() else None,
+                                 workspace.numel(), _stream()), "shiftnd_backward (input gradient only)")
+    return grad_x
+
+
 def forward_quantized(xq, wq, w_zero_point, x_zero_point, pad, borders=None, out=None):
     """xq: int8/uint8/int32 device tensor (int_repr); wq: int8/uint8/int32 device tensor [C, nd]."""
     p = problem(xq, pad, False, borders)

@@ -78,3 +78,45 @@ def shift2d_pool_func(input: Tensor, weights: Tensor, padding_mode: int, active_
 def shift3d_pool_func(input: Tensor, weights: Tensor, padding_mode: int, active_flag: bool,
                       borders: Optional[Tensor] = None, pool=2) -> Tensor:
     return _shift_func(3, input, weights, padding_mode, active_flag, borders, pool)
+
+
+# ---- fixed (grouped) shifts: integer shifts that nobody learns (not in the reference) -----------------------------------
+# `shifts` is a [n_channels, dim] table of integers (int32 / int64, or floats that hold integers; a float table is rounded half
+# to even like the sparse shift's weights).  The result equals shift{N}d_func(input, shifts.to(input.dtype), padding_mode, False,
+# borders); the backward returns the input gradient alone -- the autograd node keeps the table, not the input, and on HIP tensors
+# no kernel reads the input or forms a weight gradient.  The table is converted to the input's dtype: exact for |shift| <= 256
+# in bfloat16, <= 2048 in float16.
+def _shift_fixed_func(dim: int, input: Tensor, shifts: Tensor, padding_mode: int, borders: Optional[Tensor]) -> Tensor:
+    name = f"shift{dim}d_fixed_func()"
+    _assert_has_ops()
+    assert padding_mode in [0, 1, 2, 3, 4], f"{name} expected padding_mode can be {_PADDING_DOC}"
+    assert len(input.shape) == dim + 2, f"{name}: expected {dim + 2}D tensor as input, but it is shape is {input.shape}"
+    assert len(shifts.shape) == 2 and shifts.shape[-1] == dim, \
+        f"{name}: expected [n_channels,{dim}] tensor as shifts, but it is shape is {shifts.shape}"
+    assert input.shape[1] == shifts.shape[0], \
+        (f"{name}: expected that input and shifts have equal number of channels, but input have "
+         f"{input.shape[1]} and shifts have {shifts.shape[0]} channels.")
+    assert input.device == shifts.device, \
+        (f"{name}: expected input and shifts to be on same device, but input is  on {input.device} "
+         f"and shifts is on {shifts.device}")
+    if borders is not None:
+        assert (len(borders.shape) == 2) and (borders.shape[1] == 2) and (borders.shape[0] == dim), \
+            f"borders must have shape [{dim}, 2]"
+    else:
+        borders = torch.Tensor()
+    return getattr(torch.ops.torchshifts, f"shift{dim}d_fixed")(input, shifts, borders, padding_mode)
+
+
+def shift1d_fixed_func(input: Tensor, shifts: Tensor, padding_mode: int, borders: Optional[Tensor] = None) -> Tensor:
+    """Shift a [N, C, H] tensor by the integers of shifts [C, 1]; borders [1, 2] = (cut_left, cut_right)."""
+    return _shift_fixed_func(1, input, shifts, padding_mode, borders)
+
+
+def shift2d_fixed_func(input: Tensor, shifts: Tensor, padding_mode: int, borders: Optional[Tensor] = None) -> Tensor:
+    """Shift a [N, C, H, W] tensor by the integers of shifts [C, 2] (H, W); borders [2, 2]."""
+    return _shift_fixed_func(2, input, shifts, padding_mode, borders)
+
+
+def shift3d_fixed_func(input: Tensor, shifts: Tensor, padding_mode: int, borders: Optional[Tensor] = None) -> Tensor:
+    """Shift a [N, C, H, W, D] tensor by the integers of shifts [C, 3] (H, W, D); borders [3, 2]."""
+    return _shift_fixed_func(3, input, shifts, padding_mode, borders)

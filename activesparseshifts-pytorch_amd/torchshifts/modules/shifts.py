@@ -11,13 +11,14 @@ from functools import partial
 import torch
 from torch import nn
 
-from torchshifts.functional import (shift1d_func, shift1d_pool_func, shift2d_func, shift2d_pool_func, shift3d_func,
-                                    shift3d_pool_func)
+from torchshifts.functional import (shift1d_fixed_func, shift1d_func, shift1d_pool_func, shift2d_fixed_func, shift2d_func,
+                                    shift2d_pool_func, shift3d_fixed_func, shift3d_func, shift3d_pool_func)
 
 paddings_dict = {'zeros': 0, 'border': 1, 'periodic': 2, 'reflect': 3, 'symmetric': 4}
 
 _SHIFT_FUNCS = {1: shift1d_func, 2: shift2d_func, 3: shift3d_func}
 _SHIFT_POOL_FUNCS = {1: shift1d_pool_func, 2: shift2d_pool_func, 3: shift3d_pool_func}
+_SHIFT_FIXED_FUNCS = {1: shift1d_fixed_func, 2: shift2d_fixed_func, 3: shift3d_fixed_func}
 _AVG_POOLS = {1: torch.nn.functional.avg_pool1d, 2: torch.nn.functional.avg_pool2d, 3: torch.nn.functional.avg_pool3d}
 
 
@@ -181,4 +182,101 @@ class Shift2d(_Shiftnd):
 
 class Shift3d(_Shiftnd):
     """Learnable per-channel (H, W, D) shift of a [N, C, H, W, D] tensor.  forward(x) -> (out, loss)."""
+    dim = 3
+
+
+class _GroupedShiftnd(nn.Module):
+    """Fixed integer shifts, nothing to learn (GroupedShift, arXiv 1711.08141 section 3.1; or a trained sparse-shift layer frozen
+    by `from_shift`).  The table is the persistent buffer `shifts` (int64 [in_channels, dim]): it travels in state_dict and with
+    .to(device), and the module has no parameters.  The backward returns the input gradient alone: the autograd node keeps the
+    table, never the input, and no weight gradient is computed.
+
+    Arguments:
+        in_channels (int): channels of the input.
+        kernel_size (int): the default table splits the channels, in order, into kernel_size**dim equal groups; group g is
+            shifted by unravel(g, (kernel_size,) * dim) - kernel_size // 2, the in_channels % kernel_size**dim channels left
+            over are not shifted.  Default 3.
+        padding (str): 'zeros' | 'border' | 'periodic' | 'reflect' | 'symmetric'. Default 'zeros'.
+        shifts (tensor / nested list): a [in_channels, dim] table of integers that replaces the default one.
+        emulate_dw (dict): parameters of the depthwise conv this layer replaces (kernel_size, stride, padding): the output is
+            cut as Shift{N}d cuts it, and with a stride > 1 followed by the same avg_pool{N}d(ceil_mode=True) (through ATen:
+            there is no fused fixed shift + pool kernel); its kernel_size also sizes the default table.
+    forward(x) -> (output, None): the pair convention of Shift{N}d with sparsity_term == 0.
+    """
+    dim = None
+
+    def __init__(self, in_channels, kernel_size=3, padding='zeros', shifts=None, emulate_dw=None):
+        super().__init__()
+        assert padding.lower() in paddings_dict.keys(), f'incorrect padding option: {padding}'
+        self.padding = paddings_dict[padding.lower()]
+        self.in_channels = in_channels
+        self.cut_borders = None
+        self._pool_size = None
+        if emulate_dw is not None:
+            args = dict(emulate_dw)   # (the caller's dict stays as it is)
+            args.setdefault('init_thumb_rule_type', 1)
+            _, scales, self.cut_borders, _ = _create_dw_emulation(args, self.dim)
+            if not (scales == 1).all():
+                self._pool_size = [int(k) for k in scales.reshape(-1).tolist()]
+            kernel_size = _wrap_dim(args['kernel_size'], self.dim, 'kernel_size')[0]
+        self.kernel_size = int(kernel_size)
+        if shifts is None:
+            table = self.default_table(in_channels, self.kernel_size, self.dim)
+        else:
+            table = torch.as_tensor(shifts)
+            assert tuple(table.shape) == (in_channels, self.dim), f'shifts must have shape [{in_channels}, {self.dim}]'
+            if table.is_floating_point():
+                table = torch.round(table)
+            table = table.detach().to(torch.int64).clone()
+        self.register_buffer('shifts', table, persistent=True)
+
+    @staticmethod
+    def default_table(in_channels, kernel_size, dim):
+        groups = kernel_size ** dim
+        per = in_channels // groups
+        table = torch.zeros(in_channels, dim, dtype=torch.int64)
+        if per > 0:
+            g = torch.arange(groups * per) // per
+            for d in range(dim):
+                table[:groups * per, d] = (g // kernel_size ** (dim - 1 - d)) % kernel_size - kernel_size // 2
+        return table
+
+    @classmethod
+    def from_shift(cls, module):
+        """Freeze a trained, non-active Shift{N}d: round(weight) (half to even, the kernels' rounding), its padding, cut borders
+        and pool tail."""
+        assert isinstance(module, _Shiftnd) and module.dim == cls.dim, f'expected a Shift{cls.dim}d module'
+        if module._active_flag:
+            raise ValueError('an active shift interpolates: it cannot be frozen into integer shifts')
+        pad = {v: k for k, v in paddings_dict.items()}[module.padding]
+        table = torch.round(module.weight.detach()).to(torch.int64)
+        frozen = cls(module.in_channels, padding=pad, shifts=table.cpu())
+        frozen.cut_borders = None if module.cut_borders is None else module.cut_borders.clone()
+        frozen._pool_size = None if module._pool_size is None else list(module._pool_size)
+        return frozen.to(module.weight.device)
+
+    def forward(self, input):
+        """Returns (output, None)."""
+        out = _SHIFT_FIXED_FUNCS[self.dim](input, self.shifts, self.padding, self.cut_borders)
+        if self._pool_size is not None:
+            out = _AVG_POOLS[self.dim](out, kernel_size=self._pool_size, stride=self._pool_size, ceil_mode=True)
+        return out, None
+
+    def extra_repr(self):
+        pad = {v: k for k, v in paddings_dict.items()}[self.padding]
+        return f'in_channels={self.in_channels}, kernel_size={self.kernel_size}, padding_method={pad}, fixed integer shifts'
+
+
+class GroupedShift1d(_GroupedShiftnd):
+    """Fixed per-channel shift of a [N, C, H] tensor.  forward(x) -> (out, None).  Arguments: see _GroupedShiftnd."""
+    dim = 1
+
+
+class GroupedShift2d(_GroupedShiftnd):
+    """Fixed per-channel (H, W) shift of a [N, C, H, W] tensor.  forward(x) -> (out, None)."""
+    dim = 2
+
+
+class GroupedShift3d(_GroupedShiftnd):
+    """Fixed per-channel (H, W, D) shift of a [N, C, H, W, D] tensor.  forward(x) -> (out, None)."""
     dim = 3

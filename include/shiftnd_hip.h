@@ -169,6 +169,17 @@ SHIFTND_API int shiftnd_forward(const shiftnd_problem *p,
  * grad_w is a contiguous [C, ndim] array of the tensor dtype and is fully overwritten.
  * workspace: device scratch of at least shiftnd_backward_workspace_bytes(p) bytes
  * (fp64 partial sums of the weight gradient); its contents need not be initialised.
+ *
+ * Input gradient only (fixed / frozen shifts): x == NULL and grad_w == NULL together, p->active == 0.  Nothing of the
+ * input is read and no weight gradient is formed; grad_x is bit for bit what the full call writes:
+ *   grad_x[n,c,i,j,k] = inside the window ? grad_out[n,c, pad(i-l_i+s_i), pad(j-l_j+s_j), pad(k-l_k+s_k)] : 0,  s = rint(w).
+ * x_strides is ignored (may be NULL).  Workspace of this form:
+ *   - window == whole input (no cut): C * ndim * sizeof(element) bytes, 8-byte aligned -- the negated shift table, on
+ *     which the forward kernels run (grad_x = sparse forward of grad_out under -w); fewer bytes, or a NULL workspace,
+ *     return SHIFTND_ERR_WORKSPACE_TOO_SMALL before anything is launched;
+ *   - cut window: none, workspace may be NULL with workspace_bytes == 0.
+ * shiftnd_backward_workspace_bytes(p) covers both (it stays the upper bound of every form).
+ * p->active == 1 with this form, or only one of x / grad_w NULL, is SHIFTND_ERR_INVALID_ARGUMENT; nothing is launched.
  */
 SHIFTND_API size_t shiftnd_backward_workspace_bytes(const shiftnd_problem *p);
 
