@@ -3,6 +3,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <array>
 
 #include "shiftnd_common.hpp"
 #include "shiftnd_launch.hpp"
@@ -71,12 +72,6 @@ bool ragged_rows(const Geometry &g, int dtype) {
     return (g.S[2] * es) % 16 != 0;
 }
 
-bool cropped(const Geometry &g) {
-    for (int d = 0; d < 3; ++d)
-        if (g.L[d] != 0 || g.O[d] != g.S[d]) return true;
-    return false;
-}
-
 // ---------------------------------------------------------------------------------------------
 // The tuning knobs (shiftnd_set_tuning) live in thread-local arrays next to the kernels they shape; this file keeps a
 // thread-local shadow of every value so that a call can be planned under the DEFAULT knobs whatever the calling thread
@@ -85,7 +80,7 @@ bool cropped(const Geometry &g) {
 // default plan instead -- sizing on one thread and running on another can never end in WORKSPACE_TOO_SMALL.
 // ---------------------------------------------------------------------------------------------
 constexpr int kKnobs = 40;
-constexpr int kKnobDefault[kKnobs] = {
+constexpr std::array<int, kKnobs> kKnobDefault = {
     0, 128 * 1024, 4, 2, 1, 0, 1, 0,   //  0..7   plane kernels (g_tune)
     4, 512, 2, 256,                    //  8..11  sweep kernels
     -1, 0, 16, 0,                      // 12..15  sliding-window kernels
@@ -98,8 +93,7 @@ constexpr int kKnobDefault[kKnobs] = {
     0, 0, 0, 0,                        // 32..35  one-step kernels
     0, 0,                              // 36..37  quantized pool
     0, 0};                             // 38      planes per workgroup of the walk kernels (39 unused)
-thread_local int g_knob[kKnobs] = {
-    0, 128 * 1024, 4, 2, 1, 0, 1, 0, 4, 512, 2, 256, -1, 0, 16, 0, 1, 0, 0, 0, 1, 0, 1, 0, 1, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+thread_local std::array<int, kKnobs> g_knob = kKnobDefault;
 
 void apply_knob(int knob, int value) {
     if (knob == 27) { g_flat = value; flat_set_tuning(value); }   // 27: the flat-stream kernels 0 automatic (ragged rows) / 1 never / 2 whenever eligible

@@ -809,29 +809,30 @@ bool flat_common_ok(const Geometry &g, int dtype, const void *a, const void *b) 
     // 32-bit element and byte arithmetic in the kernels
     if (g.N * g.C * g.S[1] * g.S[2] * es >= (1LL << 32) || g.N * g.C * g.O[1] * g.O[2] * es >= (1LL << 32)) return false;
     if (g.N * g.C >= (1LL << 31) || g.S[1] >= (1 << 15) || g.S[2] >= (1 << 15) || g.S[1] * g.S[2] * es >= (1LL << 26)) return false;
-    if (reinterpret_cast<uintptr_t>(a) % 16 || reinterpret_cast<uintptr_t>(b) % 16) return false;
+    if (!aligned_to(a, 16) || !aligned_to(b, 16)) return false;
     return true;
 }
 
-template <typename T, bool ACTIVE, bool SMALL>
-void launch_flat_forward(const FlatParams &p, size_t lds, int pad, hipStream_t st) {
+// flat_forward<T, ACTIVE, PAD, SMALL>; PAD: 0, 1, kPadRT -- periodic / reflect / symmetric are one instantiation that reads p.pad
+template <typename T, bool ACTIVE>
+void launch_flat_forward(const FlatParams &p, const FlatPlan &pl, hipStream_t st) {
     const dim3 grid(p.steps_per_xcd * 8), block(kThreads);
-    switch (pad) {
-    case 0: hipLaunchKernelGGL((flat_forward<T, ACTIVE, 0, SMALL>), grid, block, lds, st, p); break;
-    case 1: hipLaunchKernelGGL((flat_forward<T, ACTIVE, 1, SMALL>), grid, block, lds, st, p); break;
-    default: hipLaunchKernelGGL((flat_forward<T, ACTIVE, kPadRT, SMALL>), grid, block, lds, st, p); break;   // periodic / reflect / symmetric: one instantiation, p.pad
-    }
+    with_bool(pl.small, [&](auto small) {
+        with_pad<0, 1, kPadRT>(p.pad, [&](auto pad) {
+            hipLaunchKernelGGL((flat_forward<T, ACTIVE, decltype(pad)::value, decltype(small)::value>), grid, block, pl.lds, st, p);
+        });
+    });
 }
 
-template <typename T, bool ACTIVE, bool SMALL>
-void launch_flat_backward(const FlatParams &p, const FlatPlan &pl, int pad, int N, void *gw, hipStream_t st) {
+template <typename T, bool ACTIVE>
+void launch_flat_backward(const FlatParams &p, const FlatPlan &pl, int N, void *gw, hipStream_t st) {
     const dim3 grid(p.steps_per_xcd * 8), block(kThreads);
     if (!FLAT_INLINE_PREP) hipLaunchKernelGGL((flat_prep<T>), dim3((p.C + kThreads - 1) / kThreads), block, 0, st, p, ACTIVE ? 1 : 0);
-    switch (pad) {
-    case 0: hipLaunchKernelGGL((flat_backward<T, ACTIVE, 0, SMALL>), grid, block, pl.lds, st, p, pl.gcov_off); break;
-    case 1: hipLaunchKernelGGL((flat_backward<T, ACTIVE, 1, SMALL>), grid, block, pl.lds, st, p, pl.gcov_off); break;
-    default: hipLaunchKernelGGL((flat_backward<T, ACTIVE, kPadRT, SMALL>), grid, block, pl.lds, st, p, pl.gcov_off); break;   // periodic / reflect / symmetric: one instantiation, p.pad
-    }
+    with_bool(pl.small, [&](auto small) {
+        with_pad<0, 1, kPadRT>(p.pad, [&](auto pad) {
+            hipLaunchKernelGGL((flat_backward<T, ACTIVE, decltype(pad)::value, decltype(small)::value>), grid, block, pl.lds, st, p, pl.gcov_off);
+        });
+    });
     hipLaunchKernelGGL((flat_reduce<T>), dim3(p.C), dim3(64), 0, st, p, N, ACTIVE ? 1 : 0, static_cast<typename T::S *>(gw));
 }
 
@@ -885,22 +886,12 @@ int flat_forward(const Geometry &g, int dtype, const void *x, const void *w, int
     fill_params(p, g, es, false, pl);
     const bool active = g.active != 0;
     note_kernel(active ? "flat_active_forward" : "flat_gather_forward");
-    // (the sparse shift is a raw copy: one instantiation per element size)
-#define SHIFTND_FLAT_FWD(TT, ACT) \
-    if (pl.small) launch_flat_forward<TT, ACT, true>(p, pl.lds, g.pad, st); \
-    else launch_flat_forward<TT, ACT, false>(p, pl.lds, g.pad, st);
-    if (!active) {
-        if (es == 2) { SHIFTND_FLAT_FWD(f16_t, false) } else if (es == 4) { SHIFTND_FLAT_FWD(f32_t, false) } else { SHIFTND_FLAT_FWD(f64_t, false) }
-    } else if (dtype == SHIFTND_F32) { SHIFTND_FLAT_FWD(f32_t, true)
-    } else if (dtype == SHIFTND_F64) { SHIFTND_FLAT_FWD(f64_t, true)
-    } else if (dtype == SHIFTND_F16) { SHIFTND_FLAT_FWD(f16_t, true)
-    } else { SHIFTND_FLAT_FWD(bf16_t, true) }
-#undef SHIFTND_FLAT_FWD
+    with_shift_type(active, dtype, [&](auto t, auto act) { launch_flat_forward<tag_type<decltype(t)>, decltype(act)::value>(p, pl, st); });
     return SHIFTND_OK;
 }
 
 bool flat_backward_eligible(const Geometry &g, int dtype, const void *go, const void *x, const void *gx) {
-    if (!flat_common_ok(g, dtype, x, gx) || reinterpret_cast<uintptr_t>(go) % 16) return false;
+    if (!flat_common_ok(g, dtype, x, gx) || !aligned_to(go, 16)) return false;
     if (!dense(g.xs, g.N, g.C, g.S) || !dense(g.os, g.N, g.C, g.O) || !dense(g.gs, g.N, g.C, g.S)) return false;
     return flat_plan(g, dtype_size(dtype), true).ok;
 }
@@ -911,8 +902,7 @@ size_t flat_backward_workspace(const Geometry &g) {
     if (g.N * g.C * g.S[1] * g.S[2] >= (1LL << 32)) return 0;
     const uint64_t total = static_cast<uint64_t>(g.N) * g.C * g.S[1] * g.S[2];
     const uint64_t steps = (total + kThreads * 2 - 1) / (kThreads * 2);   // E = 2 (fp64): the most steps
-    auto up = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
-    return up((steps + static_cast<uint64_t>(g.N) * g.C + 1) * 2 * sizeof(double)) + up(static_cast<size_t>(g.C) * sizeof(FlatDesc));
+    return align_up_256((steps + static_cast<uint64_t>(g.N) * g.C + 1) * 2 * sizeof(double)) + align_up_256(static_cast<size_t>(g.C) * sizeof(FlatDesc));
 }
 
 int flat_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, void *gx, void *gw, void *workspace,
@@ -926,24 +916,13 @@ int flat_backward(const Geometry &g, int dtype, const void *go, const void *x, c
     p.w = w;
     p.wkind = dtype;
     fill_params(p, g, es, true, pl);
-    auto up = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
     p.partials = static_cast<double *>(workspace);
-    p.desc = reinterpret_cast<FlatDesc *>(static_cast<char *>(workspace) + up((pl.steps + static_cast<uint64_t>(g.N) * g.C + 1) * 2 * sizeof(double)));
+    p.desc = reinterpret_cast<FlatDesc *>(static_cast<char *>(workspace) + align_up_256((pl.steps + static_cast<uint64_t>(g.N) * g.C + 1) * 2 * sizeof(double)));
     const bool active = g.active != 0;
     note_kernel("flat_backward");
-#define SHIFTND_FLAT_BWD(TT, ACT) \
-    if (pl.small) launch_flat_backward<TT, ACT, true>(p, pl, g.pad, static_cast<int>(g.N), gw, st); \
-    else launch_flat_backward<TT, ACT, false>(p, pl, g.pad, static_cast<int>(g.N), gw, st);
-#define SHIFTND_FLAT_BWD2(TT) \
-    if (active) { SHIFTND_FLAT_BWD(TT, true) } else { SHIFTND_FLAT_BWD(TT, false) }
-    switch (dtype) {
-    case SHIFTND_F32: SHIFTND_FLAT_BWD2(f32_t) break;
-    case SHIFTND_F64: SHIFTND_FLAT_BWD2(f64_t) break;
-    case SHIFTND_F16: SHIFTND_FLAT_BWD2(f16_t) break;
-    default: SHIFTND_FLAT_BWD2(bf16_t) break;
-    }
-#undef SHIFTND_FLAT_BWD2
-#undef SHIFTND_FLAT_BWD
+    with_float_type(dtype, [&](auto t) {
+        with_bool(active, [&](auto act) { launch_flat_backward<tag_type<decltype(t)>, decltype(act)::value>(p, pl, static_cast<int>(g.N), gw, st); });
+    });
     return SHIFTND_OK;
 }
 

@@ -21,6 +21,16 @@ inline int dtype_size(int dtype) {
     }
 }
 
+// a window: the output is not the whole input (normalised dims: a missing dim has O = S = 1, L = 0)
+inline bool cropped(const Geometry &g) {
+    for (int d = 0; d < 3; ++d)
+        if (g.O[d] != g.S[d] || g.L[d] != 0) return true;
+    return false;
+}
+
+inline size_t align_up_256(size_t v) { return (v + 255) & ~static_cast<size_t>(255); }   // workspace sections
+inline bool aligned_to(const void *p, size_t n) { return reinterpret_cast<uintptr_t>(p) % n == 0; }
+
 // name of the main kernel launched by the last call on this host thread (diagnostics: bench.py matches it
 // against the rocprofv3 kernel trace)
 void note_kernel(const char *name);

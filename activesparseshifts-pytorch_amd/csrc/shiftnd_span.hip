@@ -1673,7 +1673,7 @@ __global__ __launch_bounds__(kThreads) void row_backward(const SpanParams p) {
 }
 
 struct SpanFwdPlan {
-    int ocp, cps, spp, P, wholeP;
+    int ocp, cps, spp, P, wholeP, rsteps;
     uint64_t total;
     size_t lds;
     bool ok;
@@ -1752,11 +1752,10 @@ SpanPlan span_plan(const Geometry &g, int es) {
     s.ndiff = g.nd == 1 ? 1 : (g.nd == 2 ? 2 : 8);
     s.rec = (E + 3 <= 8) ? 8 : 16;
     s.total = static_cast<uint64_t>(g.N) * g.C * s.spp;
-    auto up = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
-    s.off_desc = up(s.total * s.ndiff * sizeof(double));
-    s.off_colx = s.off_desc + up(static_cast<size_t>(g.C) * sizeof(ChanDesc));
-    s.off_colg = s.off_colx + up(static_cast<size_t>(g.C) * s.cpr * s.rec * sizeof(int16_t));
-    s.bytes = s.off_colg + up(static_cast<size_t>(g.C) * s.cpr * s.rec * sizeof(int16_t));
+    s.off_desc = align_up_256(s.total * s.ndiff * sizeof(double));
+    s.off_colx = s.off_desc + align_up_256(static_cast<size_t>(g.C) * sizeof(ChanDesc));
+    s.off_colg = s.off_colx + align_up_256(static_cast<size_t>(g.C) * s.cpr * s.rec * sizeof(int16_t));
+    s.bytes = s.off_colg + align_up_256(static_cast<size_t>(g.C) * s.cpr * s.rec * sizeof(int16_t));
     if (g.nd == 3) {   // crop_backward3: x rows [2][R + 1][cpr] | own rows [R][cpr + 2] | read rows [2][R + 1][cpr + 2]
         const size_t tile = (static_cast<size_t>(2 * (R + 1)) * s.cpr + static_cast<size_t>(R + 2 * (R + 1)) * (s.cpr + 2)) * 16;
         s.lds = 64 + ((tile + 63) & ~static_cast<size_t>(63)) + 64 + (kThreads / 64) * 8 * sizeof(double);
@@ -1822,15 +1821,12 @@ static bool ragged_forward_ok(const Geometry &g, int es) {
 static bool crop_forward3_ok(const Geometry &g, int dtype, const void *x, const void *out) {
     if (g.nd != 3 || dtype > SHIFTND_BF16 || g.K[0] > 0 || (g_step_tune[3] & 1024)) return false;
     const int es = dtype_size(dtype);
-    bool crop3 = false;
-    for (int d = 0; d < 3; ++d) {
+    for (int d = 0; d < 3; ++d)
         if (g.S[d] < 2 || g.O[d] < 2) return false;
-        crop3 = crop3 || g.O[d] != g.S[d] || g.L[d] != 0;
-    }
-    if (!crop3 || (g.S[2] * es) % 16 != 0 || g.S[2] * es / 16 > kThreads || (es == 2 && g.O[2] % 2 != 0)) return false;
+    if (!cropped(g) || (g.S[2] * es) % 16 != 0 || g.S[2] * es / 16 > kThreads || (es == 2 && g.O[2] % 2 != 0)) return false;
     if (g.S[0] * g.S[1] * g.S[2] >= (1LL << 28) || g.O[0] * g.O[1] * g.O[2] >= (1LL << 28)) return false;
     if (!dense(g.xs, g.N, g.C, g.S) || !dense(g.os, g.N, g.C, g.O)) return false;
-    if (reinterpret_cast<uintptr_t>(x) % 16 || reinterpret_cast<uintptr_t>(out) % (es < 4 ? 4 : es)) return false;
+    if (!aligned_to(x, 16) || !aligned_to(out, es < 4 ? 4 : es)) return false;
     const int64_t xcpr = g.S[2] * es / 16, rows = std::max<int64_t>(1, std::min<int64_t>(g.O[1], kThreads / xcpr));
     return g.N * g.C * g.O[0] * ((g.O[1] + rows - 1) / rows) + 8 < (1LL << 31);
 }
@@ -1842,13 +1838,11 @@ static bool crop_rows_forward_ok(const Geometry &g, int dtype, const void *x, co
     if (g.nd != 2 || dtype > SHIFTND_BF16 || dtype == SHIFTND_F64 || g.K[0] > 0 || (g_step_tune[3] & 1024)) return false;
     const int es = dtype_size(dtype);
     if (g.S[0] != 1 || g.O[0] != 1 || g.S[1] < 2 || g.S[2] < 2 || g.O[1] < 2 || g.O[2] < 2) return false;
-    bool crop = false;
-    for (int d = 1; d < 3; ++d) crop = crop || g.O[d] != g.S[d] || g.L[d] != 0;
-    if (!crop || (g.O[1] * g.O[2] * es) % 16 == 0) return false;   // (whole-piece planes: crop_forward)
+    if (!cropped(g) || (g.O[1] * g.O[2] * es) % 16 == 0) return false;   // (whole-piece planes: crop_forward)
     if ((g.S[2] * es) % 16 != 0 || g.S[2] * es / 16 > kThreads || (es == 2 && g.O[2] % 2 != 0)) return false;
     if (g.S[1] * g.S[2] >= (1LL << 28)) return false;
     if (!dense(g.xs, g.N, g.C, g.S) || !dense(g.os, g.N, g.C, g.O)) return false;
-    if (reinterpret_cast<uintptr_t>(x) % 16 || reinterpret_cast<uintptr_t>(out) % 4) return false;
+    if (!aligned_to(x, 16) || !aligned_to(out, 4)) return false;
     const int64_t xcpr = g.S[2] * es / 16, rows = std::max<int64_t>(1, std::min<int64_t>(g.O[1], kThreads / xcpr));
     // (a step is `rows` output rows of ONE plane: planes too small to fill half a workgroup keep the flat-stream kernels, which pack
     //  many planes into a step)
@@ -1865,7 +1859,7 @@ bool span_forward_eligible(const Geometry &g, int dtype, const void *x, const vo
     if (g.S[0] != 1 || g.O[0] != 1 || g.S[1] < 1 || g.S[2] < 1 || g.O[1] < 1 || g.O[2] < 1) return false;
     if (ragged_forward_ok(g, es)) {
         if (!dense(g.xs, g.N, g.C, g.S) || !dense(g.os, g.N, g.C, g.O)) return false;
-        if (reinterpret_cast<uintptr_t>(x) % 16 || reinterpret_cast<uintptr_t>(out) % es) return false;
+        if (!aligned_to(x, 16) || !aligned_to(out, es)) return false;
         const int64_t rows = std::min<int64_t>(g.O[1], kThreads / ((g.S[2] * es + 15) / 16 + 2));
         return g.N * g.C * ((g.O[1] + rows - 1) / rows) + 8 < (1LL << 31);
     }
@@ -1875,19 +1869,17 @@ bool span_forward_eligible(const Geometry &g, int dtype, const void *x, const vo
     if (((g.O[1] * g.O[2] * es) % 16 != 0 && !ragged_row1) || (g.N * g.C * g.S[1] * g.S[2] * es) % 16 != 0) return false;
     if (g.S[1] * g.S[2] >= (1LL << 28) || g.O[1] * g.O[2] >= (1LL << 28)) return false;
     if (!dense(g.xs, g.N, g.C, g.S) || !dense(g.os, g.N, g.C, g.O)) return false;
-    if (reinterpret_cast<uintptr_t>(x) % 16 || reinterpret_cast<uintptr_t>(out) % 16) return false;
+    if (!aligned_to(x, 16) || !aligned_to(out, 16)) return false;
     const SpanFwdPlan s = span_forward_plan(g, es);
     if (!s.ok || s.total + 8 >= (1ull << 31) || s.lds > 64 * 1024) return false;
     const bool served = g.nd == 1 ? (g.S[2] * es) % 16 == 0 : crop_forward_ok(g, es);   // row_forward / crop_forward
     if (!served) return false;
     if (g_step_tune[2] >= 2) return true;
-    bool crop = false;
-    for (int d = 1; d < 3; ++d) crop = crop || g.O[d] != g.S[d] || g.L[d] != 0;
     // cropped 2-D windows on source rows of whole pieces (the aligned ones whose output rows are whole pieces too: the step kernels,
     // asked first) and 1-D rows of at least 128 chunks (same box, N256 C512 L4096: fp32 0.94 -> 0.69 ms, interpolating 0.84 -> 0.69,
     // fp16 0.44 -> 0.35).  Ragged source rows: shiftnd_flat.hip.
     if (g.nd == 1) return g.O[2] * es / 16 >= 128;   // row_forward (short rows: the per-channel kernels)
-    return crop;
+    return cropped(g);
 }
 
 // crop_forward: 2-D, source rows of whole pieces (at most 256), at most four staging rounds
@@ -1923,67 +1915,81 @@ bool span_forward_pooled3_eligible(const Geometry &g, int dtype, const void *x, 
     if ((g.S[2] * es) % 16 != 0 || 3 * (g.S[2] * es / 16) > kThreads) return false;
     if (g.S[0] * g.S[1] * g.S[2] >= (1LL << 28)) return false;
     if (!dense(g.xs, g.N, g.C, g.S)) return false;
-    if (reinterpret_cast<uintptr_t>(x) % 16 || reinterpret_cast<uintptr_t>(out) % (es < 4 ? 4 : es)) return false;
+    if (!aligned_to(x, 16) || !aligned_to(out, es < 4 ? 4 : es)) return false;
     const int64_t xcpr = g.S[2] * es / 16, R = std::max<int64_t>(1, std::min<int64_t>(g.P[1], (kThreads / xcpr - 1) / 2));
     return g.N * g.C * g.P[0] * ((g.P[1] + R - 1) / R) + 8 < (1LL << 31);
 }
 
-int span_forward_pooled3(const Geometry &g, int dtype, const void *x, const void *w, int wkind, void *out, hipStream_t st) {
-    const int es = dtype_size(dtype);
-    SpanFwdParams p{};
+// Geometry + step layout -> SpanFwdParams, for every forward of this file.  `sp`: P, ocp, cps, spp (wholeP, rsteps where the kernel has
+// them); `volume`: the forms with a plane dim (crop_forward3 and its pooled form: S0 / O0 / L0, d_per0, d_rsteps -- the others leave them
+// zero); `row_div`: what d_O2 divides by -- the chunks of an output row where threads map to (row, chunk), else O2.
+static void fill_span_forward(SpanFwdParams &p, const Geometry &g, const SpanFwdPlan &sp, bool volume, int row_div, const void *x,
+                              const void *w, int wkind, void *out) {
     p.x = x;
     p.out = out;
     p.w = w;
     p.wkind = wkind;
     p.C = static_cast<int>(g.C);
-    p.nd = 3;
+    p.nd = g.nd;
     p.pad = g.pad;
-    p.S0 = static_cast<int>(g.S[0]);
     p.S1 = static_cast<int>(g.S[1]);
     p.S2 = static_cast<int>(g.S[2]);
-    p.O0 = static_cast<int>(g.O[0]);
     p.O1 = static_cast<int>(g.O[1]);
     p.O2 = static_cast<int>(g.O[2]);
-    p.L0 = static_cast<int>(g.L[0]);
     p.L1 = static_cast<int>(g.L[1]);
     p.L2 = static_cast<int>(g.L[2]);
+    p.x_plane = g.S[0] * g.S[1] * g.S[2];   // (1-D / 2-D: S0 = O0 = 1)
+    p.o_plane = g.O[0] * g.O[1] * g.O[2];
+    p.ocp = sp.ocp;
+    p.cps = sp.cps;
+    p.spp = sp.spp;
+    p.P = sp.P;
+    p.wholeP = sp.wholeP;
+    const uint64_t total = static_cast<uint64_t>(g.N) * g.C * sp.spp;
+    p.total_steps = static_cast<uint32_t>(total);
+    p.steps_per_xcd = static_cast<uint32_t>((total + 7) / 8);
+    p.d_spp = make_fastdiv(static_cast<uint32_t>(sp.spp));
+    p.d_C = make_fastdiv(static_cast<uint32_t>(p.C));
+    p.d_O2 = make_fastdiv(static_cast<uint32_t>(row_div));
+    p.d_P = make_fastdiv(static_cast<uint32_t>(sp.P));
+    p.d_per1 = make_fastdiv(static_cast<uint32_t>(map_period(p.S1, g.pad)));
+    p.d_per2 = make_fastdiv(static_cast<uint32_t>(map_period(p.S2, g.pad)));
+    if (volume) {
+        p.S0 = static_cast<int>(g.S[0]);
+        p.O0 = static_cast<int>(g.O[0]);
+        p.L0 = static_cast<int>(g.L[0]);
+        p.rsteps = sp.rsteps;
+        p.d_rsteps = make_fastdiv(static_cast<uint32_t>(sp.rsteps));
+        p.d_per0 = make_fastdiv(static_cast<uint32_t>(map_period(p.S0, g.pad)));
+    }
+}
+
+int span_forward_pooled3(const Geometry &g, int dtype, const void *x, const void *w, int wkind, void *out, hipStream_t st) {
+    const int es = dtype_size(dtype);
+    SpanFwdPlan sp{};
+    sp.P = static_cast<int>(g.S[2] * es / 16);                      // pieces per staged source row
+    sp.ocp = static_cast<int>((g.O[2] * es + 15) / 16);             // chunks per virtual output row
+    sp.cps = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(g.P[1], (kThreads / sp.P - 1) / 2)));   // pooled rows per step
+    sp.rsteps = (static_cast<int>(g.P[1]) + sp.cps - 1) / sp.cps;
+    sp.spp = sp.rsteps * static_cast<int>(g.P[0]);
+    SpanFwdParams p{};
+    fill_span_forward(p, g, sp, true, sp.ocp, x, w, wkind, out);
     p.P0 = static_cast<int>(g.P[0]);
     p.P1 = static_cast<int>(g.P[1]);
     p.P2 = static_cast<int>(g.P[2]);
-    p.x_plane = g.S[0] * g.S[1] * g.S[2];
     p.o_plane = g.P[0] * g.P[1] * g.P[2];
-    p.P = static_cast<int>(g.S[2] * es / 16);                      // pieces per staged source row
-    p.ocp = static_cast<int>((g.O[2] * es + 15) / 16);             // chunks per virtual output row
-    p.cps = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(g.P[1], (kThreads / p.P - 1) / 2)));   // pooled rows per step
-    p.rsteps = (p.P1 + p.cps - 1) / p.cps;
-    p.spp = p.rsteps * p.P0;
-    const uint64_t total = static_cast<uint64_t>(g.N) * g.C * p.spp;
-    p.total_steps = static_cast<uint32_t>(total);
-    p.steps_per_xcd = static_cast<uint32_t>((total + 7) / 8);
-    p.d_spp = make_fastdiv(static_cast<uint32_t>(p.spp));
-    p.d_C = make_fastdiv(static_cast<uint32_t>(p.C));
-    p.d_O2 = make_fastdiv(static_cast<uint32_t>(p.ocp));
-    p.d_P = make_fastdiv(static_cast<uint32_t>(p.P));
-    p.d_rsteps = make_fastdiv(static_cast<uint32_t>(p.rsteps));
-    p.d_per0 = make_fastdiv(static_cast<uint32_t>(map_period(p.S0, g.pad)));
-    p.d_per1 = make_fastdiv(static_cast<uint32_t>(map_period(p.S1, g.pad)));
-    p.d_per2 = make_fastdiv(static_cast<uint32_t>(map_period(p.S2, g.pad)));
     const bool act = g.active != 0;
-    const size_t lds = 64 + static_cast<size_t>(act ? 3 : 2) * (2 * p.cps + 1) * p.P * 16 + 64;
+    const size_t lds = 64 + static_cast<size_t>(act ? 3 : 2) * (2 * sp.cps + 1) * sp.P * 16 + 64;
     note_kernel("crop_forward3_pool");
     const dim3 grid(p.steps_per_xcd * 8), block(kThreads);
-#define SHIFTND_CROP3_POOL(TT, ACT) \
-    switch (pad_template(g.pad)) { \
-    case 0: hipLaunchKernelGGL((crop_forward3_pool<TT, ACT, 0>), grid, block, lds, st, p); break; \
-    case 1: hipLaunchKernelGGL((crop_forward3_pool<TT, ACT, 1>), grid, block, lds, st, p); break; \
-    case 2: hipLaunchKernelGGL((crop_forward3_pool<TT, ACT, 2>), grid, block, lds, st, p); break; \
-    default: hipLaunchKernelGGL((crop_forward3_pool<TT, ACT, kPadMirror>), grid, block, lds, st, p); break; \
-    }
-#define SHIFTND_CROP3_POOL_T(TT) \
-    if (act) { SHIFTND_CROP3_POOL(TT, true) } else { SHIFTND_CROP3_POOL(TT, false) }
-    if (dtype == SHIFTND_F32) { SHIFTND_CROP3_POOL_T(f32_t) } else if (dtype == SHIFTND_F16) { SHIFTND_CROP3_POOL_T(f16_t) } else { SHIFTND_CROP3_POOL_T(bf16_t) }
-#undef SHIFTND_CROP3_POOL_T
-#undef SHIFTND_CROP3_POOL
+    // (the pooled forms average: the sparse shift too is one instantiation per dtype -- f32, f16, bf16)
+    with_type<f32_t, f16_t, bf16_t>(dtype, [&](auto t) {
+        with_bool(act, [&](auto a) {
+            with_pad_mirror(g.pad, [&](auto pad) {
+                hipLaunchKernelGGL((crop_forward3_pool<tag_type<decltype(t)>, decltype(a)::value, decltype(pad)::value>), grid, block, lds, st, p);
+            });
+        });
+    });
     return SHIFTND_OK;
 }
 
@@ -1996,7 +2002,7 @@ bool span_forward_pooled_eligible(const Geometry &g, int dtype, const void *x, c
     if (g.S[0] != 1 || g.S[1] != 1 || g.O[0] != 1 || g.O[1] != 1 || g.S[2] < 2 || g.O[2] < 1) return false;
     if ((g.S[2] * es) % 16 != 0 || g.S[2] >= (1LL << 28) || (g.N * g.C * g.S[2] * es) % 16 != 0) return false;
     if (!dense(g.xs, g.N, g.C, g.S)) return false;
-    if (reinterpret_cast<uintptr_t>(x) % 16 || reinterpret_cast<uintptr_t>(out) % (es < 4 ? 4 : es)) return false;
+    if (!aligned_to(x, 16) || !aligned_to(out, es < 4 ? 4 : es)) return false;
     const int64_t ocp = (g.O[2] * es + 15) / 16;
     if (g.N * g.C * ((ocp + kThreads - 1) / kThreads) + 8 >= (1LL << 31)) return false;
     return g_step_tune[2] >= 2 || ocp >= 128;
@@ -2004,172 +2010,76 @@ bool span_forward_pooled_eligible(const Geometry &g, int dtype, const void *x, c
 
 int span_forward_pooled(const Geometry &g, int dtype, const void *x, const void *w, int wkind, void *out, hipStream_t st) {
     const int es = dtype_size(dtype);
+    SpanFwdPlan sp{};
+    sp.ocp = static_cast<int>((g.O[2] * es + 15) / 16);
+    sp.cps = kThreads;
+    sp.spp = (sp.ocp + kThreads - 1) / kThreads;
+    sp.P = kThreads + 2;
     SpanFwdParams p{};
-    p.x = x;
-    p.out = out;
-    p.w = w;
-    p.wkind = wkind;
-    p.C = static_cast<int>(g.C);
-    p.nd = 1;
-    p.S1 = p.O1 = 1;
-    p.S2 = static_cast<int>(g.S[2]);
-    p.O2 = static_cast<int>(g.O[2]);
-    p.L2 = static_cast<int>(g.L[2]);
+    fill_span_forward(p, g, sp, false, static_cast<int>(g.O[2]), x, w, wkind, out);
     p.P2 = static_cast<int>(g.P[2]);
-    p.x_plane = g.S[2];
     p.o_plane = g.P[2];   // (the pooled row)
-    p.ocp = static_cast<int>((g.O[2] * es + 15) / 16);
-    p.cps = kThreads;
-    p.spp = (p.ocp + kThreads - 1) / kThreads;
-    p.P = kThreads + 2;
-    const uint64_t total = static_cast<uint64_t>(g.N) * g.C * p.spp;
-    p.total_steps = static_cast<uint32_t>(total);
-    p.steps_per_xcd = static_cast<uint32_t>((total + 7) / 8);
-    p.d_spp = make_fastdiv(static_cast<uint32_t>(p.spp));
-    p.d_C = make_fastdiv(static_cast<uint32_t>(p.C));
-    p.d_O2 = make_fastdiv(static_cast<uint32_t>(p.O2));
-    p.d_P = make_fastdiv(static_cast<uint32_t>(p.P));
-    p.pad = g.pad;
     p.d_per1 = make_fastdiv(1u);
-    p.d_per2 = make_fastdiv(static_cast<uint32_t>(map_period(p.S2, g.pad)));
     const size_t lds = 64 + (kThreads + 3) * 16 + 64;
     note_kernel("row_forward_pool");
     const dim3 grid(p.steps_per_xcd * 8), block(kThreads);
-#define SHIFTND_ROW_POOL(TT, ACT) \
-    switch (pad_template(g.pad)) { \
-    case 0: hipLaunchKernelGGL((row_forward<TT, ACT, 0, true>), grid, block, lds, st, p); break; \
-    case 1: hipLaunchKernelGGL((row_forward<TT, ACT, 1, true>), grid, block, lds, st, p); break; \
-    case 2: hipLaunchKernelGGL((row_forward<TT, ACT, 2, true>), grid, block, lds, st, p); break; \
-    default: hipLaunchKernelGGL((row_forward<TT, ACT, kPadMirror, true>), grid, block, lds, st, p); break; \
-    }
-#define SHIFTND_ROW_POOL_T(TT) \
-    if (g.active) { SHIFTND_ROW_POOL(TT, true) } else { SHIFTND_ROW_POOL(TT, false) }
-    if (dtype == SHIFTND_F32) { SHIFTND_ROW_POOL_T(f32_t) } else if (dtype == SHIFTND_F16) { SHIFTND_ROW_POOL_T(f16_t) } else { SHIFTND_ROW_POOL_T(bf16_t) }
-#undef SHIFTND_ROW_POOL_T
-#undef SHIFTND_ROW_POOL
+    with_type<f32_t, f16_t, bf16_t>(dtype, [&](auto t) {
+        with_bool(g.active != 0, [&](auto a) {
+            with_pad_mirror(g.pad, [&](auto pad) {
+                hipLaunchKernelGGL((row_forward<tag_type<decltype(t)>, decltype(a)::value, decltype(pad)::value, true>), grid, block, lds, st, p);
+            });
+        });
+    });
     return SHIFTND_OK;
 }
 
 int span_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, void *out, hipStream_t st) {
     const int es = dtype_size(dtype);
+    const bool active = g.active != 0;
+    SpanFwdParams p{};
+    const dim3 block(kThreads);
     const bool rows2 = g.nd == 2 && crop_rows_forward_ok(g, dtype, x, out);
     if (g.nd == 3 || rows2) {   // crop_forward3 (3-D volumes; 2-D windows whose planes are not whole pieces)
-        SpanFwdParams p{};
-        p.x = x;
-        p.out = out;
-        p.w = w;
-        p.wkind = wkind;
-        p.C = static_cast<int>(g.C);
-        p.nd = g.nd;
-        p.pad = g.pad;
-        p.S0 = static_cast<int>(g.S[0]);
-        p.S1 = static_cast<int>(g.S[1]);
-        p.S2 = static_cast<int>(g.S[2]);
-        p.O0 = static_cast<int>(g.O[0]);
-        p.O1 = static_cast<int>(g.O[1]);
-        p.O2 = static_cast<int>(g.O[2]);
-        p.L0 = static_cast<int>(g.L[0]);
-        p.L1 = static_cast<int>(g.L[1]);
-        p.L2 = static_cast<int>(g.L[2]);
-        p.x_plane = g.S[0] * g.S[1] * g.S[2];
-        p.o_plane = g.O[0] * g.O[1] * g.O[2];
-        p.P = static_cast<int>(g.S[2] * es / 16);                      // pieces per staged source row
-        p.ocp = static_cast<int>((g.O[2] * es + 15) / 16);             // output chunks per row
-        p.cps = std::max(1, std::min<int>(static_cast<int>(g.O[1]), kThreads / p.P));   // rows per row group
-        const int kU = (g.active && (es == 4 || g.nd == 2)) ? 2 : 1;                    // row groups per thread (crop_forward3: U)
-        p.rsteps = (p.O1 + kU * p.cps - 1) / (kU * p.cps);
-        p.spp = p.rsteps * p.O0;
-        const uint64_t total = static_cast<uint64_t>(g.N) * g.C * p.spp;
-        p.total_steps = static_cast<uint32_t>(total);
-        p.steps_per_xcd = static_cast<uint32_t>((total + 7) / 8);
-        p.d_spp = make_fastdiv(static_cast<uint32_t>(p.spp));
-        p.d_C = make_fastdiv(static_cast<uint32_t>(p.C));
-        p.d_O2 = make_fastdiv(static_cast<uint32_t>(p.ocp));           // (thread -> (row, chunk))
-        p.d_P = make_fastdiv(static_cast<uint32_t>(p.P));
-        p.d_rsteps = make_fastdiv(static_cast<uint32_t>(p.rsteps));
-        p.d_per0 = make_fastdiv(static_cast<uint32_t>(map_period(p.S0, g.pad)));
-        p.d_per1 = make_fastdiv(static_cast<uint32_t>(map_period(p.S1, g.pad)));
-        p.d_per2 = make_fastdiv(static_cast<uint32_t>(map_period(p.S2, g.pad)));
-        const bool act = g.active != 0;
-        const size_t lds = 64 + static_cast<size_t>(act ? 2 : 1) * (kU * p.cps + 1) * p.P * 16 + 64;
-        if (rows2) note_kernel(act ? "crop_active_forward_rows" : "crop_gather_forward_rows");
-        else note_kernel(act ? "crop_active_forward3" : "crop_gather_forward3");
-        const dim3 grid(p.steps_per_xcd * 8), block(kThreads);
-#define SHIFTND_CROP3_FWD_ND(TT, ACT, NDV) \
-        switch (pad_template(g.pad)) { \
-        case 0: hipLaunchKernelGGL((crop_forward3<TT, ACT, 0, NDV>), grid, block, lds, st, p); break; \
-        case 1: hipLaunchKernelGGL((crop_forward3<TT, ACT, 1, NDV>), grid, block, lds, st, p); break; \
-        case 2: hipLaunchKernelGGL((crop_forward3<TT, ACT, 2, NDV>), grid, block, lds, st, p); break; \
-        default: hipLaunchKernelGGL((crop_forward3<TT, ACT, kPadMirror, NDV>), grid, block, lds, st, p); break; \
-        }
-        if (rows2) {   // 2- and 4-byte elements
-            if (!act) {
-                if (es == 2) { SHIFTND_CROP3_FWD_ND(f16_t, false, 2) } else { SHIFTND_CROP3_FWD_ND(f32_t, false, 2) }
-            } else if (dtype == SHIFTND_F32) { SHIFTND_CROP3_FWD_ND(f32_t, true, 2)
-            } else if (dtype == SHIFTND_F16) { SHIFTND_CROP3_FWD_ND(f16_t, true, 2)
-            } else { SHIFTND_CROP3_FWD_ND(bf16_t, true, 2) }
-            return SHIFTND_OK;
-        }
-#define SHIFTND_CROP3_FWD(TT, ACT) SHIFTND_CROP3_FWD_ND(TT, ACT, 3)
-        if (!act) {   // a raw copy (the weights are widened by their own dtype, p.wkind): one instantiation per element size
-            if (es == 2) { SHIFTND_CROP3_FWD(f16_t, false) } else if (es == 4) { SHIFTND_CROP3_FWD(f32_t, false) } else { SHIFTND_CROP3_FWD(f64_t, false) }
-        } else if (dtype == SHIFTND_F32) { SHIFTND_CROP3_FWD(f32_t, true)
-        } else if (dtype == SHIFTND_F64) { SHIFTND_CROP3_FWD(f64_t, true)
-        } else if (dtype == SHIFTND_F16) { SHIFTND_CROP3_FWD(f16_t, true)
-        } else { SHIFTND_CROP3_FWD(bf16_t, true) }
-#undef SHIFTND_CROP3_FWD
-#undef SHIFTND_CROP3_FWD_ND
+        SpanFwdPlan sp{};
+        sp.P = static_cast<int>(g.S[2] * es / 16);                      // pieces per staged source row
+        sp.ocp = static_cast<int>((g.O[2] * es + 15) / 16);             // output chunks per row
+        sp.cps = std::max(1, std::min<int>(static_cast<int>(g.O[1]), kThreads / sp.P));   // rows per row group
+        const int kU = (active && (es == 4 || g.nd == 2)) ? 2 : 1;                        // row groups per thread (crop_forward3: U)
+        sp.rsteps = (static_cast<int>(g.O[1]) + kU * sp.cps - 1) / (kU * sp.cps);
+        sp.spp = sp.rsteps * static_cast<int>(g.O[0]);
+        fill_span_forward(p, g, sp, true, sp.ocp, x, w, wkind, out);   // (d_O2: thread -> (row, chunk))
+        const size_t lds = 64 + static_cast<size_t>(active ? 2 : 1) * (kU * sp.cps + 1) * sp.P * 16 + 64;
+        if (rows2) note_kernel(active ? "crop_active_forward_rows" : "crop_gather_forward_rows");
+        else note_kernel(active ? "crop_active_forward3" : "crop_gather_forward3");
+        const dim3 grid(p.steps_per_xcd * 8);
+        with_shift_type(active, dtype, [&](auto t, auto a) {
+            using T = tag_type<decltype(t)>;
+            with_bool(rows2, [&](auto two) {
+                constexpr int NDV = decltype(two)::value ? 2 : 3;
+                if constexpr (NDV == 3 || sizeof(typename T::S) <= 4) {   // (the 2-D form: 2- and 4-byte elements)
+                    with_pad_mirror(g.pad, [&](auto pad) {
+                        hipLaunchKernelGGL((crop_forward3<T, decltype(a)::value, decltype(pad)::value, NDV>), grid, block, lds, st, p);
+                    });
+                }
+            });
+        });
         return SHIFTND_OK;
     }
     if (ragged_forward_ok(g, es)) {
-        SpanFwdParams p{};
-        p.x = x;
-        p.out = out;
-        p.w = w;
-        p.wkind = wkind;
-        p.C = static_cast<int>(g.C);
-        p.nd = g.nd;
-        p.S1 = static_cast<int>(g.S[1]);
-        p.S2 = static_cast<int>(g.S[2]);
-        p.O1 = static_cast<int>(g.O[1]);
-        p.O2 = static_cast<int>(g.O[2]);
-        p.L1 = static_cast<int>(g.L[1]);
-        p.L2 = static_cast<int>(g.L[2]);
-        p.x_plane = g.S[1] * g.S[2];
-        p.o_plane = g.O[1] * g.O[2];
-        const int xcpr = static_cast<int>((g.S[2] * es + 15) / 16);
-        p.P = xcpr + 2;                                                 // pieces per staged source row
-        p.ocp = static_cast<int>((g.O[2] * es + 15) / 16);              // output chunks per row
-        p.cps = std::max(1, std::min<int>(static_cast<int>(g.O[1]), kThreads / p.P));   // rows per step
-        p.spp = (p.O1 + p.cps - 1) / p.cps;
-        const uint64_t total = static_cast<uint64_t>(g.N) * g.C * p.spp;
-        p.total_steps = static_cast<uint32_t>(total);
-        p.steps_per_xcd = static_cast<uint32_t>((total + 7) / 8);
-        p.d_spp = make_fastdiv(static_cast<uint32_t>(p.spp));
-        p.d_C = make_fastdiv(static_cast<uint32_t>(p.C));
-        p.d_O2 = make_fastdiv(static_cast<uint32_t>(p.ocp));            // (ragged_forward: thread -> (row, chunk))
-        p.d_P = make_fastdiv(static_cast<uint32_t>(p.P));
-        p.pad = g.pad;
-        p.d_per1 = make_fastdiv(static_cast<uint32_t>(map_period(p.S1, g.pad)));
-        p.d_per2 = make_fastdiv(static_cast<uint32_t>(map_period(p.S2, g.pad)));
-        const size_t lds = 64 + static_cast<size_t>(p.cps + 1) * p.P * 16 + 64;
-        const bool act = g.active != 0;
-        note_kernel(act ? "ragged_active_forward" : "ragged_gather_forward");
-        const dim3 grid(p.steps_per_xcd * 8), block(kThreads);
-#define SHIFTND_RAG_FWD(TT, ACT) \
-        switch (pad_template(g.pad)) { \
-        case 0: hipLaunchKernelGGL((ragged_forward<TT, ACT, 0>), grid, block, lds, st, p); break; \
-        case 1: hipLaunchKernelGGL((ragged_forward<TT, ACT, 1>), grid, block, lds, st, p); break; \
-        case 2: hipLaunchKernelGGL((ragged_forward<TT, ACT, 2>), grid, block, lds, st, p); break; \
-        default: hipLaunchKernelGGL((ragged_forward<TT, ACT, kPadMirror>), grid, block, lds, st, p); break; \
-        }
-        if (!act) {   // a raw copy: one instantiation per element size
-            if (es == 2) { SHIFTND_RAG_FWD(f16_t, false) } else if (es == 4) { SHIFTND_RAG_FWD(f32_t, false) } else { SHIFTND_RAG_FWD(f64_t, false) }
-        } else if (dtype == SHIFTND_F32) { SHIFTND_RAG_FWD(f32_t, true)
-        } else if (dtype == SHIFTND_F64) { SHIFTND_RAG_FWD(f64_t, true)
-        } else if (dtype == SHIFTND_F16) { SHIFTND_RAG_FWD(f16_t, true)
-        } else { SHIFTND_RAG_FWD(bf16_t, true) }
-#undef SHIFTND_RAG_FWD
+        SpanFwdPlan sp{};
+        sp.P = static_cast<int>((g.S[2] * es + 15) / 16) + 2;            // pieces per staged source row
+        sp.ocp = static_cast<int>((g.O[2] * es + 15) / 16);              // output chunks per row
+        sp.cps = std::max(1, std::min<int>(static_cast<int>(g.O[1]), kThreads / sp.P));   // rows per step
+        sp.spp = (static_cast<int>(g.O[1]) + sp.cps - 1) / sp.cps;
+        fill_span_forward(p, g, sp, false, sp.ocp, x, w, wkind, out);    // (d_O2: thread -> (row, chunk))
+        const size_t lds = 64 + static_cast<size_t>(sp.cps + 1) * sp.P * 16 + 64;
+        note_kernel(active ? "ragged_active_forward" : "ragged_gather_forward");
+        const dim3 grid(p.steps_per_xcd * 8);
+        with_shift_type(active, dtype, [&](auto t, auto a) {
+            with_pad_mirror(g.pad, [&](auto pad) {
+                hipLaunchKernelGGL((ragged_forward<tag_type<decltype(t)>, decltype(a)::value, decltype(pad)::value>), grid, block, lds, st, p);
+            });
+        });
         return SHIFTND_OK;
     }
     SpanFwdPlan sp = span_forward_plan(g, es);
@@ -2179,7 +2089,6 @@ int span_forward(const Geometry &g, int dtype, const void *x, const void *w, int
         sp.wholeP = 0;
         sp.cps = kThreads;
         sp.spp = (sp.ocp + kThreads - 1) / kThreads;
-        sp.total = static_cast<uint64_t>(g.N) * g.C * sp.spp;
         sp.lds = 64 + (kThreads + 3) * 16 + 64;
     }
     const bool lean = crop_forward_ok(g, es);
@@ -2190,78 +2099,30 @@ int span_forward(const Geometry &g, int dtype, const void *x, const void *w, int
         sp.P = sp.wholeP = static_cast<int>(g.S[2] * es / 16);
         sp.cps = cropU * kThreads;
         sp.spp = (sp.ocp + sp.cps - 1) / sp.cps;
-        sp.total = static_cast<uint64_t>(g.N) * g.C * sp.spp;
         sp.lds = 64 + ((static_cast<size_t>(rows) * sp.P * 16 + 63) & ~static_cast<size_t>(63)) + 64;
     }
-    SpanFwdParams p{};
-    p.x = x;
-    p.out = out;
-    p.w = w;
-    p.wkind = wkind;
-    p.C = static_cast<int>(g.C);
-    p.nd = g.nd;
-    p.S1 = static_cast<int>(g.S[1]);
-    p.S2 = static_cast<int>(g.S[2]);
-    p.O1 = static_cast<int>(g.O[1]);
-    p.O2 = static_cast<int>(g.O[2]);
-    p.L1 = static_cast<int>(g.L[1]);
-    p.L2 = static_cast<int>(g.L[2]);
-    p.x_plane = g.S[1] * g.S[2];
-    p.o_plane = g.O[1] * g.O[2];
-    p.ocp = sp.ocp;
-    p.cps = sp.cps;
-    p.spp = sp.spp;
-    p.P = sp.P;
-    p.wholeP = sp.wholeP;
-    p.total_steps = static_cast<uint32_t>(sp.total);
-    p.steps_per_xcd = static_cast<uint32_t>((sp.total + 7) / 8);
-    p.d_spp = make_fastdiv(static_cast<uint32_t>(sp.spp));
-    p.d_C = make_fastdiv(static_cast<uint32_t>(p.C));
-    p.d_O2 = make_fastdiv(static_cast<uint32_t>(p.O2));
-    p.d_P = make_fastdiv(static_cast<uint32_t>(sp.P));
-    p.pad = g.pad;
-    p.d_per1 = make_fastdiv(static_cast<uint32_t>(map_period(p.S1, g.pad)));
-    p.d_per2 = make_fastdiv(static_cast<uint32_t>(map_period(p.S2, g.pad)));
-    const bool active = g.active != 0;
+    fill_span_forward(p, g, sp, false, static_cast<int>(g.O[2]), x, w, wkind, out);
+    const dim3 grid(p.steps_per_xcd * 8);
     if (row1d) {
         note_kernel(active ? "row_active_forward" : "row_gather_forward");
-        const dim3 grid(p.steps_per_xcd * 8), block(kThreads);
-#define SHIFTND_ROW_FWD(TT, ACT) \
-        switch (pad_template(g.pad)) { \
-        case 0: hipLaunchKernelGGL((row_forward<TT, ACT, 0>), grid, block, sp.lds, st, p); break; \
-        case 1: hipLaunchKernelGGL((row_forward<TT, ACT, 1>), grid, block, sp.lds, st, p); break; \
-        case 2: hipLaunchKernelGGL((row_forward<TT, ACT, 2>), grid, block, sp.lds, st, p); break; \
-        default: hipLaunchKernelGGL((row_forward<TT, ACT, kPadMirror>), grid, block, sp.lds, st, p); break; \
-        }
-        if (!active) {
-            if (es == 2) { SHIFTND_ROW_FWD(f16_t, false) } else if (es == 4) { SHIFTND_ROW_FWD(f32_t, false) } else { SHIFTND_ROW_FWD(f64_t, false) }
-        } else if (dtype == SHIFTND_F32) { SHIFTND_ROW_FWD(f32_t, true)
-        } else if (dtype == SHIFTND_F64) { SHIFTND_ROW_FWD(f64_t, true)
-        } else if (dtype == SHIFTND_F16) { SHIFTND_ROW_FWD(f16_t, true)
-        } else { SHIFTND_ROW_FWD(bf16_t, true) }
-#undef SHIFTND_ROW_FWD
+        with_shift_type(active, dtype, [&](auto t, auto a) {
+            with_pad_mirror(g.pad, [&](auto pad) {
+                hipLaunchKernelGGL((row_forward<tag_type<decltype(t)>, decltype(a)::value, decltype(pad)::value>), grid, block, sp.lds, st, p);
+            });
+        });
         return SHIFTND_OK;
     }
     if (lean) {
         note_kernel(active ? "crop_active_forward" : "crop_gather_forward");
-        const dim3 grid(p.steps_per_xcd * 8), block(kThreads);
-#define SHIFTND_CROP_FWD_U(TT, ACT, UU) \
-        switch (pad_template(g.pad)) { \
-        case 0: hipLaunchKernelGGL((crop_forward<TT, ACT, 0, UU>), grid, block, sp.lds, st, p); break; \
-        case 1: hipLaunchKernelGGL((crop_forward<TT, ACT, 1, UU>), grid, block, sp.lds, st, p); break; \
-        case 2: hipLaunchKernelGGL((crop_forward<TT, ACT, 2, UU>), grid, block, sp.lds, st, p); break; \
-        default: hipLaunchKernelGGL((crop_forward<TT, ACT, kPadMirror, UU>), grid, block, sp.lds, st, p); break; \
-        }
-#define SHIFTND_CROP_FWD(TT, ACT) \
-        if (ACT && cropU == 2) { SHIFTND_CROP_FWD_U(TT, ACT, (ACT ? 2 : 1)) } else { SHIFTND_CROP_FWD_U(TT, ACT, 1) }
-        if (!active) {   // a raw copy: one instantiation per element size
-            if (es == 2) { SHIFTND_CROP_FWD(f16_t, false) } else if (es == 4) { SHIFTND_CROP_FWD(f32_t, false) } else { SHIFTND_CROP_FWD(f64_t, false) }
-        } else if (dtype == SHIFTND_F32) { SHIFTND_CROP_FWD(f32_t, true)
-        } else if (dtype == SHIFTND_F64) { SHIFTND_CROP_FWD(f64_t, true)
-        } else if (dtype == SHIFTND_F16) { SHIFTND_CROP_FWD(f16_t, true)
-        } else { SHIFTND_CROP_FWD(bf16_t, true) }
-#undef SHIFTND_CROP_FWD
-#undef SHIFTND_CROP_FWD_U
+        with_shift_type(active, dtype, [&](auto t, auto a) {
+            constexpr bool ACT = decltype(a)::value;
+            with_bool(ACT && cropU == 2, [&](auto two) {   // two chunks per thread: the interpolating shift only
+                constexpr int U = (ACT && decltype(two)::value) ? 2 : 1;
+                with_pad_mirror(g.pad, [&](auto pad) {
+                    hipLaunchKernelGGL((crop_forward<tag_type<decltype(t)>, ACT, decltype(pad)::value, U>), grid, block, sp.lds, st, p);
+                });
+            });
+        });
         return SHIFTND_OK;
     }
     return SHIFTND_ERR_INVALID_ARGUMENT;   // (span_forward_eligible admits nothing else)
@@ -2271,24 +2132,20 @@ int span_forward(const Geometry &g, int dtype, const void *x, const void *w, int
 bool span_backward_eligible(const Geometry &g, int dtype, const void *go, const void *x, const void *gx) {
     if (g_step_tune[0] == 1 || !span_geometry_ok(g, dtype)) return false;
     if (!dense(g.xs, g.N, g.C, g.S) || !dense(g.os, g.N, g.C, g.O) || !dense(g.gs, g.N, g.C, g.S)) return false;
-    if (reinterpret_cast<uintptr_t>(go) % 16 || reinterpret_cast<uintptr_t>(x) % 16 || reinterpret_cast<uintptr_t>(gx) % 16) return false;
+    if (!aligned_to(go, 16) || !aligned_to(x, 16) || !aligned_to(gx, 16)) return false;
     // (crop_backward<.., PAD = 0> reads every chunk through an affine column state; a window one column wide ignores the shift and
     //  is not one)
     if (g.nd == 2 && g.pad == 0 && g.O[2] == 1) return false;
     if (g.nd == 3) {   // crop_backward3: cropped volumes only (the walk kernels take the others); knob 35 bit 10 keeps the plane kernels
-        bool crop3 = false;
-        for (int d = 0; d < 3; ++d) crop3 = crop3 || g.O[d] != g.S[d] || g.L[d] != 0;
-        return crop3 && !(g_step_tune[3] & 1024);
+        return cropped(g) && !(g_step_tune[3] & 1024);
     }
     if (g_step_tune[0] == 2) return true;
     const int es = dtype_size(dtype);
     if (g.nd == 1) return g.S[2] * es / 16 >= 128;   // (short rows: one row per workgroup would leave most lanes idle)
-    bool crop = false;
-    for (int d = 1; d < 3; ++d) crop = crop || g.O[d] != g.S[d] || g.L[d] != 0;
     // ragged x rows of at least 8 chunks (62 x 62, 222 x 222 fp32 ...): the row-relative form; shorter rows (14 x 14, 7 x 7) leave most
     // of a workgroup's lanes idle here -- whole planes through the flat-stream kernels
     if ((g.S[2] * es) % 16 != 0) return g.S[2] * es >= 8 * 16 && g.S[1] >= 16;
-    return crop;   // (uncropped 2-D: step_backward)
+    return cropped(g);   // (uncropped 2-D: step_backward)
 }
 
 size_t span_backward_workspace(const Geometry &g, int dtype) { return span_geometry_ok(g, dtype) ? span_plan(g, dtype_size(dtype)).bytes : 0; }
@@ -2298,13 +2155,11 @@ size_t span_backward_workspace(const Geometry &g, int dtype) { return span_geome
 bool span_backward_pooled_eligible(const Geometry &g, int dtype, const void *go, const void *x, const void *gx) {
     if (g_step_tune[0] == 1 || !span_geometry_ok(g, dtype, true)) return false;
     if (!dense(g.xs, g.N, g.C, g.S) || !dense(g.gs, g.N, g.C, g.S)) return false;
-    if (reinterpret_cast<uintptr_t>(go) % dtype_size(dtype) || reinterpret_cast<uintptr_t>(x) % 16 || reinterpret_cast<uintptr_t>(gx) % 16) return false;
+    if (!aligned_to(go, dtype_size(dtype)) || !aligned_to(x, 16) || !aligned_to(gx, 16)) return false;
     if (g.pad == 0 && g.O[2] == 1) return false;   // (as span_backward_eligible: the affine column state)
     if (g.nd == 1) return g.S[2] * dtype_size(dtype) / 16 >= 128 || g_step_tune[0] == 2;   // (short rows: the per-channel kernels, as unpooled)
     if (g.nd == 3) {   // cropped volumes (the walk takes the others), as crop_backward3
-        bool crop3 = false;
-        for (int d = 0; d < 3; ++d) crop3 = crop3 || g.O[d] != g.S[d] || g.L[d] != 0;
-        return crop3 && !(g_step_tune[3] & 1024);
+        return cropped(g) && !(g_step_tune[3] & 1024);
     }
     return true;
 }
@@ -2313,32 +2168,29 @@ size_t span_backward_pooled_workspace(const Geometry &g, int dtype) { return spa
 template <typename T, int ND, bool XRAG = false, bool POOL = false>
 static void launch_span_backward(const SpanParams &p, const SpanPlan &sp, bool active, void *gw, hipStream_t st) {
     const dim3 grid(p.steps_per_xcd * 8), block(kThreads);
-#define SHIFTND_SPAN_PAD(ACT, PADV) \
-    case PADV: \
-        if constexpr (ND == 2 && sizeof(typename T::S) <= 4 && ACT) { \
-            hipLaunchKernelGGL((crop_backward<T, ACT, PADV, XRAG, POOL, 2>), grid, block, sp.lds, st, p); \
-        } else if constexpr (ND == 2 && sizeof(typename T::S) <= 4) { \
-            if (sp.U == 2) hipLaunchKernelGGL((crop_backward<T, ACT, PADV, XRAG, POOL, 2>), grid, block, sp.lds, st, p); \
-            else hipLaunchKernelGGL((crop_backward<T, ACT, PADV, XRAG, POOL, 1>), grid, block, sp.lds, st, p); \
-        } else if constexpr (ND == 2) { \
-            hipLaunchKernelGGL((crop_backward<T, ACT, PADV, XRAG, POOL>), grid, block, sp.lds, st, p); \
-        } else if constexpr (ND == 3) { \
-            hipLaunchKernelGGL((crop_backward3<T, ACT, PADV, POOL>), grid, block, sp.lds, st, p); \
-        } else { \
-            hipLaunchKernelGGL((row_backward<T, ACT, PADV, POOL>), grid, block, sp.lds, st, p); \
-        } \
-        break;
     // (the channel descriptors come from span_prep for every padding: computing them in crop_backward itself -- tried in round 5 to save
     //  the 4.5 us launch -- put weight loads and 64-bit shift arithmetic in front of every one-step workgroup's first DMA: N64 C256
     //  224x224 cut 1/1 fp32 1.65 -> 2.02 ms)
-    if (active) {
-        hipLaunchKernelGGL((span_prep<T>), dim3(p.C), block, 0, st, p, true);
-        switch (pad_template(p.pad)) { SHIFTND_SPAN_PAD(true, 0) SHIFTND_SPAN_PAD(true, 1) SHIFTND_SPAN_PAD(true, 2) default: SHIFTND_SPAN_PAD(true, 3) }
-    } else {
-        hipLaunchKernelGGL((span_prep<T>), dim3(p.C), block, 0, st, p, false);
-        switch (pad_template(p.pad)) { SHIFTND_SPAN_PAD(false, 0) SHIFTND_SPAN_PAD(false, 1) SHIFTND_SPAN_PAD(false, 2) default: SHIFTND_SPAN_PAD(false, 3) }
-    }
-#undef SHIFTND_SPAN_PAD
+    hipLaunchKernelGGL((span_prep<T>), dim3(p.C), block, 0, st, p, active);
+    with_bool(active, [&](auto act) {
+        constexpr bool ACT = decltype(act)::value;
+        with_pad_mirror(p.pad, [&](auto pad) {
+            constexpr int PAD = decltype(pad)::value;
+            if constexpr (ND == 2 && sizeof(typename T::S) <= 4) {
+                // two row groups per thread (span_plan: U); the interpolating shift of 4- / 2-byte elements has no one-group instantiation
+                with_bool(ACT || sp.U == 2, [&](auto two) {
+                    constexpr int U = (ACT || decltype(two)::value) ? 2 : 1;
+                    hipLaunchKernelGGL((crop_backward<T, ACT, PAD, XRAG, POOL, U>), grid, block, sp.lds, st, p);
+                });
+            } else if constexpr (ND == 2) {
+                hipLaunchKernelGGL((crop_backward<T, ACT, PAD, XRAG, POOL>), grid, block, sp.lds, st, p);
+            } else if constexpr (ND == 3) {
+                hipLaunchKernelGGL((crop_backward3<T, ACT, PAD, POOL>), grid, block, sp.lds, st, p);
+            } else {
+                hipLaunchKernelGGL((row_backward<T, ACT, PAD, POOL>), grid, block, sp.lds, st, p);
+            }
+        });
+    });
     // the channel sums and the blends: step_reduce reads the record layout through StepParams
     StepParams r{};
     r.partials = p.partials;
@@ -2408,64 +2260,27 @@ int span_backward(const Geometry &g, int dtype, const void *go, const void *x, c
     p.d_per0x = make_fastdiv(static_cast<uint32_t>(map_period(p.S0, g.pad)));
     p.d_per0g = make_fastdiv(static_cast<uint32_t>(map_period(p.O0, g.pad)));
     const bool active = g.active != 0;
-    if (g.nd == 3 && pooled) {
-        note_kernel("crop_backward3_pool");
-        switch (dtype) {
-        case SHIFTND_F32: launch_span_backward<f32_t, 3, false, true>(p, sp, active, gw, st); break;
-        case SHIFTND_F16: launch_span_backward<f16_t, 3, false, true>(p, sp, active, gw, st); break;
-        default: launch_span_backward<bf16_t, 3, false, true>(p, sp, active, gw, st); break;
-        }
-        return SHIFTND_OK;
-    }
-    if (g.nd == 3) {
-        note_kernel("crop_backward3");
-        switch (dtype) {
-        case SHIFTND_F64: launch_span_backward<f64_t, 3>(p, sp, active, gw, st); break;
-        case SHIFTND_F32: launch_span_backward<f32_t, 3>(p, sp, active, gw, st); break;
-        case SHIFTND_F16: launch_span_backward<f16_t, 3>(p, sp, active, gw, st); break;
-        default: launch_span_backward<bf16_t, 3>(p, sp, active, gw, st); break;
-        }
-        return SHIFTND_OK;
-    }
-    if (pooled && g.nd == 1) {
-        note_kernel("row_backward_pool");
-        switch (dtype) {
-        case SHIFTND_F64: launch_span_backward<f64_t, 1, false, true>(p, sp, active, gw, st); break;
-        case SHIFTND_F32: launch_span_backward<f32_t, 1, false, true>(p, sp, active, gw, st); break;
-        case SHIFTND_F16: launch_span_backward<f16_t, 1, false, true>(p, sp, active, gw, st); break;
-        default: launch_span_backward<bf16_t, 1, false, true>(p, sp, active, gw, st); break;
-        }
-        return SHIFTND_OK;
-    }
-    if (pooled) {
-        note_kernel("crop_backward_pool");
-        switch (dtype) {
-        case SHIFTND_F64: launch_span_backward<f64_t, 2, false, true>(p, sp, active, gw, st); break;
-        case SHIFTND_F32: launch_span_backward<f32_t, 2, false, true>(p, sp, active, gw, st); break;
-        case SHIFTND_F16: launch_span_backward<f16_t, 2, false, true>(p, sp, active, gw, st); break;
-        default: launch_span_backward<bf16_t, 2, false, true>(p, sp, active, gw, st); break;
-        }
-        return SHIFTND_OK;
-    }
-    if (g.nd == 2 && (g.S[2] * es) % 16 != 0) {   // ragged x rows (4- / 8-byte elements: span_geometry_ok)
-        note_kernel("crop_backward_ragged");
-        switch (dtype) {
-        case SHIFTND_F64: launch_span_backward<f64_t, 2, true>(p, sp, active, gw, st); break;
-        case SHIFTND_F32: launch_span_backward<f32_t, 2, true>(p, sp, active, gw, st); break;
-        case SHIFTND_F16: launch_span_backward<f16_t, 2, true>(p, sp, active, gw, st); break;
-        default: launch_span_backward<bf16_t, 2, true>(p, sp, active, gw, st); break;
-        }
-        return SHIFTND_OK;
-    }
-    note_kernel(g.nd == 2 ? "crop_backward" : "row_backward");
-#define SHIFTND_SPAN_T(TT) (g.nd == 1 ? launch_span_backward<TT, 1>(p, sp, active, gw, st) : launch_span_backward<TT, 2>(p, sp, active, gw, st))
-    switch (dtype) {
-    case SHIFTND_F32: SHIFTND_SPAN_T(f32_t); break;
-    case SHIFTND_F64: SHIFTND_SPAN_T(f64_t); break;
-    case SHIFTND_F16: SHIFTND_SPAN_T(f16_t); break;
-    default: SHIFTND_SPAN_T(bf16_t); break;
-    }
-#undef SHIFTND_SPAN_T
+    const bool xrag = g.nd == 2 && !pooled && (g.S[2] * es) % 16 != 0;   // ragged x rows (span_geometry_ok: not pooled)
+    if (g.nd == 3) note_kernel(pooled ? "crop_backward3_pool" : "crop_backward3");
+    else if (pooled) note_kernel(g.nd == 1 ? "row_backward_pool" : "crop_backward_pool");
+    else if (xrag) note_kernel("crop_backward_ragged");
+    else note_kernel(g.nd == 2 ? "crop_backward" : "row_backward");
+    with_float_type(dtype, [&](auto t) {
+        using T = tag_type<decltype(t)>;
+        with_bool(pooled, [&](auto pool) {
+            constexpr bool POOL = decltype(pool)::value;
+            if (g.nd == 3) {
+                // (3-D pooled: 2- / 4-byte elements -- span_geometry_ok)
+                if constexpr (!(POOL && sizeof(typename T::S) == 8)) launch_span_backward<T, 3, false, POOL>(p, sp, active, gw, st);
+            } else if (g.nd == 1) {
+                launch_span_backward<T, 1, false, POOL>(p, sp, active, gw, st);
+            } else if (xrag) {
+                if constexpr (!POOL) launch_span_backward<T, 2, true>(p, sp, active, gw, st);
+            } else {
+                launch_span_backward<T, 2, false, POOL>(p, sp, active, gw, st);
+            }
+        });
+    });
     return SHIFTND_OK;
 }
 

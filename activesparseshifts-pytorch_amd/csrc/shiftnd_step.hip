@@ -437,23 +437,19 @@ int launch_step_backward(StepParams &p, const StepLayout &L, bool active, void *
     using S = typename T::S;
     const size_t lds = step_lds_bytes(L, ND, active);
     const dim3 grid(p.steps_per_xcd * 8), block(kThreads);
-    // (only the forms a call reaches are built: the fused pool for the sparse shift, two row groups per thread for 16-bit data)
-#define SHIFTND_STEP_PAD(ACT, PADV) \
-    case PADV: \
-        if constexpr (ND == 2) { \
-            if constexpr (!ACT) \
-                if (p.K1 > 0) { hipLaunchKernelGGL((step_backward<T, ND, ACT, PADV, true>), grid, block, lds, st, p); break; } \
-            if constexpr (sizeof(S) == 2) \
-                if (L.U == 2) { hipLaunchKernelGGL((step_backward<T, ND, ACT, PADV, false, 2>), grid, block, lds, st, p); break; } \
-        } \
-        hipLaunchKernelGGL((step_backward<T, ND, ACT, PADV>), grid, block, lds, st, p); break;
     launch_step_prep(T::kDtype, active, p, st);
-    if (active) {
-        switch (p.pad) { SHIFTND_STEP_PAD(true, 0) SHIFTND_STEP_PAD(true, 1) SHIFTND_STEP_PAD(true, 2) default: SHIFTND_STEP_PAD(true, 3) }   // (3 = reflect and symmetric: shiftnd_step.hpp kPadMirror)
-    } else {
-        switch (p.pad) { SHIFTND_STEP_PAD(false, 0) SHIFTND_STEP_PAD(false, 1) SHIFTND_STEP_PAD(false, 2) default: SHIFTND_STEP_PAD(false, 3) }
-    }
-#undef SHIFTND_STEP_PAD
+    with_bool(active, [&](auto act) {
+        constexpr bool ACT = decltype(act)::value;
+        with_pad_mirror(p.pad, [&](auto pad) {
+            constexpr int PAD = decltype(pad)::value;
+            // (only the forms a call reaches are built: the fused pool for the sparse shift, two row groups per thread for 16-bit data)
+            if constexpr (ND == 2 && !ACT)
+                if (p.K1 > 0) { hipLaunchKernelGGL((step_backward<T, ND, ACT, PAD, true>), grid, block, lds, st, p); return; }
+            if constexpr (ND == 2 && sizeof(S) == 2)
+                if (L.U == 2) { hipLaunchKernelGGL((step_backward<T, ND, ACT, PAD, false, 2>), grid, block, lds, st, p); return; }
+            hipLaunchKernelGGL((step_backward<T, ND, ACT, PAD>), grid, block, lds, st, p);
+        });
+    });
     launch_step_reduce(T::kDtype, ND, p, gw, st);
     return SHIFTND_OK;
 }
@@ -462,26 +458,15 @@ int launch_step_backward(StepParams &p, const StepLayout &L, bool active, void *
 
 void launch_step_prep(int dtype, bool active, const StepParams &p, hipStream_t st) {
     const dim3 grid(p.C), block(kThreads);
-#define SHIFTND_PREP(TT) hipLaunchKernelGGL((step_prep<TT>), grid, block, 0, st, p, active);
-    switch (dtype) {
-    case SHIFTND_F32: SHIFTND_PREP(f32_t) break;
-    case SHIFTND_F64: SHIFTND_PREP(f64_t) break;
-    case SHIFTND_F16: SHIFTND_PREP(f16_t) break;
-    default: SHIFTND_PREP(bf16_t) break;
-    }
-#undef SHIFTND_PREP
+    with_float_type(dtype, [&](auto t) { hipLaunchKernelGGL((step_prep<tag_type<decltype(t)>>), grid, block, 0, st, p, active); });
 }
 
 void launch_step_reduce(int dtype, int nd, const StepParams &p, void *grad_w, hipStream_t st) {
     const dim3 grid(p.C), block(kThreads);
-#define SHIFTND_REDUCE(TT) hipLaunchKernelGGL((step_reduce<TT>), grid, block, 0, st, p, static_cast<typename TT::S *>(grad_w), nd);
-    switch (dtype) {
-    case SHIFTND_F32: SHIFTND_REDUCE(f32_t) break;
-    case SHIFTND_F64: SHIFTND_REDUCE(f64_t) break;
-    case SHIFTND_F16: SHIFTND_REDUCE(f16_t) break;
-    default: SHIFTND_REDUCE(bf16_t) break;
-    }
-#undef SHIFTND_REDUCE
+    with_float_type(dtype, [&](auto t) {
+        using T = tag_type<decltype(t)>;
+        hipLaunchKernelGGL((step_reduce<T>), grid, block, 0, st, p, static_cast<typename T::S *>(grad_w), nd);
+    });
 }
 
 void step_set_tuning(int knob, int value) {
@@ -511,8 +496,7 @@ static bool step_backward_core(const Geometry &g, int dtype, const void *go, con
     if (g_step_tune[0] == 1) return false;
     if (dtype > SHIFTND_BF16 || (g.nd != 2 && g.nd != 3)) return false;
     const int es = dtype_size(dtype);
-    for (int d = 0; d < 3; ++d)
-        if ((g.O[d] != g.S[d] || g.L[d] != 0) && !((es == 4 || g.K[0] > 0) && walk_crop_window_ok(g, g.K[0] > 0))) return false;   // (a window: walk_backward<.., CROP>, 3-D)
+    if (cropped(g) && !((es == 4 || g.K[0] > 0) && walk_crop_window_ok(g, g.K[0] > 0))) return false;   // (a window: walk_backward<.., CROP>, 3-D)
     if ((g.nd == 2 && g.S[0] != 1) || g.S[0] < 1 || g.S[1] < 1 || g.S[2] < 1) return false;
     if ((g.S[2] * es) % 16 != 0 || g.S[2] * es / 16 > kThreads || g.S[2] > 32000) return false;
     if (g.S[0] * g.S[1] * g.S[2] >= (1LL << 30)) return false;
@@ -521,7 +505,7 @@ static bool step_backward_core(const Geometry &g, int dtype, const void *go, con
     } else if (!dense(g.xs, g.N, g.C, g.S) || !dense(g.os, g.N, g.C, g.O) || !dense(g.gs, g.N, g.C, g.S)) {
         return false;
     }
-    if ((g.K[0] <= 0 && reinterpret_cast<uintptr_t>(go) % 16) || reinterpret_cast<uintptr_t>(x) % 16 || reinterpret_cast<uintptr_t>(gx) % 16) return false;
+    if ((g.K[0] <= 0 && !aligned_to(go, 16)) || !aligned_to(x, 16) || !aligned_to(gx, 16)) return false;
     const StepLayout L = step_layout(g, es);
     if (L.total_steps + 8 >= (1ull << 31)) return false;
     if (step_lds_bytes(L, g.nd, g.active != 0) > 64 * 1024) return false;
@@ -539,8 +523,7 @@ static bool step_shape_ok(const Geometry &g, int dtype) {
     // (a window: the cropped walk of 3-D fp32 volumes -- geometry only: the knob's state must not shrink a workspace)
     bool window_ok = g.nd == 3 && (es == 4 || g.K[0] > 0) && g.pad == 0 && g.L[2] <= 2;
     for (int d = 0; d < 3; ++d) window_ok = window_ok && g.O[d] >= 2 && g.L[d] >= 0 && g.L[d] + g.O[d] <= g.S[d];
-    for (int d = 0; d < 3; ++d)
-        if ((g.O[d] != g.S[d] || g.L[d] != 0) && !window_ok) return false;
+    if (cropped(g) && !window_ok) return false;
     if ((g.nd == 2 && g.S[0] != 1) || g.S[0] < 1 || g.S[1] < 1 || g.S[2] < 1) return false;
     if ((g.S[2] * es) % 16 != 0 || g.S[2] * es / 16 > kThreads || g.S[2] > 32000) return false;
     return g.S[0] * g.S[1] * g.S[2] < (1LL << 30);
@@ -603,14 +586,8 @@ int step_backward(const Geometry &g, int dtype, const void *go, const void *x, c
         return walk3_backward_launch(p, g, dtype, L.cpr, gw, st);
     note_kernel(g.K[0] > 0 ? "step_backward_pool" : "step_backward");
     const bool active = g.active != 0;
-#define SHIFTND_STEP_T(TT) launch_step_backward<TT, 2>(p, L, active, gw, st)
-    switch (dtype) {
-    case SHIFTND_F32: return SHIFTND_STEP_T(f32_t);
-    case SHIFTND_F64: return SHIFTND_STEP_T(f64_t);
-    case SHIFTND_F16: return SHIFTND_STEP_T(f16_t);
-    default: return SHIFTND_STEP_T(bf16_t);
-    }
-#undef SHIFTND_STEP_T
+    with_float_type(dtype, [&](auto t) { launch_step_backward<tag_type<decltype(t)>, 2>(p, L, active, gw, st); });
+    return SHIFTND_OK;
 }
 
 }  // namespace shiftnd

@@ -8,6 +8,7 @@
 #include <type_traits>
 
 #include "shiftnd_common.hpp"
+#include "shiftnd_dispatch.hpp"
 #include "shiftnd_launch.hpp"
 #include "shiftnd_stage.hpp"
 
@@ -61,12 +62,9 @@ struct StepParams {
 // keeps the one-step crop_backward3.
 inline bool walk_crop_window_ok(const Geometry &g, bool pooled = false) {
     if (g.nd != 3 || g.pad != 0 || (g.K[0] > 0) != pooled || (g_step_tune[3] & 2048)) return false;
-    bool cropped = false;
-    for (int d = 0; d < 3; ++d) {
+    for (int d = 0; d < 3; ++d)
         if (g.O[d] < 2 || g.L[d] < 0 || g.L[d] + g.O[d] > g.S[d]) return false;
-        cropped = cropped || g.O[d] != g.S[d] || g.L[d] != 0;
-    }
-    return cropped && g.L[2] <= 2;
+    return cropped(g) && g.L[2] <= 2;
 }
 
 // the second half of step_backward()'s launch for 3-D problems (shiftnd_walk3.hip)
@@ -204,8 +202,7 @@ __device__ __forceinline__ double wave_total(double v) {
 // `rt` is the kernel's padding argument (p.pad); it only matters for PAD = 3.  (A run-time mode for all four non-zeros paddings was
 // measured on the row-span kernels: + 13 .. 30 % on their forwards, + 5 .. 20 % on the backwards -- ten VALU instructions per fold
 // against two to five; the flat-stream kernels, whose per-element path hides it, merge the three wrapping modes: shiftnd_flat.hip.)
-constexpr int kPadMirror = 3;
-constexpr int pad_template(int pad) { return pad >= kPadMirror ? kPadMirror : pad; }
+// (kPadMirror = 3 and pad_template(): shiftnd_dispatch.hpp)
 
 __device__ __forceinline__ int fold_mirror(int idx, int len, int k) {
     const int t = max(idx, -k - idx);
@@ -491,11 +488,10 @@ StepLayout step_layout(const Geometry &g, int es, int force_u = 0) {
     L.rec = (E + 3 <= 8) ? 8 : 16;
     L.ndiff = g.nd == 3 ? 8 : 2;
     L.total_steps = static_cast<uint64_t>(g.N) * g.C * L.spv;
-    auto up = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
-    L.off_desc = up(L.total_steps * L.ndiff * sizeof(double));
-    L.off_colx = L.off_desc + up(static_cast<size_t>(g.C) * sizeof(ChanDesc));
-    L.off_colg = L.off_colx + up(static_cast<size_t>(g.C) * L.cpr * L.rec * sizeof(int16_t));
-    L.bytes = L.off_colg + up(static_cast<size_t>(g.C) * L.cpr * L.rec * sizeof(int16_t));
+    L.off_desc = align_up_256(L.total_steps * L.ndiff * sizeof(double));
+    L.off_colx = L.off_desc + align_up_256(static_cast<size_t>(g.C) * sizeof(ChanDesc));
+    L.off_colg = L.off_colx + align_up_256(static_cast<size_t>(g.C) * L.cpr * L.rec * sizeof(int16_t));
+    L.bytes = L.off_colg + align_up_256(static_cast<size_t>(g.C) * L.cpr * L.rec * sizeof(int16_t));
     return L;
 }
 

@@ -487,10 +487,10 @@ bool step_forward_eligible(const Geometry &g, int dtype, const void *x, const vo
     // 2-D; 3-D for the sparse shift of 4- / 8-byte elements (the caller checks that its weights are floats)
     if (g.nd == 3 ? es < 4 : (g.nd != 2 || g.S[0] != 1 || g.O[0] != 1)) return false;
     // 1- / 2-byte elements: aligned pieces of the source rows
-    if (es < 4 && ((g.S[2] * es) % 16 != 0 || reinterpret_cast<uintptr_t>(x) % 16 != 0)) return false;
+    if (es < 4 && ((g.S[2] * es) % 16 != 0 || !aligned_to(x, 16))) return false;
     const int64_t xe = g.S[0] * g.S[1] * g.S[2], oe = g.O[0] * g.O[1] * g.O[2];
     if (xe < 1 || oe < 1 || xe >= (1LL << 30) || oe >= (1LL << 30)) return false;
-    if ((g.O[2] * es) % 16 != 0 || g.O[2] * es / 16 > kThreads || reinterpret_cast<uintptr_t>(out) % 16 != 0) return false;
+    if ((g.O[2] * es) % 16 != 0 || g.O[2] * es / 16 > kThreads || !aligned_to(out, 16)) return false;
     if (!dense(g.xs, g.N, g.C, g.S) || !dense(g.os, g.N, g.C, g.O)) return false;
     const int cpr = static_cast<int>(g.O[2] * es / 16);
     const int64_t R = kThreads / cpr;
@@ -550,30 +550,21 @@ int step_forward(const Geometry &g, int dtype, const void *x, const void *w, int
     const dim3 grid(p.steps_per_xcd * 8), block(kThreads);
     if (g.nd == 3) {   // sparse shift of 4- / 8-byte elements, float weights (the eligibility check and the caller see to that)
         note_kernel("step_gather_forward");
-#define SHIFTND_STEP_FWD3(ES) \
-    switch (g.pad) { \
-    case 0: hipLaunchKernelGGL((step_gather_forward<ES, 0, 3>), grid, block, 0, st, p); break; \
-    case 1: hipLaunchKernelGGL((step_gather_forward<ES, 1, 3>), grid, block, 0, st, p); break; \
-    case 2: hipLaunchKernelGGL((step_gather_forward<ES, 2, 3>), grid, block, 0, st, p); break; \
-    default: hipLaunchKernelGGL((step_gather_forward<ES, kPadMirror, 3>), grid, block, 0, st, p); break; \
-    }
-        if (es == 4) { SHIFTND_STEP_FWD3(4) } else { SHIFTND_STEP_FWD3(8) }
-#undef SHIFTND_STEP_FWD3
+        with_bool(es == 4, [&](auto four) {
+            with_pad_mirror(g.pad, [&](auto pad) {
+                hipLaunchKernelGGL((step_gather_forward<decltype(four)::value ? 4 : 8, decltype(pad)::value, 3>), grid, block, 0, st, p);
+            });
+        });
         return SHIFTND_OK;
     }
     note_kernel(es < 4 ? "step_gather_forward_small" : "step_gather_forward");
-#define SHIFTND_STEP_FWD(KERNEL, ES) \
-    switch (g.pad) { \
-    case 0: hipLaunchKernelGGL((KERNEL<ES, 0>), grid, block, 0, st, p); break; \
-    case 1: hipLaunchKernelGGL((KERNEL<ES, 1>), grid, block, 0, st, p); break; \
-    case 2: hipLaunchKernelGGL((KERNEL<ES, 2>), grid, block, 0, st, p); break; \
-    default: hipLaunchKernelGGL((KERNEL<ES, kPadMirror>), grid, block, 0, st, p); break;   /* reflect and symmetric */ \
-    }
-    if (es == 1) { SHIFTND_STEP_FWD(step_gather_forward_small, 1) }
-    else if (es == 2) { SHIFTND_STEP_FWD(step_gather_forward_small, 2) }
-    else if (es == 4) { SHIFTND_STEP_FWD(step_gather_forward, 4) }
-    else { SHIFTND_STEP_FWD(step_gather_forward, 8) }
-#undef SHIFTND_STEP_FWD
+    with_pad_mirror(g.pad, [&](auto pad) {
+        constexpr int PAD = decltype(pad)::value;
+        if (es == 1) hipLaunchKernelGGL((step_gather_forward_small<1, PAD>), grid, block, 0, st, p);
+        else if (es == 2) hipLaunchKernelGGL((step_gather_forward_small<2, PAD>), grid, block, 0, st, p);
+        else if (es == 4) hipLaunchKernelGGL((step_gather_forward<4, PAD>), grid, block, 0, st, p);
+        else hipLaunchKernelGGL((step_gather_forward<8, PAD>), grid, block, 0, st, p);
+    });
     return SHIFTND_OK;
 }
 
@@ -593,8 +584,8 @@ bool step_forward_lds_eligible(const Geometry &g, int dtype, const void *x, cons
     if (g.nd == 3 && interpolating && es == 2) return false;
     const int64_t xe = g.S[0] * g.S[1] * g.S[2], oe = g.O[0] * g.O[1] * g.O[2];
     if (xe < 1 || oe < 1 || xe >= (1LL << 30) || oe >= (1LL << 30) || g.S[2] > 32000) return false;
-    if ((g.S[2] * es) % 16 != 0 || reinterpret_cast<uintptr_t>(x) % 16 != 0) return false;
-    if ((g.O[2] * es) % 16 != 0 || g.O[2] * es / 16 > kThreads || reinterpret_cast<uintptr_t>(out) % 16 != 0) return false;
+    if ((g.S[2] * es) % 16 != 0 || !aligned_to(x, 16)) return false;
+    if ((g.O[2] * es) % 16 != 0 || g.O[2] * es / 16 > kThreads || !aligned_to(out, 16)) return false;
     if (!dense(g.xs, g.N, g.C, g.S) || !dense(g.os, g.N, g.C, g.O)) return false;
     const int cpr = static_cast<int>(g.O[2] * es / 16), xppr = static_cast<int>(g.S[2] * es / 16);
     int64_t R = kThreads / cpr;
@@ -618,14 +609,14 @@ template <typename T, bool ACT>
 static void launch_step_forward_lds(const FwdParams &p, int pad, size_t lds, hipStream_t st) {
     const dim3 grid(p.steps_per_xcd * 8), block(kThreads);
     constexpr bool k3d = !ACT || sizeof(typename T::S) >= 4;
-#define SHIFTND_STEP_FWD_LDS(PADV) \
-    case PADV: \
-        if (p.nd == 3) { \
-            if constexpr (k3d) hipLaunchKernelGGL((step_forward_lds<T, 3, ACT, PADV, 2>), grid, block, lds, st, p); \
-        } else hipLaunchKernelGGL((step_forward_lds<T, 2, ACT, PADV, 2>), grid, block, lds, st, p); \
-        break;
-    switch (pad) { SHIFTND_STEP_FWD_LDS(0) SHIFTND_STEP_FWD_LDS(1) SHIFTND_STEP_FWD_LDS(2) default: SHIFTND_STEP_FWD_LDS(3) }
-#undef SHIFTND_STEP_FWD_LDS
+    with_pad_mirror(pad, [&](auto padc) {
+        constexpr int PAD = decltype(padc)::value;
+        if (p.nd == 3) {
+            if constexpr (k3d) hipLaunchKernelGGL((step_forward_lds<T, 3, ACT, PAD, 2>), grid, block, lds, st, p);
+        } else {
+            hipLaunchKernelGGL((step_forward_lds<T, 2, ACT, PAD, 2>), grid, block, lds, st, p);
+        }
+    });
 }
 
 int step_forward_lds(const Geometry &g, int dtype, const void *x, const void *w, int wkind, uint64_t fill_bits, void *out, hipStream_t st) {
@@ -677,12 +668,7 @@ int step_forward_lds(const Geometry &g, int dtype, const void *x, const void *w,
         launch_step_forward_lds<f16_t, false>(p, g.pad, lds, st);
         return SHIFTND_OK;
     }
-    switch (dtype) {
-    case SHIFTND_F32: launch_step_forward_lds<f32_t, true>(p, g.pad, lds, st); break;
-    case SHIFTND_F64: launch_step_forward_lds<f64_t, true>(p, g.pad, lds, st); break;
-    case SHIFTND_F16: launch_step_forward_lds<f16_t, true>(p, g.pad, lds, st); break;
-    default: launch_step_forward_lds<bf16_t, true>(p, g.pad, lds, st); break;
-    }
+    with_float_type(dtype, [&](auto t) { launch_step_forward_lds<tag_type<decltype(t)>, true>(p, g.pad, lds, st); });
     return SHIFTND_OK;
 }
 
@@ -699,7 +685,7 @@ bool step_forward_pooled_eligible(const Geometry &g, int dtype, const void *x, c
     const int64_t xe = g.S[1] * g.S[2], oe = g.O[1] * g.O[2];
     if (xe < 1 || oe < 1 || xe >= (1LL << 30) || oe >= (1LL << 30)) return false;
     // (round 6: windows of any width -- the last chunk of a row may be partial; pooled rows at the element's alignment)
-    if ((g.O[2] * es + 15) / 16 > kThreads || reinterpret_cast<uintptr_t>(out) % es != 0) return false;
+    if ((g.O[2] * es + 15) / 16 > kThreads || !aligned_to(out, es)) return false;
     if (!dense(g.xs, g.N, g.C, g.S)) return false;
     const int64_t cpr = (g.O[2] * es + 15) / 16, R = kThreads / cpr, p1 = (g.O[1] + 1) / 2;
     return g.N * g.C * ((p1 + R - 1) / R) + 8 < (1LL << 31);
@@ -724,7 +710,7 @@ int step_forward_pooled(const Geometry &g, int dtype, const void *x, const void 
     p.o_plane = g.P[1] * g.P[2];   // (the pooled plane)
     p.cpr = static_cast<int>((g.O[2] * es + 15) / 16);
     // (16-bit: the aligned-pieces form needs source rows of whole pieces at a 16-byte boundary; 0: element-aligned loads)
-    p.xppr = ((g.S[2] * es) % 16 == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0) ? static_cast<int>(g.S[2] * es / 16) : 0;
+    p.xppr = ((g.S[2] * es) % 16 == 0 && aligned_to(x, 16)) ? static_cast<int>(g.S[2] * es / 16) : 0;
     const int P1 = static_cast<int>(g.P[1]);
     p.R = kThreads / p.cpr;
     if (p.R > P1) p.R = P1;
@@ -739,21 +725,17 @@ int step_forward_pooled(const Geometry &g, int dtype, const void *x, const void 
     p.d_per2 = make_fastdiv(static_cast<uint32_t>(map_period(p.S2, g.pad)));
     const dim3 grid(p.steps_per_xcd * 8), block(kThreads);
     note_kernel("step_gather_forward_pool");
-#define SHIFTND_STEP_FWD_POOL_A(TT, ACT) \
-    switch (g.pad) { \
-    case 0: hipLaunchKernelGGL((step_gather_forward_pool<TT, 0, ACT>), grid, block, 0, st, p); break; \
-    case 1: hipLaunchKernelGGL((step_gather_forward_pool<TT, 1, ACT>), grid, block, 0, st, p); break; \
-    case 2: hipLaunchKernelGGL((step_gather_forward_pool<TT, 2, ACT>), grid, block, 0, st, p); break; \
-    default: hipLaunchKernelGGL((step_gather_forward_pool<TT, kPadMirror, ACT>), grid, block, 0, st, p); break; \
-    }
-#define SHIFTND_STEP_FWD_POOL(TT) \
-    if (g.active) { SHIFTND_STEP_FWD_POOL_A(TT, true) } else { SHIFTND_STEP_FWD_POOL_A(TT, false) }
-    if (dtype == SHIFTND_F32) { SHIFTND_STEP_FWD_POOL(f32_t) }
-    else if (dtype == SHIFTND_F64) { SHIFTND_STEP_FWD_POOL(f64_t) }
-    else if (dtype == SHIFTND_F16) { SHIFTND_STEP_FWD_POOL_A(f16_t, false) }   // (16-bit: the sparse shift only, step_forward_pooled_eligible)
-    else { SHIFTND_STEP_FWD_POOL_A(bf16_t, false) }
-#undef SHIFTND_STEP_FWD_POOL_A
-#undef SHIFTND_STEP_FWD_POOL
+    with_float_type(dtype, [&](auto t) {
+        using T = tag_type<decltype(t)>;
+        with_bool(g.active != 0, [&](auto act) {
+            constexpr bool ACT = decltype(act)::value;
+            if constexpr (!ACT || sizeof(typename T::S) >= 4) {   // (16-bit: the sparse shift only, step_forward_pooled_eligible)
+                with_pad_mirror(g.pad, [&](auto pad) {
+                    hipLaunchKernelGGL((step_gather_forward_pool<T, decltype(pad)::value, ACT>), grid, block, 0, st, p);
+                });
+            }
+        });
+    });
     return SHIFTND_OK;
 }
 

@@ -720,9 +720,8 @@ WalkPlan walk_plan(const Geometry &g, int64_t rows = 0) {
     w.spp = static_cast<int>((rows + rmax - 1) / rmax);
     w.R = static_cast<int>((rows + w.spp - 1) / w.spp);   // balanced steps: 112 rows of 14 pieces -> 7 steps of 16 rows
     w.total = static_cast<uint64_t>(g.N) * g.C * w.spp;
-    auto up = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
-    w.off_desc = up(w.total * 8 * sizeof(double));
-    w.bytes = w.off_desc + up(static_cast<size_t>(g.C) * sizeof(ChanDesc));
+    w.off_desc = align_up_256(w.total * 8 * sizeof(double));
+    w.bytes = w.off_desc + align_up_256(static_cast<size_t>(g.C) * sizeof(ChanDesc));
     return w;
 }
 
@@ -733,13 +732,7 @@ bool walk16_volume_ok(const Geometry &g, int dtype) {
     return walk_plan(g).total + 8 < (1ull << 31);
 }
 
-bool walk16_cropped(const Geometry &g) {
-    for (int d = 0; d < 3; ++d)
-        if (g.O[d] != g.S[d] || g.L[d] != 0) return true;
-    return false;
-}
-
-bool walk16_geometry_ok(const Geometry &g, int dtype) { return walk16_volume_ok(g, dtype) && !walk16_cropped(g); }
+bool walk16_geometry_ok(const Geometry &g, int dtype) { return walk16_volume_ok(g, dtype) && !cropped(g); }
 
 // walk_backward16<.., CROP>: zeros padding, a window with rows of an even number of elements (every window row starts on a dword)
 // that begins at most two columns into the volume's rows (the own chunk's funnel), every window dim at least 2 (a size-1 dim ignores
@@ -755,15 +748,15 @@ bool walk16_crop_geometry_ok(const Geometry &g, int dtype) {
 bool walk16_forward_eligible(const Geometry &g, int dtype, const void *x, const void *out) {
     if (g_step_tune[2] == 1 || (g_step_tune[3] & 16)) return false;   // knob 34 = 1: no forwards through LDS; knob 35 bit 4: no walk kernels
     // (a window: walk_forward16<.., CROP> -- zeros padding, window rows of an even number of elements, every window dim at least 2)
-    bool crop_ok = walk16_volume_ok(g, dtype) && walk16_cropped(g) && g.pad == 0 && !(g_step_tune[3] & 2048) && g.O[2] % 2 == 0;
+    bool crop_ok = walk16_volume_ok(g, dtype) && cropped(g) && g.pad == 0 && !(g_step_tune[3] & 2048) && g.O[2] % 2 == 0;
     for (int d = 0; d < 3; ++d) crop_ok = crop_ok && g.O[d] >= 2 && g.L[d] >= 0 && g.L[d] + g.O[d] <= g.S[d];
     if (!(g.active ? (walk16_geometry_ok(g, dtype) || crop_ok) : crop_ok)) return false;   // (the sparse shift: cropped volumes only)
     if (!dense(g.xs, g.N, g.C, g.S) || !dense(g.os, g.N, g.C, g.O)) return false;
-    return reinterpret_cast<uintptr_t>(x) % 16 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0;
+    return aligned_to(x, 16) && aligned_to(out, 16);
 }
 
 int walk16_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, void *out, hipStream_t st) {
-    const bool crop = walk16_cropped(g);
+    const bool crop = cropped(g);
     const WalkPlan W = walk_plan(g, crop ? g.O[1] : 0);
     FwdParams p{};
     p.x = x;
@@ -800,16 +793,19 @@ int walk16_forward(const Geometry &g, int dtype, const void *x, const void *w, i
     const bool zeros = g.pad == 0;
     if (crop && !g.active) {   // (a raw copy of the window: one instantiation for both 16-bit types)
         hipLaunchKernelGGL((walk_forward16<f16_t, true, true, false>), grid, block, kWalkTileBytes, st, p);
-    } else if (crop) {
-        if (dtype == SHIFTND_F16) hipLaunchKernelGGL((walk_forward16<f16_t, true, true>), grid, block, kWalkTileBytes, st, p);
-        else hipLaunchKernelGGL((walk_forward16<bf16_t, true, true>), grid, block, kWalkTileBytes, st, p);
-    } else if (dtype == SHIFTND_F16) {
-        if (zeros) hipLaunchKernelGGL((walk_forward16<f16_t, true>), grid, block, kWalkTileBytes, st, p);
-        else hipLaunchKernelGGL((walk_forward16<f16_t, false>), grid, block, kWalkTileBytes, st, p);
-    } else {
-        if (zeros) hipLaunchKernelGGL((walk_forward16<bf16_t, true>), grid, block, kWalkTileBytes, st, p);
-        else hipLaunchKernelGGL((walk_forward16<bf16_t, false>), grid, block, kWalkTileBytes, st, p);
+        return SHIFTND_OK;
     }
+    with_type<f16_t, bf16_t>(dtype, [&](auto t) {
+        using T = tag_type<decltype(t)>;
+        with_bool(zeros, [&](auto z) {
+            constexpr bool ZEROS = decltype(z)::value;
+            if (crop) {   // (zeros padding: walk16_forward_eligible)
+                if constexpr (ZEROS) hipLaunchKernelGGL((walk_forward16<T, true, true>), grid, block, kWalkTileBytes, st, p);
+            } else {
+                hipLaunchKernelGGL((walk_forward16<T, ZEROS>), grid, block, kWalkTileBytes, st, p);
+            }
+        });
+    });
     return SHIFTND_OK;
 }
 
@@ -818,7 +814,7 @@ bool walk16_backward_eligible(const Geometry &g, int dtype, const void *go, cons
     if (g_step_tune[0] == 1 || (g_step_tune[3] & 16)) return false;   // knob 32 = 1: never; knob 35 bit 4: no walk kernels
     if (!walk16_geometry_ok(g, dtype) && !walk16_crop_geometry_ok(g, dtype)) return false;
     if (!dense(g.xs, g.N, g.C, g.S) || !dense(g.os, g.N, g.C, g.O) || !dense(g.gs, g.N, g.C, g.S)) return false;
-    return reinterpret_cast<uintptr_t>(go) % 16 == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0 && reinterpret_cast<uintptr_t>(gx) % 16 == 0;
+    return aligned_to(go, 16) && aligned_to(x, 16) && aligned_to(gx, 16);
 }
 
 size_t walk16_backward_workspace(const Geometry &g, int dtype) { return walk16_volume_ok(g, dtype) ? walk_plan(g).bytes : 0; }
@@ -859,7 +855,7 @@ int walk16_backward(const Geometry &g, int dtype, const void *go, const void *x,
     const size_t lds = 2 * kWalkTileBytes + (kThreads / 64) * 8 * sizeof(double);
     const dim3 grid(p.steps_per_xcd * 8), block(kThreads);
     const bool active = g.active != 0, zeros = g.pad == 0;
-    const bool crop = walk16_cropped(g);
+    const bool crop = cropped(g);
     if (crop) {   // the window: sizes in wO0 / wO1 / wO2, its first plane / row / column in wL0 / wL1 / wL2 (walk_backward16<.., CROP>)
         p.wO0 = static_cast<int>(g.O[0]);
         p.wO1 = static_cast<int>(g.O[1]);
@@ -871,23 +867,22 @@ int walk16_backward(const Geometry &g, int dtype, const void *go, const void *x,
         p.crop = 1;
     }
     note_kernel(crop ? (active ? "walk_backward16_crop" : "walk_backward16_crop_sparse") : (active ? "walk_backward16" : "walk_backward16_sparse"));
-#define SHIFTND_WALK16(TT) \
-    { \
-        launch_step_prep(TT::kDtype, active, p, st); \
-        if (crop) { \
-            if (active) hipLaunchKernelGGL((walk_backward16<TT, true, true, true>), grid, block, lds, st, p); \
-            else hipLaunchKernelGGL((walk_backward16<TT, false, true, true>), grid, block, lds, st, p); \
-        } else if (active) { \
-            if (zeros) hipLaunchKernelGGL((walk_backward16<TT, true, true>), grid, block, lds, st, p); \
-            else hipLaunchKernelGGL((walk_backward16<TT, true, false>), grid, block, lds, st, p); \
-        } else { \
-            if (zeros) hipLaunchKernelGGL((walk_backward16<TT, false, true>), grid, block, lds, st, p); \
-            else hipLaunchKernelGGL((walk_backward16<TT, false, false>), grid, block, lds, st, p); \
-        } \
-        launch_step_reduce(TT::kDtype, 3, p, gw, st); \
-    }
-    if (dtype == SHIFTND_F16) SHIFTND_WALK16(f16_t) else SHIFTND_WALK16(bf16_t)
-#undef SHIFTND_WALK16
+    with_type<f16_t, bf16_t>(dtype, [&](auto t) {
+        using T = tag_type<decltype(t)>;
+        launch_step_prep(T::kDtype, active, p, st);
+        with_bool(active, [&](auto act) {
+            constexpr bool ACT = decltype(act)::value;
+            with_bool(zeros, [&](auto z) {
+                constexpr bool ZEROS = decltype(z)::value;
+                if (crop) {   // (zeros padding: walk_crop_window_ok)
+                    if constexpr (ZEROS) hipLaunchKernelGGL((walk_backward16<T, ACT, true, true>), grid, block, lds, st, p);
+                } else {
+                    hipLaunchKernelGGL((walk_backward16<T, ACT, ZEROS>), grid, block, lds, st, p);
+                }
+            });
+        });
+        launch_step_reduce(T::kDtype, 3, p, gw, st);
+    });
     return SHIFTND_OK;
 }
 

@@ -750,12 +750,11 @@ static bool walk_forward_core(const Geometry &g, int dtype, const void *x, const
     if (g_step_tune[2] == 1 || (g_step_tune[3] & 16)) return false;   // knob 34 = 1: no forwards through LDS; knob 35 bit 4: no walk
     if (dtype > SHIFTND_BF16 || g.nd != 3 || !g.active) return false;
     const int es = dtype_size(dtype);
-    for (int d = 0; d < 3; ++d)
-        if (g.L[d] != 0 || g.O[d] != g.S[d]) return false;
+    if (cropped(g)) return false;
     const int64_t xe = g.S[0] * g.S[1] * g.S[2];
     if (xe < 1 || xe >= (1LL << 30) || g.S[2] > 32000 || g.S[0] < 2) return false;
     if ((g.S[2] * es) % 16 != 0 || g.S[2] * es / 16 > kThreads) return false;
-    if (reinterpret_cast<uintptr_t>(x) % 16 != 0 || reinterpret_cast<uintptr_t>(out) % 16 != 0) return false;
+    if (!aligned_to(x, 16) || !aligned_to(out, 16)) return false;
     if (!dense(g.xs, g.N, g.C, g.S) || (!pooled && !dense(g.os, g.N, g.C, g.O))) return false;
     const int64_t cpr = g.S[2] * es / 16;
     if (cpr > kThreads / 2 || g.S[0] * g.S[1] * g.S[2] * es >= (1LL << 31)) return false;   // (one piece per thread; one buffer resource per volume)
@@ -816,21 +815,15 @@ int walk_forward(const Geometry &g, int dtype, const void *x, const void *w, int
     const size_t lds = 64 + static_cast<size_t>(p.R + 1) * p.cpr * 16 + 64 + (pooled ? 2 * kThreads * 16 + 64 : 0) + kThreads * 16;   // tile (+ exchange slots), dump slots
     const dim3 grid(p.steps_per_xcd * 8), block(kThreads);
     note_kernel(pooled ? "walk_forward_pool" : "walk_forward");
-#define SHIFTND_WALK_FWD_PAD(T, PADV) \
-    case PADV: \
-        if (pooled) hipLaunchKernelGGL((walk_forward<T, PADV, true>), grid, block, lds, st, p); \
-        else if constexpr (sizeof(typename T::S) != 2) hipLaunchKernelGGL((walk_forward<T, PADV, false>), grid, block, lds, st, p); \
-        break;
-#define SHIFTND_WALK_FWD(T) \
-    switch (g.pad) { SHIFTND_WALK_FWD_PAD(T, 0) SHIFTND_WALK_FWD_PAD(T, 1) SHIFTND_WALK_FWD_PAD(T, 2) default: SHIFTND_WALK_FWD_PAD(T, 3) }
-    switch (dtype) {
-    case SHIFTND_F32: SHIFTND_WALK_FWD(f32_t) break;
-    case SHIFTND_F64: SHIFTND_WALK_FWD(f64_t) break;
-    case SHIFTND_F16: SHIFTND_WALK_FWD(f16_t) break;
-    default: SHIFTND_WALK_FWD(bf16_t) break;
-    }
-#undef SHIFTND_WALK_FWD
-#undef SHIFTND_WALK_FWD_PAD
+    with_float_type(dtype, [&](auto t) {
+        using T = tag_type<decltype(t)>;
+        with_pad_mirror(g.pad, [&](auto pad) {
+            constexpr int PAD = decltype(pad)::value;
+            // (16-bit tensors without a pool: walk_forward16, shiftnd_walk.hip -- only their pooled variant is instantiated here)
+            if (pooled) hipLaunchKernelGGL((walk_forward<T, PAD, true>), grid, block, lds, st, p);
+            else if constexpr (sizeof(typename T::S) != 2) hipLaunchKernelGGL((walk_forward<T, PAD, false>), grid, block, lds, st, p);
+        });
+    });
     return SHIFTND_OK;
 }
 
@@ -844,7 +837,7 @@ bool walk_backward_eligible(const Geometry &g, int dtype, const void *go, const 
 // (K0, K1, 2)
 bool walk_backward_pooled_eligible(const Geometry &g, int dtype, const void *go, const void *x, const void *gx) {
     if (!(g.K[0] > 0 && g.nd == 3) || g.K[2] != 2 || g.K[1] < 1) return false;
-    if (reinterpret_cast<uintptr_t>(go) % 8) return false;
+    if (!aligned_to(go, 8)) return false;
     if (g.P[0] * g.P[1] * g.P[2] * dtype_size(dtype) >= (1LL << 31)) return false;
     return walk_backward_core(g, dtype, nullptr, x, gx, true);
 }
@@ -852,15 +845,13 @@ static bool walk_backward_core(const Geometry &g, int dtype, const void *go, con
     if (g_step_tune[0] == 1 || (g_step_tune[3] & 16)) return false;   // knob 32 = 1: never; knob 35 bit 4: no walk kernels
     if (dtype > SHIFTND_BF16 || g.nd != 3 || g.S[0] < 2) return false;
     const int es = dtype_size(dtype);
-    bool cropped = false;
-    for (int d = 0; d < 3; ++d) cropped = cropped || g.O[d] != g.S[d] || g.L[d] != 0;
     // (a window: walk_backward<.., CROP> -- zeros padding; 4-byte elements, or -- with the pool riding on the walk -- 2-byte ones too:
     //  the pooled gradient of a window with rows of an even number of elements)
-    if (cropped && (es == 8 || (!pooled && es != 4) || !walk_crop_window_ok(g, pooled) || (pooled && g.O[2] % 2 != 0))) return false;
+    if (cropped(g) && (es == 8 || (!pooled && es != 4) || !walk_crop_window_ok(g, pooled) || (pooled && g.O[2] % 2 != 0))) return false;
     if (g.S[1] < 1 || (g.S[2] * es) % 16 != 0 || g.S[2] * es / 16 > kThreads || g.S[2] > 32000) return false;
     if (g.S[0] * g.S[1] * g.S[2] >= (1LL << 30)) return false;
     if (!dense(g.xs, g.N, g.C, g.S) || (!pooled && !dense(g.os, g.N, g.C, g.O)) || !dense(g.gs, g.N, g.C, g.S)) return false;
-    if ((!pooled && reinterpret_cast<uintptr_t>(go) % 16) || reinterpret_cast<uintptr_t>(x) % 16 || reinterpret_cast<uintptr_t>(gx) % 16) return false;
+    if ((!pooled && !aligned_to(go, 16)) || !aligned_to(x, 16) || !aligned_to(gx, 16)) return false;
     const StepLayout L = step_layout(g, es);
     if (L.total_steps + 8 >= (1ull << 31)) return false;
     if (L.cpr > kThreads / 2) return false;   // (R + 1 rows of pieces per plane and tensor, one piece per thread)
@@ -877,84 +868,69 @@ template <typename T> static void launch_walk_backward(StepParams &p, size_t lds
     using S = typename T::S;
     const dim3 grid(p.steps_per_xcd * 8), block(kThreads);
     launch_step_prep(T::kDtype, active, p, st);
-    // (16-bit tensors without a pool: walk_backward16, shiftnd_walk.hip -- only their pooled variants are instantiated here)
-    constexpr bool PLAIN = sizeof(S) != 2;
-#define SHIFTND_WALK_BWD(PADV) \
-    case PADV: \
-        if (p.crop && p.K0 > 0) { \
-            if constexpr (PADV == 0 && sizeof(S) != 8) { \
-                if (!active) hipLaunchKernelGGL((walk_backward<T, 0, true, false, true>), grid, block, lds, st, p); \
-                else hipLaunchKernelGGL((walk_backward<T, 0, true, true, true>), grid, block, lds, st, p); \
-            } \
-        } else if (p.crop) { \
-            if constexpr (PADV == 0 && sizeof(S) == 4) { \
-                if (!active) hipLaunchKernelGGL((walk_backward<T, 0, false, false, true>), grid, block, lds, st, p); \
-                else hipLaunchKernelGGL((walk_backward<T, 0, false, true, true>), grid, block, lds, st, p); \
-            } \
-        } else if (!active && p.K0 > 0) hipLaunchKernelGGL((walk_backward<T, PADV, true, false>), grid, block, lds, st, p); \
-        else if (p.K0 > 0) hipLaunchKernelGGL((walk_backward<T, PADV, true>), grid, block, lds, st, p); \
-        else if constexpr (PLAIN) { \
-            if (!active) hipLaunchKernelGGL((walk_backward<T, PADV, false, false>), grid, block, lds, st, p); \
-            else hipLaunchKernelGGL((walk_backward<T, PADV, false>), grid, block, lds, st, p); \
-        } \
-        break;
-    switch (p.pad) { SHIFTND_WALK_BWD(0) SHIFTND_WALK_BWD(1) SHIFTND_WALK_BWD(2) default: SHIFTND_WALK_BWD(3) }
-#undef SHIFTND_WALK_BWD
+    with_pad_mirror(p.pad, [&](auto padc) {
+        constexpr int PAD = decltype(padc)::value;
+        with_bool(active, [&](auto act) {
+            constexpr bool ACT = decltype(act)::value;
+            with_bool(p.K0 > 0, [&](auto pool) {
+                constexpr bool POOL = decltype(pool)::value;
+                if (p.crop) {
+                    // (a window: zeros padding; 4-byte elements, or -- with the pool riding on the walk -- 2-byte ones too: walk_backward_core)
+                    if constexpr (PAD == 0 && (POOL ? sizeof(S) != 8 : sizeof(S) == 4))
+                        hipLaunchKernelGGL((walk_backward<T, 0, POOL, ACT, true>), grid, block, lds, st, p);
+                } else if constexpr (POOL || sizeof(S) != 2) {
+                    // (16-bit tensors without a pool: walk_backward16, shiftnd_walk.hip -- only their pooled variants are instantiated here)
+                    hipLaunchKernelGGL((walk_backward<T, PAD, POOL, ACT>), grid, block, lds, st, p);
+                }
+            });
+        });
+    });
     launch_step_reduce(T::kDtype, 3, p, gw, st);
 }
 
 // the second half of step_backward()'s launch for 3-D problems: balanced row steps, one record of sums per workgroup
 int walk3_backward_launch(StepParams &p, const Geometry &g, int dtype, int cpr, void *gw, hipStream_t st) {
     const int es = dtype_size(dtype);
-    struct { int cpr; } L{cpr};
-
-        // the walk through the planes: balanced row steps, one record of sums per workgroup
-        if (g.K[0] > 0) {
-            p.K0 = static_cast<int>(g.K[0]);
-            p.P0 = static_cast<int>(g.P[0]);
-            p.d_k0 = make_fastdiv(static_cast<uint32_t>(p.K0));
-            p.g_plane = g.P[0] * g.P[1] * g.P[2];
-        }
-        bool crop = false;
-        for (int d = 0; d < 3; ++d) crop = crop || g.O[d] != g.S[d] || g.L[d] != 0;
-        if (crop) {   // walk_backward<.., CROP>: the window's sizes in wO0 / wO1 / wO2, its first plane / row / column in wL0 / wL1 / wL2
-            p.crop = 1;
-            p.wO0 = static_cast<int>(g.O[0]);
-            p.wO1 = static_cast<int>(g.O[1]);
-            p.wO2 = static_cast<int>(g.O[2]);
-            p.wL0 = static_cast<int>(g.L[0]);
-            p.wL1 = static_cast<int>(g.L[1]);
-            p.wL2 = static_cast<int>(g.L[2]);
-            if (g.K[0] <= 0) p.g_plane = g.O[0] * g.O[1] * g.O[2];   // (pooled: the pooled window's elements, set above)
-        }
-        const int rmax = std::min<int>(kThreads / L.cpr - 1, p.S1);   // (R + 1) * cpr <= 256: every staged piece has its thread
-        p.spp = (p.S1 + rmax - 1) / rmax;
-        p.R = (p.S1 + p.spp - 1) / p.spp;
-        // planes per workgroup (knob 38): all of them, or a part of the depth -- more, shorter workgroups, one more staged plane each
-        p.walk_planes = (g_step_tune[4] > 0 && g_step_tune[4] < p.S0) ? g_step_tune[4] : p.S0;
-        const int dparts = (p.S0 + p.walk_planes - 1) / p.walk_planes;
-        p.spv = dparts * p.spp;
-        uint64_t total = static_cast<uint64_t>(g.N) * g.C * p.spv;
-        if (total > step_layout(g, es, 1).total_steps) {
-            // more records than the workspace was planned for (knob 38 with few rows per step: a walk step holds one row fewer
-            // than a one-step workgroup): walk the whole depth -- one part, at most twice the one-step plan's row steps <= S0 of them
-            p.walk_planes = p.S0;
-            p.spv = p.spp;
-            total = static_cast<uint64_t>(g.N) * g.C * p.spv;
-        }
-        p.total_steps = static_cast<uint32_t>(total);
-        p.steps_per_xcd = static_cast<uint32_t>((total + 7) / 8);
-        p.d_spp = make_fastdiv(static_cast<uint32_t>(p.spp));
-        p.d_spv = make_fastdiv(static_cast<uint32_t>(p.spv));
-        const size_t lds = 64 + static_cast<size_t>(2 * (p.R + 1)) * L.cpr * 16 + kThreads * 16 + kThreads * 8 * sizeof(double) + 64;   // tile, dump slots, sums, pad
-        note_kernel(g.K[0] > 0 ? (crop ? "walk_backward_crop_pool" : "walk_backward_pool") : (crop ? (g.active ? "walk_backward_crop" : "walk_backward_crop_sparse") : (g.active ? "walk_backward" : "walk_backward_sparse")));
-        switch (dtype) {
-        case SHIFTND_F32: launch_walk_backward<f32_t>(p, lds, g.active != 0, gw, st); break;
-        case SHIFTND_F64: launch_walk_backward<f64_t>(p, lds, g.active != 0, gw, st); break;
-        case SHIFTND_F16: launch_walk_backward<f16_t>(p, lds, g.active != 0, gw, st); break;
-        default: launch_walk_backward<bf16_t>(p, lds, g.active != 0, gw, st); break;
-        }
-        return SHIFTND_OK;
+    if (g.K[0] > 0) {
+        p.K0 = static_cast<int>(g.K[0]);
+        p.P0 = static_cast<int>(g.P[0]);
+        p.d_k0 = make_fastdiv(static_cast<uint32_t>(p.K0));
+        p.g_plane = g.P[0] * g.P[1] * g.P[2];
     }
+    const bool crop = cropped(g);
+    if (crop) {   // walk_backward<.., CROP>: the window's sizes in wO0 / wO1 / wO2, its first plane / row / column in wL0 / wL1 / wL2
+        p.crop = 1;
+        p.wO0 = static_cast<int>(g.O[0]);
+        p.wO1 = static_cast<int>(g.O[1]);
+        p.wO2 = static_cast<int>(g.O[2]);
+        p.wL0 = static_cast<int>(g.L[0]);
+        p.wL1 = static_cast<int>(g.L[1]);
+        p.wL2 = static_cast<int>(g.L[2]);
+        if (g.K[0] <= 0) p.g_plane = g.O[0] * g.O[1] * g.O[2];   // (pooled: the pooled window's elements, set above)
+    }
+    const int rmax = std::min<int>(kThreads / cpr - 1, p.S1);   // (R + 1) * cpr <= 256: every staged piece has its thread
+    p.spp = (p.S1 + rmax - 1) / rmax;
+    p.R = (p.S1 + p.spp - 1) / p.spp;
+    // planes per workgroup (knob 38): all of them, or a part of the depth -- more, shorter workgroups, one more staged plane each
+    p.walk_planes = (g_step_tune[4] > 0 && g_step_tune[4] < p.S0) ? g_step_tune[4] : p.S0;
+    const int dparts = (p.S0 + p.walk_planes - 1) / p.walk_planes;
+    p.spv = dparts * p.spp;
+    uint64_t total = static_cast<uint64_t>(g.N) * g.C * p.spv;
+    if (total > step_layout(g, es, 1).total_steps) {
+        // more records than the workspace was planned for (knob 38 with few rows per step: a walk step holds one row fewer
+        // than a one-step workgroup): walk the whole depth -- one part, at most twice the one-step plan's row steps <= S0 of them
+        p.walk_planes = p.S0;
+        p.spv = p.spp;
+        total = static_cast<uint64_t>(g.N) * g.C * p.spv;
+    }
+    p.total_steps = static_cast<uint32_t>(total);
+    p.steps_per_xcd = static_cast<uint32_t>((total + 7) / 8);
+    p.d_spp = make_fastdiv(static_cast<uint32_t>(p.spp));
+    p.d_spv = make_fastdiv(static_cast<uint32_t>(p.spv));
+    const size_t lds = 64 + static_cast<size_t>(2 * (p.R + 1)) * cpr * 16 + kThreads * 16 + kThreads * 8 * sizeof(double) + 64;   // tile, dump slots, sums, pad
+    note_kernel(g.K[0] > 0 ? (crop ? "walk_backward_crop_pool" : "walk_backward_pool") : (crop ? (g.active ? "walk_backward_crop" : "walk_backward_crop_sparse") : (g.active ? "walk_backward" : "walk_backward_sparse")));
+    with_float_type(dtype, [&](auto t) { launch_walk_backward<tag_type<decltype(t)>>(p, lds, g.active != 0, gw, st); });
+    return SHIFTND_OK;
+}
 
 }  // namespace shiftnd
