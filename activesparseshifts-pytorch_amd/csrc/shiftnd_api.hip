@@ -669,12 +669,25 @@ static int backward_pooled_planned(const shiftnd_problem *p, const int32_t *pool
     const int rc = pooled_geometry(p, pool, g);
     if (rc != SHIFTND_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool input_only = !x && !grad_w;
+    if (input_only && p->active) return SHIFTND_ERR_INVALID_ARGUMENT;   // (also for an empty problem: the form does not exist)
     if (g.N == 0 || g.C == 0 || g.S[0] * g.S[1] * g.S[2] == 0) {
         g_last_path = SHIFTND_PATH_EMPTY;
         if (g.C > 0 && grad_w)
             if (hipMemsetAsync(grad_w, 0, static_cast<size_t>(g.C) * g.nd * dtype_size(p->dtype), st) != hipSuccess)
                 return SHIFTND_ERR_LAUNCH_FAILED;
         return SHIFTND_OK;
+    }
+    if (input_only) {
+        // the input gradient only (fixed shifts with a stride): a gather of grad_pooled with one division, no workspace.  The
+        // kernels of shiftnd_backward's NULL form with the pool in the geometry (shiftnd_gradx.hip); never SHIFTND_ERR_NOT_FUSED
+        if (!grad_pooled || !weights || !grad_x) return SHIFTND_ERR_INVALID_ARGUMENT;
+        if (g_policy == 0 && gradx_embed_eligible(g, p->dtype, grad_pooled, grad_x)) {
+            g_last_path = SHIFTND_PATH_PLANE;
+            return finish(gradx_embed(g, p->dtype, grad_pooled, weights, grad_x, st));
+        }
+        g_last_path = SHIFTND_PATH_STRIDED;
+        return finish(gradx_gather(g, p->dtype, grad_pooled, weights, grad_x, st));
     }
     if (!grad_pooled || !x || !weights || !grad_x || !grad_w || !workspace) return SHIFTND_ERR_INVALID_ARGUMENT;
     // 3-D interpolating: the walk through the planes with the pooled gradient expanded on the way into LDS

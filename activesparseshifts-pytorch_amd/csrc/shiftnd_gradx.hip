@@ -23,6 +23,15 @@
 // ends at or before the tensor's last byte.  The handful of pieces at the two ends of grad_out that fail a test take the element
 // path, which loads exactly elements of the row it stores.  Offsets are 64-bit byte offsets from the tensor base: no descriptor, no
 // soffset, nothing a range check would have to see.
+//
+// With a run-time pool (shiftnd_backward_pooled's x == NULL && grad_w == NULL form; routed as gradx_embed_pool / gradx_gather_pool)
+// the same two kernels gather from grad_pooled and divide by the window's count:
+//   grad_x[n,c,i,j,k] = inside the window ? gp[n,c, t_i / K_i, t_j / K_j, t_k / K_k] / cnt : 0,   t_d = pad(o_d + s_d),
+//   cnt = prod_d min(K_d, O_d - (t_d / K_d) * K_d)   (ceil_mode: the last window of a dim may be partial)
+// in the compute type (div_count), rounded once to the tensor type.  `pooled` is a kernel argument: without a pool every wave takes
+// the code above.  Pooled sources of neighbouring columns repeat and fold at row ends, so every pooled piece is E element loads at
+// indices computed inside the pooled row (a fill reads the row's first element and is dropped by a select); a cut window and the
+// whole-input window are the same code.
 #include <algorithm>
 
 #include "shiftnd_common.hpp"
@@ -48,7 +57,11 @@ struct EmbedParams {
     const void *w;
     int wkind, nd, pad;
     int S0, S1, S2;   // grad_x volume (normalised dims)
-    int O0, O1, O2;   // grad_out volume = the window
+    int O0, O1, O2;   // the window (grad_out's volume without a pool)
+    int G0, G1, G2;   // the volume of the tensor that is read: the window, or its pooled sizes
+    int pooled;       // 0: go is grad_out; 1: go is grad_pooled, window K = stride per dim
+    int K0, K1, K2;
+    FastDiv d_K0, d_K1, d_K2;
     int L0, L1, L2;   // first plane / row / column of the window
     int wc0, wc1, wc2;   // weight column of each normalised dim, or -1
     int C;
@@ -61,6 +74,23 @@ struct EmbedParams {
 
 // the window coordinate o in [0, len) -> source coordinate in [0, len) or -1 (zero fill); cs = canon_shift(-s)
 __device__ __forceinline__ int gradx_map(int o, int len, int cs, int pad) { return len == 1 ? 0 : fold_index(o - cs, len, pad); }
+
+// bits of one element / cnt: divided in the compute type (fp32 for the 16-bit types), rounded once.  (A count above INT_MAX
+// can only come from gradx_gather: gradx_embed's eligibility keeps counts below 2^31.)
+template <typename T> __device__ __forceinline__ typename raw_t<sizeof(typename T::S)>::type pool_div_as(
+    typename raw_t<sizeof(typename T::S)>::type bits, int64_t cnt) {
+    typename T::S s;
+    __builtin_memcpy(&s, &bits, sizeof(s));
+    const typename T::C v = widen<T>(s);
+    s = narrow<T>(cnt <= 0x7fffffffLL ? div_count(v, static_cast<int>(cnt)) : v / static_cast<typename T::C>(cnt));
+    __builtin_memcpy(&bits, &s, sizeof(s));
+    return bits;
+}
+template <int ES> __device__ __forceinline__ typename raw_t<ES>::type pool_div(typename raw_t<ES>::type bits, int64_t cnt, int dtype) {
+    if constexpr (ES == 4) return pool_div_as<f32_t>(bits, cnt);
+    else if constexpr (ES == 8) return pool_div_as<f64_t>(bits, cnt);
+    else return dtype == SHIFTND_F16 ? pool_div_as<f16_t>(bits, cnt) : pool_div_as<bf16_t>(bits, cnt);
+}
 
 template <int ES>
 __global__ __launch_bounds__(kThreads) void gradx_embed(const EmbedParams p) {
@@ -84,10 +114,51 @@ __global__ __launch_bounds__(kThreads) void gradx_embed(const EmbedParams p) {
     const int row0 = static_cast<int>(band) * p.rows_per_band;
     const int nrows = min(p.rows_per_band, p.rows - row0);
     const uint32_t pieces = static_cast<uint32_t>(nrows) * static_cast<uint32_t>(p.pc);
-    const int64_t plane_elems = static_cast<int64_t>(p.O0) * p.O1 * p.O2;
+    const int64_t plane_elems = static_cast<int64_t>(p.G0) * p.G1 * p.G2;
     const R *gop = static_cast<const R *>(p.go) + static_cast<int64_t>(plane) * plane_elems;
     const int64_t plane_byte0 = static_cast<int64_t>(plane) * plane_elems * ES;
     shiftnd_u4 *gxp = static_cast<shiftnd_u4 *>(p.gx) + (static_cast<int64_t>(plane) * p.rows + row0) * p.pc;
+
+    if (p.pooled) {
+        // a loop of its own (the whole workgroup takes it or none does), so that the loop below is the code it was without a pool
+        for (uint32_t q = threadIdx.x; q < pieces; q += kThreads) {
+            const uint32_t r = fdiv(q, p.d_pc);
+            const int j0 = static_cast<int>(q - r * static_cast<uint32_t>(p.pc)) * E;
+            const uint32_t row = static_cast<uint32_t>(row0) + r;
+            const uint32_t i0 = fdiv(row, p.d_S1);
+            const int o0 = static_cast<int>(i0) - p.L0;
+            const int o1 = static_cast<int>(row - i0 * static_cast<uint32_t>(p.S1)) - p.L1;
+            const int m0 = (o0 >= 0 && o0 < p.O0) ? gradx_map(o0, p.O0, cs0, p.pad) : -1;
+            const int m1 = (o1 >= 0 && o1 < p.O1) ? gradx_map(o1, p.O1, cs1, p.pad) : -1;
+            shiftnd_u4 out = {0u, 0u, 0u, 0u};
+            if (m0 >= 0 && m1 >= 0) {
+                // the pooled row and the count of its windows along the two outer dims, then E elements of that row
+                const uint32_t q0 = fdiv(static_cast<uint32_t>(m0), p.d_K0), q1 = fdiv(static_cast<uint32_t>(m1), p.d_K1);
+                const int cnt01 = min(p.K0, p.O0 - static_cast<int>(q0) * p.K0) * min(p.K1, p.O1 - static_cast<int>(q1) * p.K1);
+                const int64_t rowbase = (static_cast<int64_t>(q0) * p.G1 + q1) * p.G2;
+                const int oa = j0 - p.L2;
+                int m[E];
+                uint32_t q2[E];
+                R v[E];
+#pragma unroll
+                for (int k = 0; k < E; ++k) {
+                    const int o = oa + k;
+                    m[k] = (o >= 0 && o < p.O2) ? gradx_map(o, p.O2, cs2, p.pad) : -1;
+                    q2[k] = fdiv(static_cast<uint32_t>(m[k] >= 0 ? m[k] : 0), p.d_K2);   // in [0, G2)
+                }
+#pragma unroll
+                for (int k = 0; k < E; ++k) v[k] = gop[rowbase + q2[k]];
+#pragma unroll
+                for (int k = 0; k < E; ++k) {
+                    const int64_t cnt = static_cast<int64_t>(cnt01) * min(p.K2, p.O2 - static_cast<int>(q2[k]) * p.K2);
+                    v[k] = m[k] >= 0 ? pool_div<ES>(v[k], cnt, p.wkind) : R(0);
+                }
+                __builtin_memcpy(&out, v, 16);
+            }
+            __builtin_nontemporal_store(out, gxp + q);
+        }
+        return;
+    }
 
     for (uint32_t q = threadIdx.x; q < pieces; q += kThreads) {
         const uint32_t r = fdiv(q, p.d_pc);
@@ -153,8 +224,47 @@ __global__ __launch_bounds__(kThreads) void gradx_embed(const EmbedParams p) {
 
 // ---- everything else: one element per thread, run-time strides and element width ---------------------------------------
 __global__ __launch_bounds__(kThreads) void gradx_gather(Geometry g, const void *__restrict__ go, const void *__restrict__ w,
-                                                          int wkind, void *__restrict__ gx, int es, int64_t total) {
+                                                          int wkind, void *__restrict__ gx, int es, int64_t total, int pooled) {
     const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+    if (pooled) {
+        // a loop of its own (the whole grid takes it or none does), so that the loop below is the code it was without a pool
+        for (int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; e < total; e += stride) {
+            int64_t r = e;
+            const int64_t i2 = r % g.S[2]; r /= g.S[2];
+            const int64_t i1 = r % g.S[1]; r /= g.S[1];
+            const int64_t i0 = r % g.S[0]; r /= g.S[0];
+            const int64_t c = r % g.C;
+            const int64_t n = r / g.C;
+            int64_t off = n * g.os[0] + c * g.os[1];   // (os are grad_pooled's strides)
+            int64_t cnt = 1;                           // elements of the window that holds this one
+            bool pass = true;
+#pragma unroll 1
+            for (int d = 0; d < 3; ++d) {
+                const int64_t o = (d == 0 ? i0 : (d == 1 ? i1 : i2)) - g.L[d];
+                if (!pass || o < 0 || o >= g.O[d]) {
+                    pass = false;
+                    continue;
+                }
+                const int64_t sh = g.wcol[d] >= 0 ? gather_shift(w, wkind, 0, c * g.nd + g.wcol[d]) : 0;
+                const int64_t t = g.O[d] == 1 ? 0 : pad_index(o + sh, g.O[d], g.pad);
+                if (t < 0) {
+                    pass = false;
+                    continue;
+                }
+                const int64_t q = t / g.K[d];   // the pooled coordinate, in [0, P[d])
+                const int64_t left = g.O[d] - q * g.K[d];
+                cnt *= g.K[d] < left ? g.K[d] : left;
+                off += q * g.os[2 + d];
+            }
+            const int64_t dst = n * g.gs[0] + c * g.gs[1] + i0 * g.gs[2] + i1 * g.gs[3] + i2 * g.gs[4];
+            // an index inside grad_pooled whatever `pass` says (a fill reads the tensor's first element), a select afterwards
+            off = pass ? off : 0;
+            if (es == 2) static_cast<uint16_t *>(gx)[dst] = pass ? pool_div<2>(static_cast<const uint16_t *>(go)[off], cnt, wkind) : uint16_t(0);
+            else if (es == 4) static_cast<uint32_t *>(gx)[dst] = pass ? pool_div<4>(static_cast<const uint32_t *>(go)[off], cnt, wkind) : 0u;
+            else static_cast<uint64_t *>(gx)[dst] = pass ? pool_div<8>(static_cast<const uint64_t *>(go)[off], cnt, wkind) : 0ull;
+        }
+        return;
+    }
     for (int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; e < total; e += stride) {
         int64_t r = e;
         const int64_t i2 = r % g.S[2]; r /= g.S[2];
@@ -211,12 +321,24 @@ int gradx_negate_weights(const Geometry &g, int dtype, const void *w, void *out,
 // pieces a workgroup handles: 8 per thread (32 KiB of grad_x), rounded to whole rows
 constexpr int kEmbedPieces = 8 * kThreads;
 
+// a pool in the geometry: K is 0 when the call has no pool (shiftnd_backward), at least 1 per dim from shiftnd_backward_pooled
+static bool gradx_pooled(const Geometry &g) { return g.K[0] > 0; }
+
 bool gradx_embed_eligible(const Geometry &g, int dtype, const void *go, const void *gx) {
     const int es = dtype_size(dtype);
+    const bool pooled = gradx_pooled(g);
+    if (pooled) {   // 32-bit windows and counts
+        int64_t cnt = 1;
+        for (int d = 0; d < 3; ++d) {
+            if (g.K[d] >= (1LL << 30)) return false;
+            cnt *= std::min(std::max<int64_t>(g.K[d], 1), g.O[d]);
+            if (cnt >= (1LL << 31)) return false;
+        }
+    }
     if (es != 2 && es != 4 && es != 8) return false;
     if ((reinterpret_cast<uintptr_t>(go) | reinterpret_cast<uintptr_t>(gx)) & 15u) return false;
     if ((g.S[2] * es) % 16 != 0) return false;   // grad_x rows of whole 16-byte pieces
-    if (!dense_strides(g.os, g.N, g.C, g.O) || !dense_strides(g.gs, g.N, g.C, g.S)) return false;
+    if (!dense_strides(g.os, g.N, g.C, pooled ? g.P : g.O) || !dense_strides(g.gs, g.N, g.C, g.S)) return false;
     for (int d = 0; d < 3; ++d)
         if (g.S[d] >= (1LL << 30)) return false;
     const int64_t rows = g.S[0] * g.S[1], pc = g.S[2] * es / 16;
@@ -237,6 +359,15 @@ int gradx_embed(const Geometry &g, int dtype, const void *go, const void *w, voi
     p.pad = g.pad;
     p.S0 = static_cast<int>(g.S[0]); p.S1 = static_cast<int>(g.S[1]); p.S2 = static_cast<int>(g.S[2]);
     p.O0 = static_cast<int>(g.O[0]); p.O1 = static_cast<int>(g.O[1]); p.O2 = static_cast<int>(g.O[2]);
+    const bool pooled = gradx_pooled(g);
+    const int64_t *G = pooled ? g.P : g.O;
+    p.G0 = static_cast<int>(G[0]); p.G1 = static_cast<int>(G[1]); p.G2 = static_cast<int>(G[2]);
+    p.pooled = pooled ? 1 : 0;
+    p.K0 = static_cast<int>(std::max<int64_t>(g.K[0], 1)); p.K1 = static_cast<int>(std::max<int64_t>(g.K[1], 1));
+    p.K2 = static_cast<int>(std::max<int64_t>(g.K[2], 1));
+    p.d_K0 = make_fastdiv(static_cast<uint32_t>(p.K0));
+    p.d_K1 = make_fastdiv(static_cast<uint32_t>(p.K1));
+    p.d_K2 = make_fastdiv(static_cast<uint32_t>(p.K2));
     p.L0 = static_cast<int>(g.L[0]); p.L1 = static_cast<int>(g.L[1]); p.L2 = static_cast<int>(g.L[2]);
     p.wc0 = g.wcol[0]; p.wc1 = g.wcol[1]; p.wc2 = g.wcol[2];
     p.C = static_cast<int>(g.C);
@@ -253,9 +384,9 @@ int gradx_embed(const Geometry &g, int dtype, const void *go, const void *w, voi
     p.dper0 = make_fastdiv(static_cast<uint32_t>(map_period(p.O0, g.pad)));
     p.dper1 = make_fastdiv(static_cast<uint32_t>(map_period(p.O1, g.pad)));
     p.dper2 = make_fastdiv(static_cast<uint32_t>(map_period(p.O2, g.pad)));
-    p.go_bytes = g.N * g.C * g.O[0] * g.O[1] * g.O[2] * es;
+    p.go_bytes = g.N * g.C * G[0] * G[1] * G[2] * es;
     const dim3 grid(static_cast<unsigned>(g.N * g.C * p.bands)), block(kThreads);
-    note_kernel("gradx_embed");
+    note_kernel(pooled ? "gradx_embed_pool" : "gradx_embed");
     switch (es) {
     case 2: hipLaunchKernelGGL((gradx_embed<2>), grid, block, 0, st, p); break;
     case 4: hipLaunchKernelGGL((gradx_embed<4>), grid, block, 0, st, p); break;
@@ -268,9 +399,10 @@ int gradx_gather(const Geometry &g, int dtype, const void *go, const void *w, vo
     const int64_t total = g.N * g.C * g.S[0] * g.S[1] * g.S[2];
     const int64_t blocks = (total + kThreads - 1) / kThreads;
     const int64_t cap = 256LL * 32;   // 32 workgroups per CU, grid-stride beyond
-    note_kernel("gradx_gather");
+    const bool pooled = gradx_pooled(g);
+    note_kernel(pooled ? "gradx_gather_pool" : "gradx_gather");
     hipLaunchKernelGGL(gradx_gather, dim3(static_cast<unsigned>(blocks < cap ? blocks : cap)), dim3(kThreads), 0, st, g, go, w, dtype,
-                       gx, dtype_size(dtype), total);
+                       gx, dtype_size(dtype), total, pooled ? 1 : 0);
     return SHIFTND_OK;
 }
 

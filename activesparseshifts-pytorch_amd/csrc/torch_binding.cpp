@@ -785,6 +785,99 @@ template <int ND> Tensor shift_fixed_backward_hip(const Tensor &grad_, const Ten
     return grad_input;
 }
 
+// ---- fixed shifts with a stride: shift{N}d_fixed_pool = avg_pool(shift{N}d_fixed(x)), kernel = stride = pool, ceil_mode ----------
+// The forward is _shift{N}d_pool_forward under the converted table (on HIP tensors the fused sparse forward, active = 0; composed
+// where that answers NOT_FUSED; on CPU tensors the two-step sequence).  The node keeps the table, the borders, the input's sizes and
+// the pool -- never the input, never a full-size tensor -- and its backward is _shift{N}d_fixed_pool_backward: on HIP tensors
+// shiftnd_backward_pooled's x == NULL form, a gather of the pooled gradient with one division.
+using fixed_pool_backward_sig = Tensor(const Tensor &, const Tensor &, const Tensor &, at::IntArrayRef, at::IntArrayRef, int64_t);
+template <int ND> Tensor call_fixed_pool_backward(const Tensor &grad, const Tensor &shifts, const Tensor &borders,
+                                                  at::IntArrayRef input_size, at::IntArrayRef pool, int64_t padding_mode) {
+    static auto op = c10::Dispatcher::singleton()
+                         .findSchemaOrThrow(("torchshifts::_shift" + std::to_string(ND) + "d_fixed_pool_backward").c_str(), "")
+                         .typed<fixed_pool_backward_sig>();
+    return op.call(grad, shifts, borders, input_size, pool, padding_mode);
+}
+
+template <int ND> struct FixedShiftPoolFunction : public torch::autograd::Function<FixedShiftPoolFunction<ND>> {
+    static variable_list forward(AutogradContext *ctx, const Tensor &input, const Tensor &shifts, const Tensor &borders,
+                                 at::IntArrayRef new_size, at::IntArrayRef pool, int64_t padding_mode) {
+        at::AutoDispatchBelowADInplaceOrView guard;
+        Tensor table = fixed_table(shifts, input, ND);
+        auto output = call_pool_forward<ND>(input, table, borders, new_size, pool, padding_mode, false);
+        ctx->saved_data["padding_mode"] = padding_mode;
+        ctx->saved_data["input_size"] = input.sizes().vec();
+        ctx->saved_data["pool"] = pool.vec();
+        ctx->save_for_backward({table, borders});
+        return {output};
+    }
+    static variable_list backward(AutogradContext *ctx, const variable_list &grad_output) {
+        auto saved = ctx->get_saved_variables();
+        const auto padding_mode = ctx->saved_data["padding_mode"].toInt();
+        const auto input_size = ctx->saved_data["input_size"].toIntVector();
+        const auto pool = ctx->saved_data["pool"].toIntVector();
+        return {call_fixed_pool_backward<ND>(grad_output[0], saved[0], saved[1], input_size, pool, padding_mode), Tensor(), Tensor(),
+                Tensor(), Tensor(), Tensor()};
+    }
+};
+
+template <int ND> struct FixedShiftPoolBackwardFunction : public torch::autograd::Function<FixedShiftPoolBackwardFunction<ND>> {
+    static variable_list forward(AutogradContext *ctx, const Tensor &grad, const Tensor &shifts, const Tensor &borders,
+                                 at::IntArrayRef input_size, at::IntArrayRef pool, int64_t padding_mode) {
+        at::AutoDispatchBelowADInplaceOrView guard;
+        return {call_fixed_pool_backward<ND>(grad, shifts, borders, input_size, pool, padding_mode)};
+    }
+    static variable_list backward(AutogradContext *, const variable_list &) {
+        TORCH_CHECK(0, "double backwards on shift", ND, "d_fixed_pool not supported");
+    }
+};
+
+template <int ND> Tensor shift_fixed_pool_public(const Tensor &input, const Tensor &shifts, const Tensor &borders, at::IntArrayRef pool,
+                                                 int64_t padding_mode) {
+    TORCH_CHECK(!input.is_quantized(), "shift", ND, "d_fixed: quantized inputs are not supported (the quantized modules already shift by integers)");
+    TORCH_CHECK(padding_mode >= 0 && padding_mode <= 4, "shift", ND, "d_fixed_pool: padding_mode must be 0..4");
+    check_pool<ND>(pool);
+    auto bands = check_borders(input, borders, ND);
+    return FixedShiftPoolFunction<ND>::apply(input, shifts, std::get<0>(bands), at::IntArrayRef(std::get<1>(bands)), pool, padding_mode)[0];
+}
+
+template <int ND> Tensor fixed_pool_autograd_backward(const Tensor &grad, const Tensor &shifts, const Tensor &borders,
+                                                     at::IntArrayRef input_size, at::IntArrayRef pool, int64_t padding_mode) {
+    return FixedShiftPoolBackwardFunction<ND>::apply(grad, shifts, borders, input_size, pool, padding_mode)[0];
+}
+
+template <int ND> Tensor shift_fixed_pool_backward_hip(const Tensor &grad_, const Tensor &shifts, const Tensor &borders,
+                                                       at::IntArrayRef input_size, at::IntArrayRef pool, int64_t padding_mode) {
+    check_pool<ND>(pool);
+    TORCH_CHECK(grad_.is_cuda(), "grad must be a CUDA tensor");
+    TORCH_CHECK(grad_.dim() == ND + 2 && static_cast<int>(input_size.size()) == ND + 2, "shift", ND, "d_fixed_pool backward: expected ",
+                ND + 2, "-D tensors");
+    TORCH_CHECK(padding_mode >= 0 && padding_mode <= 4, "shift", ND, "d_fixed_pool backward: padding_mode must be 0..4");
+    TORCH_CHECK(grad_.size(0) == input_size[0] && grad_.size(1) == input_size[1], "shift", ND,
+                "d_fixed_pool backward: grad does not match input_size");
+    c10::DeviceGuard device_guard(grad_.device());
+    int32_t b[6], k[3] = {1, 1, 1};
+    read_borders(borders, b);
+    for (int r = 0; r < ND; ++r) k[r] = static_cast<int32_t>(pool[r]);
+    const int dtype = to_shiftnd_dtype(grad_.scalar_type(), "shiftnd_fixed_pool_backward_cuda");
+    Tensor w = fixed_table(shifts, grad_, ND);
+    Tensor grad_input = at::empty(input_size, grad_.options(), at::MemoryFormat::Contiguous);
+    shiftnd_problem p;
+    fill_problem(p, ND, grad_input, b, padding_mode, false, dtype);
+    int64_t ps[3];
+    int rc = shiftnd_pooled_sizes(&p, k, ps);
+    TORCH_CHECK(rc == SHIFTND_OK, "shiftnd_pooled_sizes: ", shiftnd_status_string(rc));
+    for (int r = 0; r < ND; ++r)
+        TORCH_CHECK(grad_.size(2 + r) == ps[r], "shift", ND, "d_fixed_pool backward: grad does not match the pooled size");
+    // the pooled entry points take contiguous tensors: a dense channels-last gradient through the tile transpose, any other layout
+    // through ATen's copy
+    const Tensor grad = is_channels_last_dense(grad_) ? channels_last_to_contiguous(grad_) : grad_.contiguous();
+    rc = shiftnd_backward_pooled(&p, k, grad.data_ptr(), nullptr, w.data_ptr(), grad_input.data_ptr(), nullptr, nullptr, 0,
+                                 current_stream(grad));
+    TORCH_CHECK(rc == SHIFTND_OK, "shiftnd_backward_pooled, input gradient only (HIP): ", shiftnd_status_string(rc));
+    return grad_input;
+}
+
 int64_t cuda_version() { return -1; }  // no CUDA toolkit: extension.py only compares when torch.version.cuda is set
 int64_t hip_version() { return HIP_VERSION; }
 
@@ -822,12 +915,22 @@ TORCH_LIBRARY(torchshifts, m) {
     m.def("torchshifts::_shift1d_fixed_backward(Tensor grad, Tensor shifts, Tensor borders, int[] input_size, int padding_mode) -> Tensor");
     m.def("torchshifts::_shift2d_fixed_backward(Tensor grad, Tensor shifts, Tensor borders, int[] input_size, int padding_mode) -> Tensor");
     m.def("torchshifts::_shift3d_fixed_backward(Tensor grad, Tensor shifts, Tensor borders, int[] input_size, int padding_mode) -> Tensor");
+    // ... followed by avg_pool(kernel = stride = pool, ceil_mode=True) as one op
+    m.def("torchshifts::shift1d_fixed_pool(Tensor input, Tensor shifts, Tensor borders, int[] pool, int padding_mode) -> Tensor", &shift_fixed_pool_public<1>);
+    m.def("torchshifts::shift2d_fixed_pool(Tensor input, Tensor shifts, Tensor borders, int[] pool, int padding_mode) -> Tensor", &shift_fixed_pool_public<2>);
+    m.def("torchshifts::shift3d_fixed_pool(Tensor input, Tensor shifts, Tensor borders, int[] pool, int padding_mode) -> Tensor", &shift_fixed_pool_public<3>);
+    m.def("torchshifts::_shift1d_fixed_pool_backward(Tensor grad, Tensor shifts, Tensor borders, int[] input_size, int[] pool, int padding_mode) -> Tensor");
+    m.def("torchshifts::_shift2d_fixed_pool_backward(Tensor grad, Tensor shifts, Tensor borders, int[] input_size, int[] pool, int padding_mode) -> Tensor");
+    m.def("torchshifts::_shift3d_fixed_pool_backward(Tensor grad, Tensor shifts, Tensor borders, int[] input_size, int[] pool, int padding_mode) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(torchshifts, Autograd, m) {
     m.impl("_shift1d_fixed_backward", TORCH_FN(fixed_autograd_backward<1>));
     m.impl("_shift2d_fixed_backward", TORCH_FN(fixed_autograd_backward<2>));
     m.impl("_shift3d_fixed_backward", TORCH_FN(fixed_autograd_backward<3>));
+    m.impl("_shift1d_fixed_pool_backward", TORCH_FN(fixed_pool_autograd_backward<1>));
+    m.impl("_shift2d_fixed_pool_backward", TORCH_FN(fixed_pool_autograd_backward<2>));
+    m.impl("_shift3d_fixed_pool_backward", TORCH_FN(fixed_pool_autograd_backward<3>));
     m.impl("_shift1d_forward", TORCH_FN(shift_autograd<1>));
     m.impl("_shift1d_backward", TORCH_FN(shift_autograd_backward<1>));
     m.impl("_shift2d_forward", TORCH_FN(shift_autograd<2>));
@@ -856,6 +959,9 @@ TORCH_LIBRARY_IMPL(torchshifts, CUDA, m) {
     m.impl("_shift1d_fixed_backward", TORCH_FN(shift_fixed_backward_hip<1>));
     m.impl("_shift2d_fixed_backward", TORCH_FN(shift_fixed_backward_hip<2>));
     m.impl("_shift3d_fixed_backward", TORCH_FN(shift_fixed_backward_hip<3>));
+    m.impl("_shift1d_fixed_pool_backward", TORCH_FN(shift_fixed_pool_backward_hip<1>));
+    m.impl("_shift2d_fixed_pool_backward", TORCH_FN(shift_fixed_pool_backward_hip<2>));
+    m.impl("_shift3d_fixed_pool_backward", TORCH_FN(shift_fixed_pool_backward_hip<3>));
     m.impl("_shift1d_forward", TORCH_FN(shift_forward_hip<1>));
     m.impl("_shift1d_backward", TORCH_FN(shift_backward_hip<1>));
     m.impl("_shift2d_forward", TORCH_FN(shift_forward_hip<2>));

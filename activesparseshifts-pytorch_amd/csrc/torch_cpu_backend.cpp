@@ -396,6 +396,31 @@ template <int ND> Tensor shift_fixed_backward_cpu(const Tensor &grad, const Tens
     return grad_input;
 }
 
+// fixed shift + average pool, the input gradient: ATen's pool backward, then the gather above (the composed sequence; the fused
+// form is the HIP backend's)
+template <int ND> Tensor shift_fixed_pool_backward_cpu(const Tensor &grad, const Tensor &shifts, const Tensor &borders,
+                                                       at::IntArrayRef input_size, at::IntArrayRef pool, int64_t padding_mode) {
+    TORCH_CHECK(static_cast<int>(pool.size()) == ND, "shift", ND, "d_fixed_pool: pool must hold ", ND, " window sizes");
+    for (auto k : pool) TORCH_CHECK(k >= 1, "shift", ND, "d_fixed_pool: window sizes must be >= 1");
+    TORCH_CHECK(grad.dim() == ND + 2 && static_cast<int>(input_size.size()) == ND + 2, "shift", ND, "d_fixed_pool backward: expected ",
+                ND + 2, "-D tensors");
+    int32_t b[6];
+    read_borders(borders, b);
+    std::vector<int64_t> ysize = {grad.size(0), grad.size(1)};
+    for (int r = 0; r < ND; ++r) ysize.push_back(b[2 * r + 1] - b[2 * r]);
+    Tensor y_like = at::empty(ysize, grad.options());  // avg_pool's backward only looks at its shape
+    Tensor g;
+    if constexpr (ND == 1) {
+        g = at::avg_pool2d_backward(grad.unsqueeze(2), y_like.unsqueeze(2), {1, pool[0]}, {1, pool[0]}, {0, 0}, true, true,
+                                    c10::nullopt).squeeze(2);
+    } else if constexpr (ND == 2) {
+        g = at::avg_pool2d_backward(grad, y_like, pool, pool, {0, 0}, true, true, c10::nullopt);
+    } else {
+        g = at::avg_pool3d_backward(grad, y_like, pool, pool, {0, 0, 0}, true, true, c10::nullopt);
+    }
+    return shift_fixed_backward_cpu<ND>(g, shifts, borders, input_size, padding_mode);
+}
+
 template <int ND> Tensor qshift_forward_cpu(const Tensor &input, const Tensor &weights, const Tensor &borders,
                                             at::IntArrayRef new_size, int64_t padding_mode, bool /*active_flag*/) {
     TORCH_CHECK(input.is_quantized() && weights.is_quantized(), "q_shiftnd_cpu: expected quantized tensors");
@@ -443,6 +468,9 @@ TORCH_LIBRARY_IMPL(torchshifts, CPU, m) {
     m.impl("_shift1d_fixed_backward", TORCH_FN(shift_fixed_backward_cpu<1>));
     m.impl("_shift2d_fixed_backward", TORCH_FN(shift_fixed_backward_cpu<2>));
     m.impl("_shift3d_fixed_backward", TORCH_FN(shift_fixed_backward_cpu<3>));
+    m.impl("_shift1d_fixed_pool_backward", TORCH_FN(shift_fixed_pool_backward_cpu<1>));
+    m.impl("_shift2d_fixed_pool_backward", TORCH_FN(shift_fixed_pool_backward_cpu<2>));
+    m.impl("_shift3d_fixed_pool_backward", TORCH_FN(shift_fixed_pool_backward_cpu<3>));
 }
 
 TORCH_LIBRARY_IMPL(torchshifts, QuantizedCPU, m) {

@@ -273,6 +273,22 @@ def backward_pooled(grad_pooled, w, x, pad, active, pool, borders=None, grad_x=N
     return grad_x, grad_w
 
 
+def backward_pooled_input(grad_pooled, w, input_shape, pad, pool, borders=None, grad_x=None):
+    """Input gradient only of the sparse shift + average pool: shiftnd_backward_pooled with x == NULL and grad_w == NULL (no read
+    of the input, no weight gradient, no workspace).  grad_pooled: contiguous device tensor of the pooled sizes; w: [C, nd] float
+    table of its dtype; input_shape: the input's sizes; borders: the 6 absolute ints of check_borders (None = the whole input).
+    Returns grad_x (new, contiguous)."""
+    assert grad_pooled.is_contiguous()
+    like = torch.empty(list(input_shape), dtype=grad_pooled.dtype, device="meta")
+    p = problem(like, pad, False, borders)
+    w = w.contiguous()
+    if grad_x is None:
+        grad_x = _new(input_shape, grad_pooled)
+    check(lib().shiftnd_backward_pooled(ctypes.byref(p), _pool_arg(pool, p.ndim), grad_pooled.data_ptr(), None, w.data_ptr(),
+                                        grad_x.data_ptr(), None, None, 0, _stream()), "shiftnd_backward_pooled (input gradient only)")
+    return grad_x
+
+
 def to_contiguous(x):
     """channels-last dense [N, C, spatial...] device tensor -> new contiguous tensor (shiftnd_transpose)"""
     out = torch.empty(x.shape, dtype=x.dtype, device=x.device)

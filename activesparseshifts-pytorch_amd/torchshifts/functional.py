@@ -86,8 +86,8 @@ def shift3d_pool_func(input: Tensor, weights: Tensor, padding_mode: int, active_
 # borders); the backward returns the input gradient alone -- the autograd node keeps the table, not the input, and on HIP tensors
 # no kernel reads the input or forms a weight gradient.  The table is converted to the input's dtype: exact for |shift| <= 256
 # in bfloat16, <= 2048 in float16.
-def _shift_fixed_func(dim: int, input: Tensor, shifts: Tensor, padding_mode: int, borders: Optional[Tensor]) -> Tensor:
-    name = f"shift{dim}d_fixed_func()"
+def _shift_fixed_func(dim: int, input: Tensor, shifts: Tensor, padding_mode: int, borders: Optional[Tensor], pool=None) -> Tensor:
+    name = f"shift{dim}d_fixed_func()" if pool is None else f"shift{dim}d_fixed_pool_func()"
     _assert_has_ops()
     assert padding_mode in [0, 1, 2, 3, 4], f"{name} expected padding_mode can be {_PADDING_DOC}"
     assert len(input.shape) == dim + 2, f"{name}: expected {dim + 2}D tensor as input, but it is shape is {input.shape}"
@@ -104,6 +104,12 @@ def _shift_fixed_func(dim: int, input: Tensor, shifts: Tensor, padding_mode: int
             f"borders must have shape [{dim}, 2]"
     else:
         borders = torch.Tensor()
+    if pool is not None:
+        if isinstance(pool, torch.Tensor):
+            pool = pool.reshape(-1).tolist()
+        pool = [int(pool)] * dim if isinstance(pool, (int, float)) else [int(k) for k in pool]
+        assert len(pool) == dim and all(k >= 1 for k in pool), f"{name}: pool must be {dim} window sizes >= 1"
+        return getattr(torch.ops.torchshifts, f"shift{dim}d_fixed_pool")(input, shifts, borders, pool, padding_mode)
     return getattr(torch.ops.torchshifts, f"shift{dim}d_fixed")(input, shifts, borders, padding_mode)
 
 
@@ -120,3 +126,27 @@ def shift2d_fixed_func(input: Tensor, shifts: Tensor, padding_mode: int, borders
 def shift3d_fixed_func(input: Tensor, shifts: Tensor, padding_mode: int, borders: Optional[Tensor] = None) -> Tensor:
     """Shift a [N, C, H, W, D] tensor by the integers of shifts [C, 3] (H, W, D); borders [3, 2]."""
     return _shift_fixed_func(3, input, shifts, padding_mode, borders)
+
+
+# ---- fixed shift + average pool as one op -----------------------------------------------------------------------------------
+# `pool` is the window (= stride) per spatial dim, an int or a list.  The result equals
+# avg_pool{N}d(shift{N}d_fixed_func(...), kernel_size=pool, stride=pool, ceil_mode=True), the tail of a fixed layer that emulates a
+# strided depthwise conv.  On HIP tensors the full-size shift output is never written (the fused sparse forward under the table) and
+# the backward gathers the input gradient straight from the pooled gradient, one division per element: the autograd node keeps the
+# table, the borders, the input's sizes and the pool, no tensor of the input's size.  On CPU tensors the op is that two-step sequence.
+def shift1d_fixed_pool_func(input: Tensor, shifts: Tensor, padding_mode: int, pool=2, borders: Optional[Tensor] = None) -> Tensor:
+    """Shift a [N, C, H] tensor by the integers of shifts [C, 1], then avg_pool1d(kernel_size=pool, stride=pool, ceil_mode=True),
+    as one op; pool: an int or 1 window sizes; borders [1, 2] = (cut_left, cut_right) per dim."""
+    return _shift_fixed_func(1, input, shifts, padding_mode, borders, pool)
+
+
+def shift2d_fixed_pool_func(input: Tensor, shifts: Tensor, padding_mode: int, pool=2, borders: Optional[Tensor] = None) -> Tensor:
+    """Shift a [N, C, H, W] tensor by the integers of shifts [C, 2] (H, W), then avg_pool2d(kernel_size=pool, stride=pool, ceil_mode=True),
+    as one op; pool: an int or 2 window sizes; borders [2, 2] = (cut_left, cut_right) per dim."""
+    return _shift_fixed_func(2, input, shifts, padding_mode, borders, pool)
+
+
+def shift3d_fixed_pool_func(input: Tensor, shifts: Tensor, padding_mode: int, pool=2, borders: Optional[Tensor] = None) -> Tensor:
+    """Shift a [N, C, H, W, D] tensor by the integers of shifts [C, 3] (H, W, D), then avg_pool3d(kernel_size=pool, stride=pool, ceil_mode=True),
+    as one op; pool: an int or 3 window sizes; borders [3, 2] = (cut_left, cut_right) per dim."""
+    return _shift_fixed_func(3, input, shifts, padding_mode, borders, pool)

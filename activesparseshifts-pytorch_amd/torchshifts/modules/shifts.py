@@ -11,14 +11,16 @@ from functools import partial
 import torch
 from torch import nn
 
-from torchshifts.functional import (shift1d_fixed_func, shift1d_func, shift1d_pool_func, shift2d_fixed_func, shift2d_func,
-                                    shift2d_pool_func, shift3d_fixed_func, shift3d_func, shift3d_pool_func)
+from torchshifts.functional import (shift1d_fixed_func, shift1d_fixed_pool_func, shift1d_func, shift1d_pool_func, shift2d_fixed_func,
+                                    shift2d_fixed_pool_func, shift2d_func, shift2d_pool_func, shift3d_fixed_func,
+                                    shift3d_fixed_pool_func, shift3d_func, shift3d_pool_func)
 
 paddings_dict = {'zeros': 0, 'border': 1, 'periodic': 2, 'reflect': 3, 'symmetric': 4}
 
 _SHIFT_FUNCS = {1: shift1d_func, 2: shift2d_func, 3: shift3d_func}
 _SHIFT_POOL_FUNCS = {1: shift1d_pool_func, 2: shift2d_pool_func, 3: shift3d_pool_func}
 _SHIFT_FIXED_FUNCS = {1: shift1d_fixed_func, 2: shift2d_fixed_func, 3: shift3d_fixed_func}
+_SHIFT_FIXED_POOL_FUNCS = {1: shift1d_fixed_pool_func, 2: shift2d_fixed_pool_func, 3: shift3d_fixed_pool_func}
 _AVG_POOLS = {1: torch.nn.functional.avg_pool1d, 2: torch.nn.functional.avg_pool2d, 3: torch.nn.functional.avg_pool3d}
 
 
@@ -199,8 +201,8 @@ class _GroupedShiftnd(nn.Module):
         padding (str): 'zeros' | 'border' | 'periodic' | 'reflect' | 'symmetric'. Default 'zeros'.
         shifts (tensor / nested list): a [in_channels, dim] table of integers that replaces the default one.
         emulate_dw (dict): parameters of the depthwise conv this layer replaces (kernel_size, stride, padding): the output is
-            cut as Shift{N}d cuts it, and with a stride > 1 followed by the same avg_pool{N}d(ceil_mode=True) (through ATen:
-            there is no fused fixed shift + pool kernel); its kernel_size also sizes the default table.
+            cut as Shift{N}d cuts it, and with a stride > 1 followed by the same avg_pool{N}d(ceil_mode=True), shift and pool as
+            one op (shift{N}d_fixed_pool: on HIP tensors fused in both directions); its kernel_size also sizes the default table.
     forward(x) -> (output, None): the pair convention of Shift{N}d with sparsity_term == 0.
     """
     dim = None
@@ -257,10 +259,9 @@ class _GroupedShiftnd(nn.Module):
 
     def forward(self, input):
         """Returns (output, None)."""
-        out = _SHIFT_FIXED_FUNCS[self.dim](input, self.shifts, self.padding, self.cut_borders)
         if self._pool_size is not None:
-            out = _AVG_POOLS[self.dim](out, kernel_size=self._pool_size, stride=self._pool_size, ceil_mode=True)
-        return out, None
+            return _SHIFT_FIXED_POOL_FUNCS[self.dim](input, self.shifts, self.padding, self._pool_size, self.cut_borders), None
+        return _SHIFT_FIXED_FUNCS[self.dim](input, self.shifts, self.padding, self.cut_borders), None
 
     def extra_repr(self):
         pad = {v: k for k, v in paddings_dict.items()}[self.padding]

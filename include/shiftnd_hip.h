@@ -219,6 +219,17 @@ SHIFTND_API int shiftnd_forward_quantized(const shiftnd_problem *p,
  *   partial-sum groups than the plain backward of the same tensor).
  * Return SHIFTND_ERR_NOT_FUSED when the geometry is not served (the caller then runs shift and pool
  * separately); nothing has been launched in that case.
+ *
+ * shiftnd_backward_pooled, input gradient only (fixed / frozen shifts with a stride): x == NULL and grad_w == NULL together,
+ * p->active == 0 -- the convention of shiftnd_backward.  Nothing of the input is read and no weight gradient is formed:
+ *   grad_x[n,c,i,j,k] = inside the window ? grad_pooled[n,c, t_i / K_i, t_j / K_j, t_k / K_k] / cnt : 0
+ *   t_d = pad(o_d + s_d) in [0, O_d),  o_d = i_d - l_d,  s = rint(w),  O_d = r_d - l_d,  K = pool
+ *   cnt = prod_d min(K_d, O_d - (t_d / K_d) * K_d)        (ceil_mode: the last window of a dim may be partial)
+ * the sparse shift's grad_x applied to ATen's average-pool backward: a gather of grad_pooled with one division, in fp32 for
+ * fp16 / bf16 tensors and fp64 for fp64, rounded once to the tensor type -- bit for bit the grad_x of the full form for a
+ * sparse shift, and of the two-step sequence.  No workspace: workspace may be NULL with workspace_bytes == 0.  This form never
+ * returns SHIFTND_ERR_NOT_FUSED (the element-wide kernel serves every geometry).  p->active == 1 with this form, or only one of
+ * x / grad_w NULL, is SHIFTND_ERR_INVALID_ARGUMENT; nothing is launched.
  */
 SHIFTND_API int shiftnd_pooled_sizes(const shiftnd_problem *p, const int32_t *pool, int64_t pooled_spatial[3]);
 
