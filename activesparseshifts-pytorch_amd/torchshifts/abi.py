@@ -289,19 +289,24 @@ def backward_pooled_input(grad_pooled, w, input_shape, pad, pool, borders=None, 
     return grad_x
 
 
-def to_contiguous(x):
-    """channels-last dense [N, C, spatial...] device tensor -> new contiguous tensor (shiftnd_transpose)"""
-    out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+def to_contiguous(x, out=None):
+    """channels-last dense [N, C, spatial...] device tensor -> new contiguous tensor (shiftnd_transpose), or fills the contiguous `out`"""
+    if out is None:
+        out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    assert out.shape == x.shape and out.dtype == x.dtype and out.is_contiguous()
     P = x[0, 0].numel()
     check(lib().shiftnd_transpose(x.data_ptr(), out.data_ptr(), x.shape[0], P, x.shape[1], x.element_size(), _stream()),
           "shiftnd_transpose")
     return out
 
 
-def to_channels_last(x):
-    """contiguous [N, C, spatial...] device tensor -> new channels-last dense tensor (shiftnd_transpose)"""
+def to_channels_last(x, out=None):
+    """contiguous [N, C, spatial...] device tensor -> new channels-last dense tensor (shiftnd_transpose), or fills the
+    channels-last dense `out`"""
     fmt = torch.channels_last if x.dim() == 4 else torch.channels_last_3d
-    out = torch.empty(x.shape, dtype=x.dtype, device=x.device, memory_format=fmt)
+    if out is None:
+        out = torch.empty(x.shape, dtype=x.dtype, device=x.device, memory_format=fmt)
+    assert out.shape == x.shape and out.dtype == x.dtype and out.is_contiguous(memory_format=fmt)
     P = x[0, 0].numel()
     check(lib().shiftnd_transpose(x.data_ptr(), out.data_ptr(), x.shape[0], x.shape[1], P, x.element_size(), _stream()),
           "shiftnd_transpose")

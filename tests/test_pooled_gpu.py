@@ -242,6 +242,38 @@ def aten_inv(cnt):
     return np.float32(1.0) / (np.float32(1.0) / mult)
 
 
+def quantized_pool_inputs(rs, nd, shape, npdt):
+    """-> xq, wq, x zero point of one case of CASES + QCASES (the weight zero point is 128), drawn from `rs`"""
+    info = np.iinfo(npdt)
+    xq = rs.randint(info.min, info.max + 1, size=shape).astype(npdt)
+    wq = rs.randint(123, 134, size=(shape[1], nd)).astype(np.uint8)
+    wq[0] = 128 + shape[-1] + 2 if shape[-1] < 120 else 130
+    if nd == 2 and shape[1] == 6 and (shape[-1] >= 200 or shape[-1] == 52):   # the band cases: shifts around the pads' edges and partially in range
+        for ch, (sr, sc) in enumerate(BAND_SHIFTS, start=1):
+            wq[ch] = [128 + (shape[2] // 2 if sr is None else sr), 128 - (shape[3] // 2 - 14 if sc is None else -sc)]
+    return xq, wq, 7 if npdt == np.uint8 else -9
+
+
+def quantized_pool_references(xq, wq, zp, pad, pool, b, new):
+    """the oracle's quantized shift followed by ATen's QuantizedCPU average-pool arithmetic restated in numpy (shared with
+    tests/test_redzone_gpu.py) -> [zero point inside the rounding, zero point outside]: the two `requant` forms"""
+    npdt, nd = xq.dtype, xq.ndim - 2
+    info = np.iinfo(npdt)
+    y = O.forward_q(xq, wq, 128, zp, pad, b).astype(np.int64) - zp
+    psz = [-(-new[2 + r] // pool[r]) for r in range(nd)]
+    refs = [np.zeros(list(new[:2]) + psz, dtype=npdt) for _ in range(2)]
+    for idx in np.ndindex(*psz):
+        sl = tuple(slice(idx[r] * pool[r], min((idx[r] + 1) * pool[r], new[2 + r])) for r in range(nd))
+        win = y[(slice(None), slice(None)) + sl]
+        cnt = int(np.prod(win.shape[2:]))
+        s32 = win.reshape(win.shape[0], win.shape[1], -1).sum(axis=2).astype(np.float32)
+        q_in = np.rint(np.float32(zp) + s32 * aten_inv(cnt)).astype(np.int64)
+        q_out = np.rint(s32 * np.float32(1.0 / cnt)).astype(np.int64) + zp
+        for ref, q in zip(refs, (q_in, q_out)):
+            ref[(slice(None), slice(None)) + idx] = np.clip(q, info.min, info.max).astype(npdt)
+    return refs
+
+
 @pytest.mark.parametrize("npdt", [np.uint8, np.int8])
 def test_quantized_pooled_forward_vs_oracle(abi, npdt):
     """shiftnd_forward_quantized_pooled (csrc/shiftnd_qpool.hip) through the C ABI: the oracle's quantized shift followed by
@@ -251,31 +283,13 @@ def test_quantized_pooled_forward_vs_oracle(abi, npdt):
     test_quantized_avg_pool_restatement_matches_aten); odd zero points so that the two differ; every padding, crops, ragged
     last windows, 1-D / 2-D / 3-D"""
     rs = np.random.RandomState(21)
-    info = np.iinfo(npdt)
     differ = False
     served = set()
     for nd, shape, pool, crop in CASES + QCASES:
-        xq = rs.randint(info.min, info.max + 1, size=shape).astype(npdt)
-        wq = rs.randint(123, 134, size=(shape[1], nd)).astype(np.uint8)
-        wq[0] = 128 + shape[-1] + 2 if shape[-1] < 120 else 130
-        if nd == 2 and shape[1] == 6 and (shape[-1] >= 200 or shape[-1] == 52):   # the band cases: shifts around the pads' edges and partially in range
-            for ch, (sr, sc) in enumerate(BAND_SHIFTS, start=1):
-                wq[ch] = [128 + (shape[2] // 2 if sr is None else sr), 128 - (shape[3] // 2 - 14 if sc is None else -sc)]
-        zp = 7 if npdt == np.uint8 else -9
+        xq, wq, zp = quantized_pool_inputs(rs, nd, shape, npdt)
         b, new = abi.check_borders(list(shape), crop, nd)
         for pad in range(5):
-            y = O.forward_q(xq, wq, 128, zp, pad, b).astype(np.int64) - zp
-            psz = [-(-new[2 + r] // pool[r]) for r in range(nd)]
-            refs = [np.zeros(list(new[:2]) + psz, dtype=npdt) for _ in range(2)]
-            for idx in np.ndindex(*psz):
-                sl = tuple(slice(idx[r] * pool[r], min((idx[r] + 1) * pool[r], new[2 + r])) for r in range(nd))
-                win = y[(slice(None), slice(None)) + sl]
-                cnt = int(np.prod(win.shape[2:]))
-                s32 = win.reshape(win.shape[0], win.shape[1], -1).sum(axis=2).astype(np.float32)
-                q_in = np.rint(np.float32(zp) + s32 * aten_inv(cnt)).astype(np.int64)
-                q_out = np.rint(s32 * np.float32(1.0 / cnt)).astype(np.int64) + zp
-                for ref, q in zip(refs, (q_in, q_out)):
-                    ref[(slice(None), slice(None)) + idx] = np.clip(q, info.min, info.max).astype(npdt)
+            refs = quantized_pool_references(xq, wq, zp, pad, pool, b, new)
             differ = differ or not np.array_equal(refs[0], refs[1])
             for requant, ref in zip((abi.REQUANT_ZP_INSIDE, abi.REQUANT_ZP_OUTSIDE), refs):
                 for knob in (0, 1):  # 0: the per-channel plane kernel where it serves, 1: one thread per pooled element
