@@ -20,6 +20,19 @@ thread_local int g_policy = 0;  // 0 auto, 1 force strided, 2 plane kernels (or 
 bool is_float_dtype(int dt) { return dt >= SHIFTND_F32 && dt <= SHIFTND_BF16; }
 bool is_quant_dtype(int dt) { return dt >= SHIFTND_I8 && dt <= SHIFTND_I32; }
 
+// Mixed precision (SHIFTND_WEIGHTS_F32 on p->dtype): fp32 weights and grad_w with fp16 / bf16 tensors.  `q` becomes the problem
+// with the tensors' plain dtype -- all the routing below sees -- and `wkind` the element type of the weights (and of grad_w): q.dtype
+// without the flag.  The flag on any other dtype is SHIFTND_ERR_UNSUPPORTED_DTYPE.
+int split_dtype(const shiftnd_problem *p, shiftnd_problem &q, int &wkind) {
+    q = *p;
+    q.dtype = p->dtype & ~SHIFTND_WEIGHTS_F32;
+    wkind = q.dtype;
+    if (!(p->dtype & SHIFTND_WEIGHTS_F32)) return SHIFTND_OK;
+    if (q.dtype != SHIFTND_F16 && q.dtype != SHIFTND_BF16) return SHIFTND_ERR_UNSUPPORTED_DTYPE;
+    wkind = SHIFTND_F32;
+    return SHIFTND_OK;
+}
+
 // Build the normalised 3-dim geometry: real spatial dim r (0..nd-1 = H, W, D) becomes normalised
 // dim r + 3 - nd, so the innermost (contiguous) dim is always index 2 and leading dims have size 1.
 int build_geometry(const shiftnd_problem *p, const int64_t *xs, const int64_t *os, const int64_t *gs, Geometry &g) {
@@ -161,7 +174,7 @@ int forward_common(const shiftnd_problem *p, const void *x, const int64_t *xs, c
         // (interpolating problems keep the LDS-staged plane kernels whenever those take them: see DESIGN 3.14)
         const bool interpolating = g.active && p->dtype <= SHIFTND_BF16;
         const bool prefer_sweep = (out_plane_bytes >= 32 * 1024 && !interpolating && !(can_plane && plane_forward_lds_gather(g, p->dtype, x, out))) || !can_plane;
-        if (g_policy == 0 && g_flat == 2 && wkind == p->dtype && flat_forward_eligible(g, p->dtype, x, out)) {   // (knob 27 = 2: tests)
+        if (g_policy == 0 && g_flat == 2 && wkind <= SHIFTND_BF16 && flat_forward_eligible(g, p->dtype, x, out)) {   // (knob 27 = 2: tests)
             g_last_path = SHIFTND_PATH_PLANE;
             return finish(flat_forward(g, p->dtype, x, w, wkind, out, st));
         }
@@ -173,17 +186,17 @@ int forward_common(const shiftnd_problem *p, const void *x, const int64_t *xs, c
         // cropped windows with ragged rows, 1-D rows of any length, ragged source rows (float tensors): one-step workgroups over
         // row spans -- what the aligned one-step forwards below do not take
         // cropped 16-bit volumes under zeros padding, interpolating: the walk through the planes with the window inside (round 6)
-        if (g_policy == 0 && wkind == p->dtype && cropped(g) && walk16_forward_eligible(g, p->dtype, x, out)) {
+        if (g_policy == 0 && wkind <= SHIFTND_BF16 && cropped(g) && walk16_forward_eligible(g, p->dtype, x, out)) {
             g_last_path = SHIFTND_PATH_PLANE;
             return finish(walk16_forward(g, p->dtype, x, w, wkind, out, st));
         }
-        if (g_policy == 0 && wkind == p->dtype && !step_forward_lds_eligible(g, p->dtype, x, out) && span_forward_eligible(g, p->dtype, x, out)) {
+        if (g_policy == 0 && wkind <= SHIFTND_BF16 && !step_forward_lds_eligible(g, p->dtype, x, out) && span_forward_eligible(g, p->dtype, x, out)) {
             g_last_path = SHIFTND_PATH_PLANE;
             return finish(span_forward(g, p->dtype, x, w, wkind, out, st));
         }
         // rows that are not whole 16-byte pieces (14 x 14, 62 x 62, 222 x 222 ...; float tensors): one-step workgroups over the
         // tensor's flat chunk stream
-        if (g_policy == 0 && wkind == p->dtype && ragged_rows(g, p->dtype) && flat_forward_eligible(g, p->dtype, x, out)) {
+        if (g_policy == 0 && wkind <= SHIFTND_BF16 && ragged_rows(g, p->dtype) && flat_forward_eligible(g, p->dtype, x, out)) {
             g_last_path = SHIFTND_PATH_PLANE;
             return finish(flat_forward(g, p->dtype, x, w, wkind, out, st));
         }
@@ -200,7 +213,7 @@ int forward_common(const shiftnd_problem *p, const void *x, const int64_t *xs, c
         }
         // 2-D sparse shift of 4- / 8-byte elements on planes of >= 32 KiB: the linear sweep of one-step workgroups
         // 3-D interpolating forward: a walk through the planes (one new plane per step, the other carried in registers)
-        if (g_policy == 0 && wkind == p->dtype && walk16_forward_eligible(g, p->dtype, x, out)) {
+        if (g_policy == 0 && wkind <= SHIFTND_BF16 && walk16_forward_eligible(g, p->dtype, x, out)) {
             g_last_path = SHIFTND_PATH_PLANE;
             return finish(walk16_forward(g, p->dtype, x, w, wkind, out, st));
         }
@@ -223,17 +236,17 @@ int forward_common(const shiftnd_problem *p, const void *x, const int64_t *xs, c
     }
     // windows no chunk kernel took (output planes that are not a whole number of 16-byte pieces): the flat chunk stream before the
     // one-thread-per-element kernels
-    if (g_policy == 0 && wkind == p->dtype && cropped(g) && flat_forward_eligible(g, p->dtype, x, out)) {
+    if (g_policy == 0 && wkind <= SHIFTND_BF16 && cropped(g) && flat_forward_eligible(g, p->dtype, x, out)) {
         g_last_path = SHIFTND_PATH_PLANE;
         return finish(flat_forward(g, p->dtype, x, w, wkind, out, st));
     }
     if (g_policy == 0 && small_forward_eligible(g, p->dtype)) {  // interpolating, rows not whole 16-byte pieces, small planes
         g_last_path = SHIFTND_PATH_PLANE;
-        return finish(small_forward(g, p->dtype, x, w, out, st));
+        return finish(small_forward(g, p->dtype, x, w, wkind, out, st));
     }
-    if (g_policy == 0 && wkind == p->dtype && plane_ragged_forward_eligible(g, p->dtype, x, out)) {  // ... larger 3-D volumes: narrow chunks
+    if (g_policy == 0 && wkind <= SHIFTND_BF16 && plane_ragged_forward_eligible(g, p->dtype, x, out)) {  // ... larger 3-D volumes: narrow chunks
         g_last_path = SHIFTND_PATH_PLANE;
-        return finish(plane_ragged_forward(g, p->dtype, x, w, out, st));
+        return finish(plane_ragged_forward(g, p->dtype, x, w, wkind, out, st));
     }
     if ((g_policy == 0 || g_policy == 4) && cl_tiled_forward_eligible(g, p->dtype, x, out)) {  // channels-last in, LDS-tiled
         g_last_path = SHIFTND_PATH_CL;
@@ -322,6 +335,10 @@ int shiftnd_check_borders(const int64_t *sizes, int nsizes, const int32_t *user,
 int shiftnd_forward_serves_channels_last(const shiftnd_problem *p, const void *x, const int64_t x_strides[5], const void *out,
                                          const int64_t out_strides[5]) {
     if (!p || !x_strides || !out_strides || g_policy != 0) return 0;
+    shiftnd_problem q;
+    int wkind;
+    if (split_dtype(p, q, wkind) != SHIFTND_OK) return 0;
+    p = &q;   // (the weights' type changes no route: the same answer with and without SHIFTND_WEIGHTS_F32)
     Geometry g;
     if (build_geometry(p, x_strides, out_strides, nullptr, g) != SHIFTND_OK || empty_problem(g)) return 0;
     // 16-bit interpolation: one layout change + the contiguous kernel is faster than the tiled kernel (N16 C256 224x224
@@ -341,7 +358,11 @@ int shiftnd_forward_serves_channels_last(const shiftnd_problem *p, const void *x
 int shiftnd_backward_serves_channels_last(const shiftnd_problem *p, const void *grad_out, const int64_t grad_out_strides[5],
                                           const void *x, const int64_t x_strides[5], const void *grad_x,
                                           const int64_t grad_x_strides[5]) {
-    if (!p || !grad_out_strides || !x_strides || !grad_x_strides || g_policy != 0 || !is_float_dtype(p->dtype)) return 0;
+    if (!p || !grad_out_strides || !x_strides || !grad_x_strides || g_policy != 0) return 0;
+    shiftnd_problem q;
+    int wkind;
+    if (split_dtype(p, q, wkind) != SHIFTND_OK || !is_float_dtype(q.dtype)) return 0;
+    p = &q;
     Geometry g;
     if (build_geometry(p, x_strides, grad_out_strides, grad_x_strides, g) != SHIFTND_OK) return 0;
     if (g.N == 0 || g.C == 0 || g.S[0] * g.S[1] * g.S[2] == 0) return 0;
@@ -360,8 +381,10 @@ int shiftnd_backward_serves_channels_last(const shiftnd_problem *p, const void *
 int shiftnd_forward(const shiftnd_problem *p, const void *x, const int64_t x_strides[5], const void *weights, void *out,
                     const int64_t out_strides[5], void *stream) {
     if (!p || !x_strides || !out_strides) return SHIFTND_ERR_INVALID_ARGUMENT;
-    if (!is_float_dtype(p->dtype)) return SHIFTND_ERR_UNSUPPORTED_DTYPE;
-    return forward_common(p, x, x_strides, weights, p->dtype, 0, 0ull, out, out_strides, stream);
+    shiftnd_problem q;
+    int wkind;
+    if (split_dtype(p, q, wkind) != SHIFTND_OK || !is_float_dtype(q.dtype)) return SHIFTND_ERR_UNSUPPORTED_DTYPE;
+    return forward_common(&q, x, x_strides, weights, wkind, 0, 0ull, out, out_strides, stream);
 }
 
 int shiftnd_forward_quantized(const shiftnd_problem *p, const void *x, const int64_t x_strides[5], const void *wq,
@@ -395,6 +418,10 @@ static size_t backward_workspace_now(const Geometry &g, int dtype) {
 
 size_t shiftnd_backward_workspace_bytes(const shiftnd_problem *p) {
     if (!p) return 0;
+    shiftnd_problem q;
+    int wkind;
+    if (split_dtype(p, q, wkind) != SHIFTND_OK) return 0;
+    p = &q;   // (the records are fp64 whatever the weights are: the same bytes with and without SHIFTND_WEIGHTS_F32)
     // the layout of the partial-sum buffer depends only on the geometry: evaluate every family's plan
     const int64_t unit[5] = {0, 0, 0, 0, 0};
     Geometry g;
@@ -433,7 +460,12 @@ static int backward_planned(const shiftnd_problem *p, const void *grad_out, cons
     // x == NULL && grad_w == NULL: the input gradient only (the sparse shift's grad_x is a gather of grad_out; shiftnd_gradx.hip)
     const bool input_only = !x && !grad_w;
     if (!p || !grad_out_strides || !grad_x_strides || (!x_strides && !input_only)) return SHIFTND_ERR_INVALID_ARGUMENT;
-    if (!is_float_dtype(p->dtype)) return SHIFTND_ERR_UNSUPPORTED_DTYPE;
+    shiftnd_problem q;
+    int wkind;   // element type of `weights` and `grad_w`
+    if (split_dtype(p, q, wkind) != SHIFTND_OK || !is_float_dtype(q.dtype)) return SHIFTND_ERR_UNSUPPORTED_DTYPE;
+    // (the fixed ops convert their integer table to the tensors' type themselves: the x == NULL form takes no fp32 table)
+    if (input_only && wkind != q.dtype) return SHIFTND_ERR_INVALID_ARGUMENT;
+    p = &q;
     Geometry g;
     const int rc = build_geometry(p, x_strides ? x_strides : grad_x_strides, grad_out_strides, grad_x_strides, g);
     if (rc != SHIFTND_OK) return rc;
@@ -442,7 +474,7 @@ static int backward_planned(const shiftnd_problem *p, const void *grad_out, cons
         // nothing to differentiate; grad_w (if any channels) is all zeros (zeros_like, shifts_cpu.cpp:247)
         g_last_path = SHIFTND_PATH_EMPTY;
         if (g.C > 0 && grad_w)
-            if (hipMemsetAsync(grad_w, 0, static_cast<size_t>(g.C) * g.nd * dtype_size(p->dtype), st) != hipSuccess)
+            if (hipMemsetAsync(grad_w, 0, static_cast<size_t>(g.C) * g.nd * dtype_size(wkind), st) != hipSuccess)
                 return SHIFTND_ERR_LAUNCH_FAILED;
         return SHIFTND_OK;
     }
@@ -467,7 +499,7 @@ static int backward_planned(const shiftnd_problem *p, const void *grad_out, cons
     if (g_policy == 0 && g_flat == 2 && flat_backward_eligible(g, p->dtype, grad_out, x, grad_x)) {   // (knob 27 = 2: tests)
         if (flat_backward_workspace(g) > workspace_bytes) return SHIFTND_ERR_WORKSPACE_TOO_SMALL;
         g_last_path = SHIFTND_PATH_PLANE;
-        return finish(flat_backward(g, p->dtype, grad_out, x, weights, grad_x, grad_w, workspace, st));
+        return finish(flat_backward(g, p->dtype, grad_out, x, weights, wkind, grad_x, grad_w, workspace, st));
     }
     const bool can_sweep = sweep_backward_eligible(g, p->dtype, grad_out, x, grad_x);
     const bool can_plane = plane_backward_eligible(g, p->dtype, grad_out, x, grad_x);
@@ -477,13 +509,13 @@ static int backward_planned(const shiftnd_problem *p, const void *grad_out, cons
     if (can_sweep && (g_policy == 3 || (g_policy == 0 && !can_plane))) {
         if (sweep_backward_workspace(g, p->dtype) > workspace_bytes) return SHIFTND_ERR_WORKSPACE_TOO_SMALL;
         g_last_path = SHIFTND_PATH_SWEEP;
-        return finish(sweep_backward(g, p->dtype, grad_out, x, weights, grad_x, grad_w, workspace, st));
+        return finish(sweep_backward(g, p->dtype, grad_out, x, weights, wkind, grad_x, grad_w, workspace, st));
     }
     // ragged rows of 4- / 8-byte elements on planes with rows of at least 8 chunks: the row-relative crop_backward (shiftnd_span.hip, XRAG)
     if (g_policy == 0 && g_flat != 2 && ragged_rows(g, p->dtype) && span_backward_eligible(g, p->dtype, grad_out, x, grad_x)) {
         if (span_backward_workspace(g, p->dtype) > workspace_bytes) return SHIFTND_ERR_WORKSPACE_TOO_SMALL;
         g_last_path = SHIFTND_PATH_PLANE;
-        return finish(span_backward(g, p->dtype, grad_out, x, weights, grad_x, grad_w, workspace, st));
+        return finish(span_backward(g, p->dtype, grad_out, x, weights, wkind, grad_x, grad_w, workspace, st));
     }
     // ragged input rows -- and windows crop_backward does not take: the flat chunk stream.  (Ragged rows of 4- / 8-byte elements on
     // planes large enough for the row-relative crop_backward: that one, through plane_backward below.)
@@ -491,44 +523,44 @@ static int backward_planned(const shiftnd_problem *p, const void *grad_out, cons
         flat_backward_eligible(g, p->dtype, grad_out, x, grad_x)) {
         if (flat_backward_workspace(g) > workspace_bytes) return SHIFTND_ERR_WORKSPACE_TOO_SMALL;
         g_last_path = SHIFTND_PATH_PLANE;
-        return finish(flat_backward(g, p->dtype, grad_out, x, weights, grad_x, grad_w, workspace, st));
+        return finish(flat_backward(g, p->dtype, grad_out, x, weights, wkind, grad_x, grad_w, workspace, st));
     }
     if (can_plane && g_policy != 1 && g_policy != 4) {
         if (plane_backward_workspace(g, p->dtype) > workspace_bytes) return SHIFTND_ERR_WORKSPACE_TOO_SMALL;
         g_last_path = SHIFTND_PATH_PLANE;
-        return finish(plane_backward(g, p->dtype, grad_out, x, weights, grad_x, grad_w, workspace, st));
+        return finish(plane_backward(g, p->dtype, grad_out, x, weights, wkind, grad_x, grad_w, workspace, st));
     }
     if (g_policy == 0 && small_backward_eligible(g, p->dtype)) {  // rows not whole 16-byte pieces, small planes
         if (small_backward_workspace(g, p->dtype) > workspace_bytes) return SHIFTND_ERR_WORKSPACE_TOO_SMALL;
         g_last_path = SHIFTND_PATH_PLANE;
-        return finish(small_backward(g, p->dtype, grad_out, x, weights, grad_x, grad_w, workspace, st));
+        return finish(small_backward(g, p->dtype, grad_out, x, weights, wkind, grad_x, grad_w, workspace, st));
     }
     // 3-D volumes with ragged rows beyond the small-plane kernels (16 x 28 x 28 bf16, 8 x 56 x 62 fp32 ...): the direct-load plane
     // kernels with 4- / 8-byte chunks instead of the one-thread-per-element fallback
     if (g_policy == 0 && plane_ragged_backward_eligible(g, p->dtype, grad_out, x, grad_x)) {
         if (plane_ragged_backward_workspace(g, p->dtype) > workspace_bytes) return SHIFTND_ERR_WORKSPACE_TOO_SMALL;
         g_last_path = SHIFTND_PATH_PLANE;
-        return finish(plane_ragged_backward(g, p->dtype, grad_out, x, weights, grad_x, grad_w, workspace, st));
+        return finish(plane_ragged_backward(g, p->dtype, grad_out, x, weights, wkind, grad_x, grad_w, workspace, st));
     }
     if ((g_policy == 0 || g_policy == 4) && cl_tiled_backward_eligible(g, p->dtype, grad_out, x, grad_x)) {  // all channels-last: LDS-tiled
         if (cl_tiled_backward_workspace(g) > workspace_bytes) return SHIFTND_ERR_WORKSPACE_TOO_SMALL;
         g_last_path = SHIFTND_PATH_CL;
-        return finish(cl_tiled_backward(g, p->dtype, grad_out, x, weights, grad_x, grad_w, workspace, st));
+        return finish(cl_tiled_backward(g, p->dtype, grad_out, x, weights, wkind, grad_x, grad_w, workspace, st));
     }
     if ((g_policy == 0 || g_policy == 4) && g_cl3 != 1 && cl_tiled3_backward_eligible(g, p->dtype, grad_out, x, grad_x)) {  // NDHWC: LDS-tiled, one plane per workgroup
         if (cl_tiled3_backward_workspace(g) > workspace_bytes) return SHIFTND_ERR_WORKSPACE_TOO_SMALL;
         g_last_path = SHIFTND_PATH_CL;
-        return finish(cl_tiled3_backward(g, p->dtype, grad_out, x, weights, grad_x, grad_w, workspace, st));
+        return finish(cl_tiled3_backward(g, p->dtype, grad_out, x, weights, wkind, grad_x, grad_w, workspace, st));
     }
     if (g_policy == 4 && !cl_backward_eligible(g, p->dtype)) return SHIFTND_ERR_INVALID_ARGUMENT;
     if ((g_policy == 0 && cl_backward_preferred(g, p->dtype)) || g_policy == 4) {
         if (cl_backward_workspace(g) > workspace_bytes) return SHIFTND_ERR_WORKSPACE_TOO_SMALL;
         g_last_path = SHIFTND_PATH_CL;
-        return finish(cl_backward(g, p->dtype, grad_out, x, weights, grad_x, grad_w, workspace, st));
+        return finish(cl_backward(g, p->dtype, grad_out, x, weights, wkind, grad_x, grad_w, workspace, st));
     }
     if (strided_backward_workspace(g) > workspace_bytes) return SHIFTND_ERR_WORKSPACE_TOO_SMALL;
     g_last_path = SHIFTND_PATH_STRIDED;
-    return finish(strided_backward(g, p->dtype, grad_out, x, weights, grad_x, grad_w, workspace, st));
+    return finish(strided_backward(g, p->dtype, grad_out, x, weights, wkind, grad_x, grad_w, workspace, st));
 }
 
 // ---- layout change ---------------------------------------------------------------------------------------------
@@ -541,6 +573,7 @@ int shiftnd_transpose(const void *src, void *dst, int64_t batch, int64_t rows, i
 }
 
 // ---- fused shift + average pool ----------------------------------------------------------------------------
+// (p: the problem with the tensors' plain dtype -- split_dtype() has run)
 static int pooled_geometry(const shiftnd_problem *p, const int32_t *pool, Geometry &g, bool quantized_too = false) {
     if (!p || !pool) return SHIFTND_ERR_INVALID_ARGUMENT;
     if (!is_float_dtype(p->dtype) && !(quantized_too && is_quant_dtype(p->dtype))) return SHIFTND_ERR_UNSUPPORTED_DTYPE;
@@ -571,6 +604,10 @@ static int pooled_geometry(const shiftnd_problem *p, const int32_t *pool, Geomet
 size_t shiftnd_backward_pooled_workspace_bytes(const shiftnd_problem *p, const int32_t *pool) {
     // the pooled backward plans its launch with the pool in the geometry (more, shorter workgroups than the plain
     // backward of the same tensor can need more partial-sum groups)
+    shiftnd_problem q;
+    int wkind;
+    if (!p || split_dtype(p, q, wkind) != SHIFTND_OK) return 0;
+    p = &q;   // (as shiftnd_backward_workspace_bytes: the same bytes with and without SHIFTND_WEIGHTS_F32)
     Geometry g;
     if (pooled_geometry(p, pool, g) != SHIFTND_OK) return 0;
     if (g.N == 0 || g.C == 0 || g.S[0] * g.S[1] * g.S[2] == 0) return sizeof(double);
@@ -583,6 +620,11 @@ size_t shiftnd_backward_pooled_workspace_bytes(const shiftnd_problem *p, const i
 }
 
 int shiftnd_pooled_sizes(const shiftnd_problem *p, const int32_t *pool, int64_t pooled_spatial[3]) {
+    if (!p) return SHIFTND_ERR_INVALID_ARGUMENT;
+    shiftnd_problem q;
+    int wkind;
+    if (split_dtype(p, q, wkind) != SHIFTND_OK) return SHIFTND_ERR_UNSUPPORTED_DTYPE;
+    p = &q;
     Geometry g;
     const int rc = pooled_geometry(p, pool, g, true);  // (the sizes do not depend on the element type)
     if (rc != SHIFTND_OK) return rc;
@@ -594,6 +636,11 @@ int shiftnd_pooled_sizes(const shiftnd_problem *p, const int32_t *pool, int64_t 
 
 int shiftnd_forward_pooled(const shiftnd_problem *p, const int32_t *pool, const void *x, const void *weights, void *out,
                            void *stream) {
+    if (!p) return SHIFTND_ERR_INVALID_ARGUMENT;
+    shiftnd_problem q;
+    int wkind;
+    if (split_dtype(p, q, wkind) != SHIFTND_OK) return SHIFTND_ERR_UNSUPPORTED_DTYPE;
+    p = &q;
     Geometry g;
     const int rc = pooled_geometry(p, pool, g);
     if (rc != SHIFTND_OK) return rc;
@@ -605,26 +652,26 @@ int shiftnd_forward_pooled(const shiftnd_problem *p, const int32_t *pool, const 
     // 3-D interpolating: the walk through the planes with the pool as its epilogue
     if (g_policy == 0 && walk_forward_pooled_eligible(g, p->dtype, x, out)) {
         g_last_path = SHIFTND_PATH_PLANE;
-        return finish(walk_forward(g, p->dtype, x, weights, p->dtype, out, static_cast<hipStream_t>(stream)));
+        return finish(walk_forward(g, p->dtype, x, weights, wkind, out, static_cast<hipStream_t>(stream)));
     }
     // 2-D sparse shift, 2 x 2 windows, fp32 / fp64: the linear sweep of one-step workgroups with the pool as its epilogue
     if (g_policy == 0 && step_forward_pooled_eligible(g, p->dtype, x, out)) {
         g_last_path = SHIFTND_PATH_SWEEP;
-        return finish(step_forward_pooled(g, p->dtype, x, weights, p->dtype, out, static_cast<hipStream_t>(stream)));
+        return finish(step_forward_pooled(g, p->dtype, x, weights, wkind, out, static_cast<hipStream_t>(stream)));
     }
     // 3-D volumes, 2 x 2 x 2 windows, cropped or not (what the walk above does not take): pooled rows through LDS (round 6)
     if (g_policy == 0 && span_forward_pooled3_eligible(g, p->dtype, x, out)) {
         g_last_path = SHIFTND_PATH_PLANE;
-        return finish(span_forward_pooled3(g, p->dtype, x, weights, p->dtype, out, static_cast<hipStream_t>(stream)));
+        return finish(span_forward_pooled3(g, p->dtype, x, weights, wkind, out, static_cast<hipStream_t>(stream)));
     }
     // 1-D rows of at least 128 chunks, windows of 2: row_forward with the pool as its epilogue (round 6)
     if (g_policy == 0 && span_forward_pooled_eligible(g, p->dtype, x, out)) {
         g_last_path = SHIFTND_PATH_PLANE;
-        return finish(span_forward_pooled(g, p->dtype, x, weights, p->dtype, out, static_cast<hipStream_t>(stream)));
+        return finish(span_forward_pooled(g, p->dtype, x, weights, wkind, out, static_cast<hipStream_t>(stream)));
     }
     if (!plane_pool_forward_eligible(g, p->dtype)) return SHIFTND_ERR_NOT_FUSED;
     g_last_path = SHIFTND_PATH_PLANE;
-    return finish(plane_pool_forward(g, p->dtype, x, weights, out, static_cast<hipStream_t>(stream)));
+    return finish(plane_pool_forward(g, p->dtype, x, weights, wkind, out, static_cast<hipStream_t>(stream)));
 }
 
 int shiftnd_forward_quantized_pooled(const shiftnd_problem *p, const int32_t *pool, const void *x, const void *wq, int32_t wq_dtype,
@@ -665,16 +712,21 @@ int shiftnd_backward_pooled(const shiftnd_problem *p, const int32_t *pool, const
 static int backward_pooled_planned(const shiftnd_problem *p, const int32_t *pool, const void *grad_pooled, const void *x,
                                    const void *weights, void *grad_x, void *grad_w, void *workspace, size_t workspace_bytes,
                                    void *stream) {
+    if (!p) return SHIFTND_ERR_INVALID_ARGUMENT;
+    shiftnd_problem q;
+    int wkind;   // element type of `weights` and `grad_w`
+    if (split_dtype(p, q, wkind) != SHIFTND_OK) return SHIFTND_ERR_UNSUPPORTED_DTYPE;
+    p = &q;
     Geometry g;
     const int rc = pooled_geometry(p, pool, g);
     if (rc != SHIFTND_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const bool input_only = !x && !grad_w;
-    if (input_only && p->active) return SHIFTND_ERR_INVALID_ARGUMENT;   // (also for an empty problem: the form does not exist)
+    if (input_only && (p->active || wkind != p->dtype)) return SHIFTND_ERR_INVALID_ARGUMENT;   // (also for an empty problem: the form does not exist)
     if (g.N == 0 || g.C == 0 || g.S[0] * g.S[1] * g.S[2] == 0) {
         g_last_path = SHIFTND_PATH_EMPTY;
         if (g.C > 0 && grad_w)
-            if (hipMemsetAsync(grad_w, 0, static_cast<size_t>(g.C) * g.nd * dtype_size(p->dtype), st) != hipSuccess)
+            if (hipMemsetAsync(grad_w, 0, static_cast<size_t>(g.C) * g.nd * dtype_size(wkind), st) != hipSuccess)
                 return SHIFTND_ERR_LAUNCH_FAILED;
         return SHIFTND_OK;
     }
@@ -694,13 +746,13 @@ static int backward_pooled_planned(const shiftnd_problem *p, const int32_t *pool
     if (g_policy == 0 && walk_backward_pooled_eligible(g, p->dtype, grad_pooled, x, grad_x)) {
         if (plane_backward_workspace(g, p->dtype) > workspace_bytes) return SHIFTND_ERR_WORKSPACE_TOO_SMALL;
         g_last_path = SHIFTND_PATH_PLANE;
-        return finish(step_backward(g, p->dtype, grad_pooled, x, weights, grad_x, grad_w, workspace, st));
+        return finish(step_backward(g, p->dtype, grad_pooled, x, weights, wkind, grad_x, grad_w, workspace, st));
     }
     // cropped 3-D volumes, 2 x 2 x 2 windows: crop_backward3 with the pooled gradient expanded on its way into LDS (round 6)
     if (g_policy == 0 && g.nd == 3 && span_backward_pooled_eligible(g, p->dtype, grad_pooled, x, grad_x)) {
         if (span_backward_pooled_workspace(g, p->dtype) > workspace_bytes) return SHIFTND_ERR_WORKSPACE_TOO_SMALL;
         g_last_path = SHIFTND_PATH_PLANE;
-        return finish(span_backward(g, p->dtype, grad_pooled, x, weights, grad_x, grad_w, workspace, st));
+        return finish(span_backward(g, p->dtype, grad_pooled, x, weights, wkind, grad_x, grad_w, workspace, st));
     }
     if (!plane_pool_backward_eligible(g, p->dtype, grad_x)) return SHIFTND_ERR_NOT_FUSED;
     // what the walk does not take of the 3-D interpolating backward: through the band-walk kernels 16 gradient corner rows per
@@ -722,7 +774,7 @@ static int backward_pooled_planned(const shiftnd_problem *p, const int32_t *pool
     }
     if (plane_backward_workspace(g, p->dtype) > workspace_bytes) return SHIFTND_ERR_WORKSPACE_TOO_SMALL;
     g_last_path = SHIFTND_PATH_PLANE;
-    return finish(plane_pool_backward(g, p->dtype, grad_pooled, x, weights, grad_x, grad_w, workspace, st));
+    return finish(plane_pool_backward(g, p->dtype, grad_pooled, x, weights, wkind, grad_x, grad_w, workspace, st));
 }
 
 }  // extern "C"

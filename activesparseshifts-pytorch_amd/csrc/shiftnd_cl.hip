@@ -419,11 +419,11 @@ static int launch_cl_backward(const ClParams &p, const Geometry &g, const ClPlan
     default: SHIFTND_CL_BWD(3) break;
     }
 #undef SHIFTND_CL_BWD
-    reduce_weight_grads_of<T>(p.partials, pl.pgroups, p.C, p.nd, gw, st);
+    launch_reduce_weight_grads(p.wkind, p.partials, pl.pgroups, p.C, p.nd, gw, st);
     return SHIFTND_OK;
 }
 
-int cl_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, void *gx, void *gw,
+int cl_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw,
                 void *workspace, hipStream_t st) {
     const ClPlan pl = cl_plan(g, g.S, kBackwardWgs);
     ClParams p{};
@@ -431,7 +431,7 @@ int cl_backward(const Geometry &g, int dtype, const void *go, const void *x, con
     p.go = go;
     p.w = w;
     p.out = gx;
-    p.wkind = dtype;
+    p.wkind = wkind;
     p.partials = static_cast<double *>(workspace);
     fill_cl(p, g, pl, g.S);
     note_kernel("cl_backward");

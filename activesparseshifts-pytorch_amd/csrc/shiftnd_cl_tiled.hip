@@ -1450,11 +1450,11 @@ void launch_cl_tiled_backward(const ClTiledBwdParams &p, const ClTiledBwdPlan &p
         if (active) hipLaunchKernelGGL((cl_tiled_backward<T, true, false>), grid, block, 0, st, p);
         else hipLaunchKernelGGL((cl_tiled_backward<T, false, false>), grid, block, 0, st, p);
     }
-    reduce_weight_grads_of<T>(p.partials, static_cast<int>(pl.groups), p.C, 2, gw, st);
+    launch_reduce_weight_grads(p.wkind, p.partials, static_cast<int>(pl.groups), p.C, 2, gw, st);
 }
 }  // namespace
 
-int cl_tiled_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, void *gx, void *gw,
+int cl_tiled_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw,
                       void *workspace, hipStream_t st) {
     // (the wide strip, TW = 32 -- built and measured in round 6, same box, fp32 NHWC tensors, bit-identical grad_x over 360 shape /
     //  padding / shift / window combinations: N16 C256 224x224 sparse 0.5115 -> 0.5216 ms, interpolating 0.5628 -> 0.5977; N32 C256
@@ -1467,7 +1467,7 @@ int cl_tiled_backward(const Geometry &g, int dtype, const void *go, const void *
     p.go = static_cast<const char *>(go);
     p.gx = static_cast<char *>(gx);
     p.w = w;
-    p.wkind = dtype;
+    p.wkind = wkind;
     p.partials = static_cast<double *>(workspace);
     p.N = static_cast<int>(g.N);
     p.C = static_cast<int>(g.C);

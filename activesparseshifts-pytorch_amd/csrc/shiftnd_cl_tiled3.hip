@@ -654,11 +654,11 @@ void launch3(const ClTiled3Params &p, const Plan3 &pl, bool active, void *gw, hi
         if (active) hipLaunchKernelGGL((cl_tiled_backward_3d<T, true, false>), grid, block, 0, st, p);
         else hipLaunchKernelGGL((cl_tiled_backward_3d<T, false, false>), grid, block, 0, st, p);
     }
-    reduce_weight_grads_of<T>(p.partials, static_cast<int>(pl.groups), p.C, 3, gw, st);
+    launch_reduce_weight_grads(p.wkind, p.partials, static_cast<int>(pl.groups), p.C, 3, gw, st);
 }
 }  // namespace
 
-int cl_tiled3_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, void *gx, void *gw, void *workspace,
+int cl_tiled3_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw, void *workspace,
                        hipStream_t st) {
     const Plan3 pl = plan3(g);
     ClTiled3Params p{};
@@ -666,7 +666,7 @@ int cl_tiled3_backward(const Geometry &g, int dtype, const void *go, const void 
     p.go = static_cast<const char *>(go);
     p.gx = static_cast<char *>(gx);
     p.w = w;
-    p.wkind = dtype;
+    p.wkind = wkind;
     p.partials = static_cast<double *>(workspace);
     p.N = static_cast<int>(g.N);
     p.C = static_cast<int>(g.C);

@@ -345,12 +345,9 @@ __device__ __forceinline__ double block_sum(double v, double *scratch) {
 
 // Final stage of the weight-gradient reduction: grad_w[c, s] = sum over partial groups.
 // partials layout: [group][C][3] doubles.  One copy of the kernels in the library (shiftnd_strided.hip defines them and this
-// launcher); T::kDtype selects the output type.
-void launch_reduce_weight_grads(int dtype, const double *partials, int groups, int C, int nd, void *grad_w, hipStream_t st);
-template <typename T>
-inline void reduce_weight_grads_of(const double *partials, int groups, int C, int nd, void *grad_w, hipStream_t st) {
-    launch_reduce_weight_grads(T::kDtype, partials, groups, C, nd, grad_w, st);
-}
+// launcher).  `wkind` is the element type of grad_w, which is the weights' (the launch parameters' wkind): the tensors' type, or
+// SHIFTND_F32 for the fp32 weights of a 16-bit tensor (SHIFTND_WEIGHTS_F32) -- the kernels use their type for this store only.
+void launch_reduce_weight_grads(int wkind, const double *partials, int groups, int C, int nd, void *grad_w, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------------
 // buffer_store_dwordx4 with the row / plane offset in an SGPR (soffset).  gfx950 reads the 128 bits of store data over more than

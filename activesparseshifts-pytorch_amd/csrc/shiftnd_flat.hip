@@ -701,7 +701,7 @@ __global__ __launch_bounds__(kThreads) void flat_backward(const FlatParams p, in
 
 // grad_w[c][:] = blend(sum over the records of channel c's planes, in a fixed order): one wave per channel, lanes over the batch
 template <typename T>
-__global__ __launch_bounds__(64) void flat_reduce(const FlatParams p, int N, int active, typename T::S *__restrict__ grad_w) {
+__global__ __launch_bounds__(64) void flat_reduce(const FlatParams p, int N, int active, void *__restrict__ grad_w) {
     using S = typename T::S;
     constexpr int E = 16 / sizeof(S);
     const int c = blockIdx.x;
@@ -732,9 +732,12 @@ __global__ __launch_bounds__(64) void flat_reduce(const FlatParams p, int N, int
             const double s[2] = {a, b}, dwd[2] = {static_cast<double>(f1), static_cast<double>(f2)};   // (exactly as the compute type holds them)
             blend_diffs<2>(s, dwd, out);
         }
+        // in the weights' type: T's, or fp32 for the fp32 weights of a 16-bit tensor (the records above are laid out by T's element size, so
+        // this kernel cannot run as f32_t's instantiation the way reduce_weight_grads and step_reduce do)
         for (int k = 0; k < p.nd; ++k) {
-            if constexpr (sizeof(S) == 8) grad_w[c * p.nd + k] = out[k];
-            else grad_w[c * p.nd + k] = narrow<T>(static_cast<float>(out[k]));
+            if constexpr (sizeof(S) == 8) static_cast<double *>(grad_w)[c * p.nd + k] = out[k];
+            else if (sizeof(S) == 2 && p.wkind == SHIFTND_F32) static_cast<float *>(grad_w)[c * p.nd + k] = static_cast<float>(out[k]);
+            else static_cast<S *>(grad_w)[c * p.nd + k] = narrow<T>(static_cast<float>(out[k]));
         }
     }
 }
@@ -833,7 +836,7 @@ void launch_flat_backward(const FlatParams &p, const FlatPlan &pl, int N, void *
             hipLaunchKernelGGL((flat_backward<T, ACTIVE, decltype(pad)::value, decltype(small)::value>), grid, block, pl.lds, st, p, pl.gcov_off);
         });
     });
-    hipLaunchKernelGGL((flat_reduce<T>), dim3(p.C), dim3(64), 0, st, p, N, ACTIVE ? 1 : 0, static_cast<typename T::S *>(gw));
+    hipLaunchKernelGGL((flat_reduce<T>), dim3(p.C), dim3(64), 0, st, p, N, ACTIVE ? 1 : 0, gw);
 }
 
 void fill_params(FlatParams &p, const Geometry &g, int es, bool backward, const FlatPlan &pl) {
@@ -905,7 +908,7 @@ size_t flat_backward_workspace(const Geometry &g) {
     return align_up_256((steps + static_cast<uint64_t>(g.N) * g.C + 1) * 2 * sizeof(double)) + align_up_256(static_cast<size_t>(g.C) * sizeof(FlatDesc));
 }
 
-int flat_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, void *gx, void *gw, void *workspace,
+int flat_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw, void *workspace,
                   hipStream_t st) {
     const int es = dtype_size(dtype);
     const FlatPlan pl = flat_plan(g, es, true);
@@ -914,7 +917,7 @@ int flat_backward(const Geometry &g, int dtype, const void *go, const void *x, c
     p.go = go;
     p.out = gx;
     p.w = w;
-    p.wkind = dtype;
+    p.wkind = wkind;
     fill_params(p, g, es, true, pl);
     p.partials = static_cast<double *>(workspace);
     p.desc = reinterpret_cast<FlatDesc *>(static_cast<char *>(workspace) + align_up_256((pl.steps + static_cast<uint64_t>(g.N) * g.C + 1) * 2 * sizeof(double)));

@@ -38,10 +38,11 @@ const char *last_kernel();
 
 // ---- strided fallback (shiftnd_strided.hip) ------------------------------------------------------
 // wkind: dtype of the weights array (float dtypes -> rint / floor+frac; I8/U8/I32 -> repr - wzp).
+// For float tensors it is `dtype`, or SHIFTND_F32 with fp16 / bf16 tensors (SHIFTND_WEIGHTS_F32); a backward stores grad_w in it too.
 int strided_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, int64_t wzp,
                     uint64_t fill_bits, void *out, hipStream_t st);
 size_t strided_backward_workspace(const Geometry &g);
-int strided_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, void *gx, void *gw,
+int strided_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw,
                      void *workspace, hipStream_t st);
 
 // ---- per-plane kernels (shiftnd_plane.hip) -------------------------------------------------------
@@ -57,30 +58,30 @@ size_t plane_backward_workspace(const Geometry &g, int dtype);
 // 3-D volumes with rows that are not whole 16-byte pieces, beyond the small-plane kernels: the direct-load plane kernels with
 // 4- / 8-byte chunks (interpolating forward, both backwards)
 bool plane_ragged_forward_eligible(const Geometry &g, int dtype, const void *x, const void *out);
-int plane_ragged_forward(const Geometry &g, int dtype, const void *x, const void *w, void *out, hipStream_t st);
+int plane_ragged_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, void *out, hipStream_t st);
 bool plane_ragged_backward_eligible(const Geometry &g, int dtype, const void *go, const void *x, const void *gx);
 size_t plane_ragged_backward_workspace(const Geometry &g, int dtype);
-int plane_ragged_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, void *gx, void *gw,
+int plane_ragged_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw,
                           void *workspace, hipStream_t st);
-int plane_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, void *gx, void *gw,
+int plane_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw,
                    void *workspace, hipStream_t st);
 
 // fused shift + average pool (kernel = stride = g.K, ceil mode), contiguous tensors only; the backward uses the
 // plane_backward_workspace layout
 bool plane_pool_forward_eligible(const Geometry &g, int dtype);
-int plane_pool_forward(const Geometry &g, int dtype, const void *x, const void *w, void *out, hipStream_t st);
+int plane_pool_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, void *out, hipStream_t st);
 bool plane_pool_backward_eligible(const Geometry &g, int dtype, const void *gx);
-int plane_pool_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, void *gx, void *gw,
+int plane_pool_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw,
                         void *workspace, hipStream_t st);
 
 // ---- sliding-window kernels (shiftnd_slide.hip): backward pass and interpolating forward of contiguous 2-D / 3-D
 // problems without crop; part of the per-channel ("plane") family: plane_forward / plane_backward route to them
 bool slide_backward_eligible(const Geometry &g, int dtype, const void *go, const void *x, const void *gx);
 size_t slide_backward_workspace(const Geometry &g, int dtype);
-int slide_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, void *gx, void *gw,
+int slide_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw,
                    void *workspace, hipStream_t st);
 bool slide_forward_eligible(const Geometry &g, int dtype, const void *x, const void *out);
-int slide_forward(const Geometry &g, int dtype, const void *x, const void *w, void *out, hipStream_t st);
+int slide_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, void *out, hipStream_t st);
 void slide_set_tuning(int knob, int value);
 
 // ---- one-step workgroups (shiftnd_step.hip): the backward pass of contiguous 2-D problems as a linear sweep of short
@@ -88,7 +89,7 @@ void slide_set_tuning(int knob, int value);
 bool step_backward_eligible(const Geometry &g, int dtype, const void *go, const void *x, const void *gx);
 bool step_backward_pooled_eligible(const Geometry &g, int dtype, const void *go, const void *x, const void *gx);
 size_t step_backward_workspace(const Geometry &g, int dtype);
-int step_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, void *gx, void *gw,
+int step_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw,
                   void *workspace, hipStream_t st);
 // ... and the sparse-shift / quantized forward of 4- / 8-byte elements in the same shape (part of the sweep family)
 bool step_forward_eligible(const Geometry &g, int dtype, const void *x, const void *out);
@@ -109,14 +110,14 @@ bool span_forward_pooled_eligible(const Geometry &g, int dtype, const void *x, c
 int span_forward_pooled(const Geometry &g, int dtype, const void *x, const void *w, int wkind, void *out, hipStream_t st);
 bool span_backward_pooled_eligible(const Geometry &g, int dtype, const void *go, const void *x, const void *gx);
 size_t span_backward_pooled_workspace(const Geometry &g, int dtype);
-int span_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, void *gx, void *gw, void *workspace,
+int span_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw, void *workspace,
                   hipStream_t st);
 // ---- the 3-D backward of 16-bit tensors as a walk through the planes (shiftnd_walk.hip, round 4; plane_backward routes to it)
 bool walk16_forward_eligible(const Geometry &g, int dtype, const void *x, const void *out);
 int walk16_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, void *out, hipStream_t st);
 bool walk16_backward_eligible(const Geometry &g, int dtype, const void *go, const void *x, const void *gx);
 size_t walk16_backward_workspace(const Geometry &g, int dtype);
-int walk16_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, void *gx, void *gw, void *workspace,
+int walk16_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw, void *workspace,
                     hipStream_t st);
 
 // ---- 1-byte elements on small planes (shiftnd_bytes.hip): whole planes through LDS, 16-byte output pieces that cross
@@ -138,7 +139,7 @@ int cl_forward(const Geometry &g, int dtype, const void *x, const void *w, int w
                void *out, hipStream_t st);
 bool cl_backward_eligible(const Geometry &g, int dtype);
 size_t cl_backward_workspace(const Geometry &g);
-int cl_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, void *gx, void *gw,
+int cl_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw,
                 void *workspace, hipStream_t st);
 
 // ---- LDS-tiled gather forward for dense channels-last inputs of 4-byte elements (shiftnd_cl_tiled.hip); the output is
@@ -150,13 +151,13 @@ void cl_tiled_set_tuning(int knob, int value);
 // ... and the backward of 2-D fp32 problems whose three tensors are all dense channels-last
 bool cl_tiled_backward_eligible(const Geometry &g, int dtype, const void *go, const void *x, const void *gx);
 size_t cl_tiled_backward_workspace(const Geometry &g);
-int cl_tiled_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, void *gx, void *gw,
+int cl_tiled_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw,
                       void *workspace, hipStream_t st);
 
 // ... and of 3-D problems whose saved input and grad_x are dense NDHWC, the gradient NDHWC or NCDHW-contiguous (shiftnd_cl_tiled3.hip, round 5)
 bool cl_tiled3_backward_eligible(const Geometry &g, int dtype, const void *go, const void *x, const void *gx);
 size_t cl_tiled3_backward_workspace(const Geometry &g);
-int cl_tiled3_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, void *gx, void *gw,
+int cl_tiled3_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw,
                        void *workspace, hipStream_t st);
 
 // ---- rows that are not whole 16-byte pieces as one-step workgroups over the tensor's flat chunk stream (shiftnd_flat.hip, round 5):
@@ -165,17 +166,17 @@ bool flat_forward_eligible(const Geometry &g, int dtype, const void *x, const vo
 int flat_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, void *out, hipStream_t st);
 bool flat_backward_eligible(const Geometry &g, int dtype, const void *go, const void *x, const void *gx);
 size_t flat_backward_workspace(const Geometry &g);
-int flat_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, void *gx, void *gw, void *workspace,
+int flat_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw, void *workspace,
                   hipStream_t st);
 void flat_set_tuning(int value);   // knob 27: 0 automatic (ragged rows), 1 never, 2 whenever eligible
 
 // ---- whole small planes through LDS (shiftnd_small.hip): interpolating forward and backward of contiguous problems whose
 // rows are not whole 16-byte pieces (planes of at most 16 KiB)
 bool small_forward_eligible(const Geometry &g, int dtype);
-int small_forward(const Geometry &g, int dtype, const void *x, const void *w, void *out, hipStream_t st);
+int small_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, void *out, hipStream_t st);
 bool small_backward_eligible(const Geometry &g, int dtype);
 size_t small_backward_workspace(const Geometry &g, int dtype);
-int small_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, void *gx, void *gw,
+int small_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw,
                    void *workspace, hipStream_t st);
 void small_set_tuning(int knob, int value);
 // ... and the sparse-shift / quantized forward of 1-D / 2-D problems with such rows (any element size)
@@ -221,7 +222,7 @@ int sweep_forward(const Geometry &g, int dtype, const void *x, const void *w, in
                   void *out, hipStream_t st);
 bool sweep_backward_eligible(const Geometry &g, int dtype, const void *go, const void *x, const void *gx);
 size_t sweep_backward_workspace(const Geometry &g, int dtype);
-int sweep_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, void *gx, void *gw,
+int sweep_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw,
                    void *workspace, hipStream_t st);
 void sweep_set_tuning(int knob, int value);
 int sweep_debug_map(int64_t p, int64_t shift, int64_t len, int pad);

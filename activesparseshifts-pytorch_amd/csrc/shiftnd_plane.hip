@@ -1548,7 +1548,7 @@ int launch_backward(const PlaneParams &p, const Plan &pl, bool active, void *gw,
         else launch_backward_pool<T, false>(p, pl, st);
     } else if (active) launch_backward_a<T, true>(p, pl, st);
     else launch_backward_a<T, false>(p, pl, st);
-    reduce_weight_grads_of<T>(p.partials, pl.groups * pl.bands, p.C, p.nd, gw, st);
+    launch_reduce_weight_grads(p.wkind, p.partials, pl.groups * pl.bands, p.C, p.nd, gw, st);
     return SHIFTND_OK;
 }
 
@@ -1635,7 +1635,7 @@ int plane_forward(const Geometry &g, int dtype, const void *x, const void *w, in
     p.wzp = wzp;
     p.fill = fill_bits;
     if (interpolating) {
-        if (slide_forward_eligible(g, dtype, x, out)) return slide_forward(g, dtype, x, w, out, st);
+        if (slide_forward_eligible(g, dtype, x, out)) return slide_forward(g, dtype, x, w, wkind, out, st);
         const Plan pl = make_plan(g, g.O[0] * g.O[1], g.O[2], es, 16, entries);
         fill_params(p, g, pl, g.O[1]);
         switch (dtype) {
@@ -1704,14 +1704,14 @@ bool plane_pool_forward_eligible(const Geometry &g, int dtype) {
     return g.S[0] + g.S[1] + g.S[2] + 3 <= kMaxMapEntries;
 }
 
-int plane_pool_forward(const Geometry &g, int dtype, const void *x, const void *w, void *out, hipStream_t st) {
+int plane_pool_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, void *out, hipStream_t st) {
     const int es = dtype_size(dtype);
     const int entries = static_cast<int>(g.S[0] + g.S[1] + g.S[2] + 3);
     PlaneParams p{};
     p.x = x;
     p.out = out;
     p.w = w;
-    p.wkind = dtype;
+    p.wkind = wkind;
     const Plan pl = make_plan(g, g.P[0] * g.P[1], g.P[2], es, es, entries);
     fill_params(p, g, pl, g.P[1]);
     switch (dtype) {
@@ -1731,18 +1731,18 @@ bool plane_pool_backward_eligible(const Geometry &g, int dtype, const void *gx) 
 
 extern thread_local int g_step_tune[5];   // knobs 32..35 / 38 (shiftnd_step.hip)
 
-int plane_pool_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, void *gx, void *gw,
+int plane_pool_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw,
                         void *workspace, hipStream_t st) {
-    if (step_backward_pooled_eligible(g, dtype, go, x, gx)) return step_backward(g, dtype, go, x, w, gx, gw, workspace, st);
+    if (step_backward_pooled_eligible(g, dtype, go, x, gx)) return step_backward(g, dtype, go, x, w, wkind, gx, gw, workspace, st);
     // cropped windows and the interpolating shift: crop_backward<.., POOL> (round 6; knob 35 bit 6 keeps the band walk)
-    if (!(g_step_tune[3] & 64) && span_backward_pooled_eligible(g, dtype, go, x, gx)) return span_backward(g, dtype, go, x, w, gx, gw, workspace, st);
+    if (!(g_step_tune[3] & 64) && span_backward_pooled_eligible(g, dtype, go, x, gx)) return span_backward(g, dtype, go, x, w, wkind, gx, gw, workspace, st);
     const Plan pl = backward_plan(g, dtype_size(dtype));
     PlaneParams p{};
     p.x = x;
     p.go = go;
     p.out = gx;
     p.w = w;
-    p.wkind = dtype;
+    p.wkind = wkind;
     p.partials = static_cast<double *>(workspace);
     fill_params(p, g, pl, g.S[1]);
     switch (dtype) {
@@ -1753,19 +1753,19 @@ int plane_pool_backward(const Geometry &g, int dtype, const void *go, const void
     }
 }
 
-int plane_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, void *gx, void *gw,
+int plane_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw,
                    void *workspace, hipStream_t st) {
-    if (walk16_backward_eligible(g, dtype, go, x, gx)) return walk16_backward(g, dtype, go, x, w, gx, gw, workspace, st);
-    if (step_backward_eligible(g, dtype, go, x, gx)) return step_backward(g, dtype, go, x, w, gx, gw, workspace, st);
-    if (span_backward_eligible(g, dtype, go, x, gx)) return span_backward(g, dtype, go, x, w, gx, gw, workspace, st);
-    if (slide_backward_eligible(g, dtype, go, x, gx)) return slide_backward(g, dtype, go, x, w, gx, gw, workspace, st);
+    if (walk16_backward_eligible(g, dtype, go, x, gx)) return walk16_backward(g, dtype, go, x, w, wkind, gx, gw, workspace, st);
+    if (step_backward_eligible(g, dtype, go, x, gx)) return step_backward(g, dtype, go, x, w, wkind, gx, gw, workspace, st);
+    if (span_backward_eligible(g, dtype, go, x, gx)) return span_backward(g, dtype, go, x, w, wkind, gx, gw, workspace, st);
+    if (slide_backward_eligible(g, dtype, go, x, gx)) return slide_backward(g, dtype, go, x, w, wkind, gx, gw, workspace, st);
     const Plan pl = backward_plan(g, dtype_size(dtype));
     PlaneParams p{};
     p.x = x;
     p.go = go;
     p.out = gx;
     p.w = w;
-    p.wkind = dtype;
+    p.wkind = wkind;
     p.partials = static_cast<double *>(workspace);
     fill_params(p, g, pl, g.S[1]);
     switch (dtype) {
@@ -1801,14 +1801,14 @@ bool plane_ragged_forward_eligible(const Geometry &g, int dtype, const void *x, 
     return reinterpret_cast<uintptr_t>(out) % dtype_size(dtype) == 0 && reinterpret_cast<uintptr_t>(x) % dtype_size(dtype) == 0;
 }
 
-int plane_ragged_forward(const Geometry &g, int dtype, const void *x, const void *w, void *out, hipStream_t st) {
+int plane_ragged_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, void *out, hipStream_t st) {
     const int es = dtype_size(dtype);
     const int entries = static_cast<int>(g.S[0] + g.S[1] + g.S[2] + 3);
     PlaneParams p{};
     p.x = x;
     p.out = out;
     p.w = w;
-    p.wkind = dtype;
+    p.wkind = wkind;
     const int vb = ragged_vector_bytes(es, g.O[2], g.nd, x, out, out);
     const Plan pl = make_plan(g, g.O[0] * g.O[1], g.O[2], es, vb, entries);
     fill_params(p, g, pl, g.O[1]);
@@ -1852,7 +1852,7 @@ size_t plane_ragged_backward_workspace(const Geometry &g, int dtype) {
     return recs * static_cast<size_t>(g.C) * 3 * sizeof(double);
 }
 
-int plane_ragged_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, void *gx, void *gw,
+int plane_ragged_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw,
                           void *workspace, hipStream_t st) {
     const int es = dtype_size(dtype);
     const int vb = ragged_vector_bytes(es, g.S[2], g.nd, go, x, gx);
@@ -1862,7 +1862,7 @@ int plane_ragged_backward(const Geometry &g, int dtype, const void *go, const vo
     p.go = go;
     p.out = gx;
     p.w = w;
-    p.wkind = dtype;
+    p.wkind = wkind;
     p.partials = static_cast<double *>(workspace);
     fill_params(p, g, pl, g.S[1]);
     note_kernel("plane_backward_ragged");
@@ -1876,7 +1876,7 @@ int plane_ragged_backward(const Geometry &g, int dtype, const void *go, const vo
     else if (g.nd == 2) { SHIFTND_RAGGED_BWD_K(TT, 2, VB1) } \
     else if (vb == VB1) { SHIFTND_RAGGED_BWD_K(TT, 3, VB1) } \
     else { SHIFTND_RAGGED_BWD_K(TT, 3, VB3) } \
-    reduce_weight_grads_of<TT>(p.partials, pl.groups * pl.bands, p.C, p.nd, gw, st);
+    launch_reduce_weight_grads(p.wkind, p.partials, pl.groups * pl.bands, p.C, p.nd, gw, st);
     switch (dtype) {
     case SHIFTND_F32: SHIFTND_RAGGED_BWD(f32_t, 4, 4) break;
     case SHIFTND_F64: SHIFTND_RAGGED_BWD(f64_t, 8, 8) break;

@@ -816,7 +816,7 @@ size_t slide_backward_workspace(const Geometry &g, int dtype) {
     return static_cast<size_t>(pl.groups) * pl.inner * static_cast<size_t>(g.C) * 3 * sizeof(double);
 }
 
-int slide_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, void *gx, void *gw,
+int slide_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw,
                    void *workspace, hipStream_t st) {
     const SlidePlan pl = slide_plan(g, dtype_size(dtype), true, kNpBackward);
     if (!pl.ok) return SHIFTND_ERR_INVALID_ARGUMENT;
@@ -825,7 +825,7 @@ int slide_backward(const Geometry &g, int dtype, const void *go, const void *x, 
     p.go = go;
     p.out = gx;
     p.w = w;
-    p.wkind = dtype;
+    p.wkind = wkind;
     p.partials = static_cast<double *>(workspace);
     fill_slide(p, g, pl);
     note_kernel("slide_backward");
@@ -834,7 +834,7 @@ int slide_backward(const Geometry &g, int dtype, const void *go, const void *x, 
     { \
         if (g.active) launch_slide_backward<TT, true>(p, pl, st); \
         else launch_slide_backward<TT, false>(p, pl, st); \
-        reduce_weight_grads_of<TT>(p.partials, groups, p.C, p.nd, gw, st); \
+        launch_reduce_weight_grads(p.wkind, p.partials, groups, p.C, p.nd, gw, st); \
     }
     switch (dtype) {
     case SHIFTND_F32: SHIFTND_SLIDE_BWD(f32_t) break;
@@ -853,14 +853,14 @@ bool slide_forward_eligible(const Geometry &g, int dtype, const void *x, const v
     return slide_plan(g, dtype_size(dtype), false, kNpForward).ok;
 }
 
-int slide_forward(const Geometry &g, int dtype, const void *x, const void *w, void *out, hipStream_t st) {
+int slide_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, void *out, hipStream_t st) {
     const SlidePlan pl = slide_plan(g, dtype_size(dtype), false, kNpForward);
     if (!pl.ok) return SHIFTND_ERR_INVALID_ARGUMENT;
     SlideParams p{};
     p.x = x;
     p.out = out;
     p.w = w;
-    p.wkind = dtype;
+    p.wkind = wkind;
     fill_slide(p, g, pl);
     note_kernel("slide_forward");
     switch (dtype) {

@@ -596,7 +596,7 @@ bool small_forward_eligible(const Geometry &g, int dtype) {
     return small_plan(g, dtype_size(dtype), false).ok || band_plan(g, dtype_size(dtype), false).ok;
 }
 
-int small_forward(const Geometry &g, int dtype, const void *x, const void *w, void *out, hipStream_t st) {
+int small_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, void *out, hipStream_t st) {
     const SmallPlan pl = small_plan(g, dtype_size(dtype), false);
     if (!pl.ok) {   // the plane does not fit: row bands
         const BandPlan bp = band_plan(g, dtype_size(dtype), false);
@@ -605,7 +605,7 @@ int small_forward(const Geometry &g, int dtype, const void *x, const void *w, vo
         b.x = x;
         b.out = out;
         b.w = w;
-        b.wkind = dtype;
+        b.wkind = wkind;
         fill_band(b, g, bp);
         note_kernel("band_plane_forward");
         switch (dtype) {
@@ -620,7 +620,7 @@ int small_forward(const Geometry &g, int dtype, const void *x, const void *w, vo
     p.x = x;
     p.out = out;
     p.w = w;
-    p.wkind = dtype;
+    p.wkind = wkind;
     fill_small(p, g, pl);
     note_kernel("small_plane_forward");
     switch (dtype) {
@@ -649,16 +649,16 @@ size_t small_backward_workspace(const Geometry &g, int dtype) {
 template <typename T>
 static void band_backward_t(const BandParams &p, const BandPlan &pl, bool active, void *gw, hipStream_t st) {
     launch_band<T, true>(p, pl, active, st);
-    reduce_weight_grads_of<T>(p.partials, pl.groups, p.C, p.nd, gw, st);
+    launch_reduce_weight_grads(p.wkind, p.partials, pl.groups, p.C, p.nd, gw, st);
 }
 
 template <typename T>
 static void small_backward_t(const SmallParams &p, const SmallPlan &pl, bool active, void *gw, hipStream_t st) {
     launch_small<T, true>(p, pl, active, st);
-    reduce_weight_grads_of<T>(p.partials, pl.groups, p.C, p.nd, gw, st);
+    launch_reduce_weight_grads(p.wkind, p.partials, pl.groups, p.C, p.nd, gw, st);
 }
 
-int small_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, void *gx, void *gw,
+int small_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw,
                    void *workspace, hipStream_t st) {
     const SmallPlan pl = small_plan(g, dtype_size(dtype), true);
     if (!pl.ok) {   // the planes do not fit: row bands
@@ -669,7 +669,7 @@ int small_backward(const Geometry &g, int dtype, const void *go, const void *x, 
         b.go = go;
         b.out = gx;
         b.w = w;
-        b.wkind = dtype;
+        b.wkind = wkind;
         b.partials = static_cast<double *>(workspace);
         fill_band(b, g, bp);
         note_kernel("band_plane_backward");
@@ -686,7 +686,7 @@ int small_backward(const Geometry &g, int dtype, const void *go, const void *x, 
     p.go = go;
     p.out = gx;
     p.w = w;
-    p.wkind = dtype;
+    p.wkind = wkind;
     p.partials = static_cast<double *>(workspace);
     fill_small(p, g, pl);
     note_kernel("small_plane_backward");

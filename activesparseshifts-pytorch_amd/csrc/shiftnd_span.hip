@@ -2199,10 +2199,10 @@ static void launch_span_backward(const SpanParams &p, const SpanPlan &sp, bool a
     r.C = p.C;
     r.spv = p.spp;
     r.d_spv = p.d_spp;
-    launch_step_reduce(T::kDtype, ND, r, gw, st);
+    launch_step_reduce(p.wkind, ND, r, gw, st);
 }
 
-int span_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, void *gx, void *gw, void *workspace,
+int span_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw, void *workspace,
                   hipStream_t st) {
     const int es = dtype_size(dtype);
     const SpanPlan sp = span_plan(g, es);
@@ -2227,7 +2227,7 @@ int span_backward(const Geometry &g, int dtype, const void *go, const void *x, c
         p.P1 = static_cast<int>(g.P[1]);
         p.g_plane = g.P[0] * g.P[1] * g.P[2];   // (2-D / 1-D: P0 = 1)
     }
-    p.wkind = dtype;
+    p.wkind = wkind;
     p.N = static_cast<int>(g.N);
     p.C = static_cast<int>(g.C);
     p.pad = g.pad;

@@ -450,7 +450,7 @@ int launch_step_backward(StepParams &p, const StepLayout &L, bool active, void *
             hipLaunchKernelGGL((step_backward<T, ND, ACT, PAD>), grid, block, lds, st, p);
         });
     });
-    launch_step_reduce(T::kDtype, ND, p, gw, st);
+    launch_step_reduce(p.wkind, ND, p, gw, st);
     return SHIFTND_OK;
 }
 
@@ -461,9 +461,9 @@ void launch_step_prep(int dtype, bool active, const StepParams &p, hipStream_t s
     with_float_type(dtype, [&](auto t) { hipLaunchKernelGGL((step_prep<tag_type<decltype(t)>>), grid, block, 0, st, p, active); });
 }
 
-void launch_step_reduce(int dtype, int nd, const StepParams &p, void *grad_w, hipStream_t st) {
+void launch_step_reduce(int wkind, int nd, const StepParams &p, void *grad_w, hipStream_t st) {
     const dim3 grid(p.C), block(kThreads);
-    with_float_type(dtype, [&](auto t) {
+    with_float_type(wkind, [&](auto t) {
         using T = tag_type<decltype(t)>;
         hipLaunchKernelGGL((step_reduce<T>), grid, block, 0, st, p, static_cast<typename T::S *>(grad_w), nd);
     });
@@ -536,7 +536,7 @@ size_t step_backward_workspace(const Geometry &g, int dtype) {
     return step_layout(g, dtype_size(dtype), 1).bytes;
 }
 
-int step_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, void *gx, void *gw,
+int step_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw,
                   void *workspace, hipStream_t st) {
     const int es = dtype_size(dtype);
     const StepLayout L = step_layout(g, es);
@@ -551,7 +551,7 @@ int step_backward(const Geometry &g, int dtype, const void *go, const void *x, c
     p.colx = reinterpret_cast<int16_t *>(ws + L.off_colx);
     p.colg = reinterpret_cast<int16_t *>(ws + L.off_colg);
     p.x_plane = g.S[0] * g.S[1] * g.S[2];
-    p.wkind = dtype;
+    p.wkind = wkind;
     p.N = static_cast<int>(g.N);
     p.C = static_cast<int>(g.C);
     p.pad = g.pad;

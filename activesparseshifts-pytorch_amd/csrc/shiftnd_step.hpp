@@ -71,9 +71,10 @@ inline bool walk_crop_window_ok(const Geometry &g, bool pooled = false) {
 int walk3_backward_launch(StepParams &p, const Geometry &g, int dtype, int cpr, void *gw, hipStream_t st);
 
 // One copy of step_prep / step_reduce in the library: shiftnd_step.hip instantiates them and defines these launchers; the walk
-// and row-span translation units call them (T::kDtype picks the element type).
+// and row-span translation units call them.  step_prep: `dtype` is the tensors' element type (it shapes the column records; the weights
+// are read as p.wkind).  step_reduce: `wkind` is the element type of grad_w, the weights' (the kernel uses its type for that store only).
 void launch_step_prep(int dtype, bool active, const StepParams &p, hipStream_t st);
-void launch_step_reduce(int dtype, int nd, const StepParams &p, void *grad_w, hipStream_t st);
+void launch_step_reduce(int wkind, int nd, const StepParams &p, void *grad_w, hipStream_t st);
 
 namespace {
 

@@ -34,9 +34,9 @@ __global__ __launch_bounds__(64) void reduce_weight_grads(const double *__restri
 }
 }  // namespace
 
-void launch_reduce_weight_grads(int dtype, const double *partials, int groups, int C, int nd, void *grad_w, hipStream_t st) {
+void launch_reduce_weight_grads(int wkind, const double *partials, int groups, int C, int nd, void *grad_w, hipStream_t st) {
     const dim3 grid(static_cast<unsigned>(C) * nd), block(64);
-    switch (dtype) {
+    switch (wkind) {
     case SHIFTND_F32: hipLaunchKernelGGL((reduce_weight_grads<f32_t>), grid, block, 0, st, partials, groups, C, nd, static_cast<float *>(grad_w)); break;
     case SHIFTND_F64: hipLaunchKernelGGL((reduce_weight_grads<f64_t>), grid, block, 0, st, partials, groups, C, nd, static_cast<double *>(grad_w)); break;
     case SHIFTND_F16: hipLaunchKernelGGL((reduce_weight_grads<f16_t>), grid, block, 0, st, partials, groups, C, nd, static_cast<f16_t::S *>(grad_w)); break;
@@ -130,7 +130,7 @@ __device__ __forceinline__ void gather_corners(const typename T::S *arr, const i
 // active forward ----------------------------------------------------------------------------------
 template <typename T, int ND>
 __global__ __launch_bounds__(kThreads) void strided_active_forward(Geometry g, const typename T::S *__restrict__ x,
-                                                                    const typename T::S *__restrict__ w,
+                                                                    const void *__restrict__ w, int wkind,
                                                                     typename T::S *__restrict__ out, int64_t total) {
     using CT = typename T::C;
     const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
@@ -147,7 +147,7 @@ __global__ __launch_bounds__(kThreads) void strided_active_forward(Geometry g, c
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
             int64_t sh = 0;
-            if (g.wcol[d] >= 0) prep_shift_forward<CT>(load_weight<CT>(w, T::kDtype, c * g.nd + g.wcol[d]), true, sh, dw[g.wcol[d]]);
+            if (g.wcol[d] >= 0) prep_shift_forward<CT>(load_weight<CT>(w, wkind, c * g.nd + g.wcol[d]), true, sh, dw[g.wcol[d]]);
             idx[d] = o[d] + g.L[d] - sh;
         }
         CT v[8];
@@ -160,7 +160,7 @@ __global__ __launch_bounds__(kThreads) void strided_active_forward(Geometry g, c
 template <typename T, int ND, bool ACTIVE>
 __global__ __launch_bounds__(kThreads) void strided_backward(Geometry g, const typename T::S *__restrict__ go,
                                                              const typename T::S *__restrict__ x,
-                                                             const typename T::S *__restrict__ w,
+                                                             const void *__restrict__ w, int wkind,
                                                              typename T::S *__restrict__ gx,
                                                              double *__restrict__ partials) {
     using CT = typename T::C;
@@ -171,7 +171,7 @@ __global__ __launch_bounds__(kThreads) void strided_backward(Geometry g, const t
     CT dw[3] = {0, 0, 0};
 #pragma unroll
     for (int d = 0; d < 3; ++d)
-        if (g.wcol[d] >= 0) prep_shift_backward<CT>(load_weight<CT>(w, T::kDtype, c * g.nd + g.wcol[d]), ACTIVE, sh[d], dw[g.wcol[d]]);
+        if (g.wcol[d] >= 0) prep_shift_backward<CT>(load_weight<CT>(w, wkind, c * g.nd + g.wcol[d]), ACTIVE, sh[d], dw[g.wcol[d]]);
 
     const typename T::S *xp = x + n * g.xs[0] + c * g.xs[1];
     const typename T::S *gop = go + n * g.os[0] + c * g.os[1];
@@ -226,49 +226,49 @@ __global__ __launch_bounds__(kThreads) void strided_backward(Geometry g, const t
 }
 
 template <typename T, int ND>
-int launch_strided_backward_nd(const Geometry &g, const void *go, const void *x, const void *w, void *gx, void *gw,
+int launch_strided_backward_nd(const Geometry &g, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw,
                                double *partials, hipStream_t st) {
     using S = typename T::S;
     const int64_t planes = g.N * g.C;
     if (planes > 0x7fffffffLL) return SHIFTND_ERR_TOO_LARGE;
     if (g.active)
         hipLaunchKernelGGL((strided_backward<T, ND, true>), dim3(static_cast<unsigned>(planes)), dim3(kThreads), 0, st, g,
-                           static_cast<const S *>(go), static_cast<const S *>(x), static_cast<const S *>(w),
+                           static_cast<const S *>(go), static_cast<const S *>(x), w, wkind,
                            static_cast<S *>(gx), partials);
     else
         hipLaunchKernelGGL((strided_backward<T, ND, false>), dim3(static_cast<unsigned>(planes)), dim3(kThreads), 0, st, g,
-                           static_cast<const S *>(go), static_cast<const S *>(x), static_cast<const S *>(w),
+                           static_cast<const S *>(go), static_cast<const S *>(x), w, wkind,
                            static_cast<S *>(gx), partials);
-    reduce_weight_grads_of<T>(partials, static_cast<int>(g.N), static_cast<int>(g.C), g.nd, gw, st);
+    launch_reduce_weight_grads(wkind, partials, static_cast<int>(g.N), static_cast<int>(g.C), g.nd, gw, st);
     return SHIFTND_OK;
 }
 
 template <typename T>
-int launch_strided_backward_t(const Geometry &g, const void *go, const void *x, const void *w, void *gx, void *gw,
+int launch_strided_backward_t(const Geometry &g, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw,
                               double *partials, hipStream_t st) {
     switch (g.nd) {
-    case 1: return launch_strided_backward_nd<T, 1>(g, go, x, w, gx, gw, partials, st);
-    case 2: return launch_strided_backward_nd<T, 2>(g, go, x, w, gx, gw, partials, st);
-    default: return launch_strided_backward_nd<T, 3>(g, go, x, w, gx, gw, partials, st);
+    case 1: return launch_strided_backward_nd<T, 1>(g, go, x, w, wkind, gx, gw, partials, st);
+    case 2: return launch_strided_backward_nd<T, 2>(g, go, x, w, wkind, gx, gw, partials, st);
+    default: return launch_strided_backward_nd<T, 3>(g, go, x, w, wkind, gx, gw, partials, st);
     }
 }
 
 template <typename T>
-int launch_strided_active_t(const Geometry &g, const void *x, const void *w, void *out, int64_t total, unsigned grid,
+int launch_strided_active_t(const Geometry &g, const void *x, const void *w, int wkind, void *out, int64_t total, unsigned grid,
                             hipStream_t st) {
     using S = typename T::S;
     switch (g.nd) {
     case 1:
         hipLaunchKernelGGL((strided_active_forward<T, 1>), dim3(grid), dim3(kThreads), 0, st, g,
-                           static_cast<const S *>(x), static_cast<const S *>(w), static_cast<S *>(out), total);
+                           static_cast<const S *>(x), w, wkind, static_cast<S *>(out), total);
         break;
     case 2:
         hipLaunchKernelGGL((strided_active_forward<T, 2>), dim3(grid), dim3(kThreads), 0, st, g,
-                           static_cast<const S *>(x), static_cast<const S *>(w), static_cast<S *>(out), total);
+                           static_cast<const S *>(x), w, wkind, static_cast<S *>(out), total);
         break;
     default:
         hipLaunchKernelGGL((strided_active_forward<T, 3>), dim3(grid), dim3(kThreads), 0, st, g,
-                           static_cast<const S *>(x), static_cast<const S *>(w), static_cast<S *>(out), total);
+                           static_cast<const S *>(x), w, wkind, static_cast<S *>(out), total);
         break;
     }
     return SHIFTND_OK;
@@ -310,25 +310,25 @@ int strided_forward(const Geometry &g, int dtype, const void *x, const void *w, 
         return SHIFTND_OK;
     }
     switch (dtype) {
-    case SHIFTND_F32: return launch_strided_active_t<f32_t>(g, x, w, out, total, grid, st);
-    case SHIFTND_F64: return launch_strided_active_t<f64_t>(g, x, w, out, total, grid, st);
-    case SHIFTND_F16: return launch_strided_active_t<f16_t>(g, x, w, out, total, grid, st);
-    case SHIFTND_BF16: return launch_strided_active_t<bf16_t>(g, x, w, out, total, grid, st);
+    case SHIFTND_F32: return launch_strided_active_t<f32_t>(g, x, w, wkind, out, total, grid, st);
+    case SHIFTND_F64: return launch_strided_active_t<f64_t>(g, x, w, wkind, out, total, grid, st);
+    case SHIFTND_F16: return launch_strided_active_t<f16_t>(g, x, w, wkind, out, total, grid, st);
+    case SHIFTND_BF16: return launch_strided_active_t<bf16_t>(g, x, w, wkind, out, total, grid, st);
     default: return SHIFTND_ERR_UNSUPPORTED_DTYPE;
     }
 }
 
 size_t strided_backward_workspace(const Geometry &g) { return static_cast<size_t>(g.N * g.C) * 3 * sizeof(double); }
 
-int strided_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, void *gx, void *gw,
+int strided_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw,
                      void *workspace, hipStream_t st) {
     double *partials = static_cast<double *>(workspace);
     note_kernel("strided_backward");
     switch (dtype) {
-    case SHIFTND_F32: return launch_strided_backward_t<f32_t>(g, go, x, w, gx, gw, partials, st);
-    case SHIFTND_F64: return launch_strided_backward_t<f64_t>(g, go, x, w, gx, gw, partials, st);
-    case SHIFTND_F16: return launch_strided_backward_t<f16_t>(g, go, x, w, gx, gw, partials, st);
-    case SHIFTND_BF16: return launch_strided_backward_t<bf16_t>(g, go, x, w, gx, gw, partials, st);
+    case SHIFTND_F32: return launch_strided_backward_t<f32_t>(g, go, x, w, wkind, gx, gw, partials, st);
+    case SHIFTND_F64: return launch_strided_backward_t<f64_t>(g, go, x, w, wkind, gx, gw, partials, st);
+    case SHIFTND_F16: return launch_strided_backward_t<f16_t>(g, go, x, w, wkind, gx, gw, partials, st);
+    case SHIFTND_BF16: return launch_strided_backward_t<bf16_t>(g, go, x, w, wkind, gx, gw, partials, st);
     default: return SHIFTND_ERR_UNSUPPORTED_DTYPE;
     }
 }

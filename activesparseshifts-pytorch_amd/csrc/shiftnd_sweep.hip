@@ -534,7 +534,7 @@ template <typename T, bool ACTIVE> void launch_backward_nd(const SweepParams &p,
 template <typename T> int launch_backward(const SweepParams &p, bool active, int groups, void *gw, hipStream_t st) {
     if (active) launch_backward_nd<T, true>(p, st);
     else launch_backward_nd<T, false>(p, st);
-    reduce_weight_grads_of<T>(p.partials, groups, p.C, p.nd, gw, st);
+    launch_reduce_weight_grads(p.wkind, p.partials, groups, p.C, p.nd, gw, st);
     return SHIFTND_OK;
 }
 
@@ -641,7 +641,7 @@ size_t sweep_backward_workspace(const Geometry &g, int dtype) {
     return static_cast<size_t>(g.N) * p.bpp * static_cast<size_t>(g.C) * 3 * sizeof(double);
 }
 
-int sweep_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, void *gx, void *gw,
+int sweep_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw,
                    void *workspace, hipStream_t st) {
     SweepParams p{};
     note_kernel("sweep_backward");
@@ -650,7 +650,7 @@ int sweep_backward(const Geometry &g, int dtype, const void *go, const void *x, 
     p.go = go;
     p.out = gx;
     p.w = w;
-    p.wkind = dtype;
+    p.wkind = wkind;
     p.partials = static_cast<double *>(workspace);
     const int groups = static_cast<int>(g.N) * static_cast<int>(p.bpp);
     switch (dtype) {

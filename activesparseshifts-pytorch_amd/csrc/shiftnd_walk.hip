@@ -819,7 +819,7 @@ bool walk16_backward_eligible(const Geometry &g, int dtype, const void *go, cons
 
 size_t walk16_backward_workspace(const Geometry &g, int dtype) { return walk16_volume_ok(g, dtype) ? walk_plan(g).bytes : 0; }
 
-int walk16_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, void *gx, void *gw, void *workspace,
+int walk16_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw, void *workspace,
                     hipStream_t st) {
     const WalkPlan W = walk_plan(g);
     StepParams p{};
@@ -832,7 +832,7 @@ int walk16_backward(const Geometry &g, int dtype, const void *go, const void *x,
     p.desc = reinterpret_cast<ChanDesc *>(ws + W.off_desc);
     p.colx = p.colg = nullptr;   // (no column tables: the kernel folds its maps itself)
     p.x_plane = g.S[0] * g.S[1] * g.S[2];
-    p.wkind = dtype;
+    p.wkind = wkind;
     p.N = static_cast<int>(g.N);
     p.C = static_cast<int>(g.C);
     p.pad = g.pad;
@@ -881,7 +881,7 @@ int walk16_backward(const Geometry &g, int dtype, const void *go, const void *x,
                 }
             });
         });
-        launch_step_reduce(T::kDtype, 3, p, gw, st);
+        launch_step_reduce(p.wkind, 3, p, gw, st);
     });
     return SHIFTND_OK;
 }

@@ -885,7 +885,7 @@ template <typename T> static void launch_walk_backward(StepParams &p, size_t lds
             });
         });
     });
-    launch_step_reduce(T::kDtype, 3, p, gw, st);
+    launch_step_reduce(p.wkind, 3, p, gw, st);
 }
 
 // the second half of step_backward()'s launch for 3-D problems: balanced row steps, one record of sums per workgroup

@@ -211,6 +211,19 @@ void check_same(const char *fn, const Tensor &a, const char *an, const Tensor &b
                 " (while checking arguments for ", fn, ")");
 }
 
+// Mixed precision: fp16 / bf16 tensors with fp32 weights, what torch.autocast hands these ops -- activations in the autocast type,
+// parameters as they are.  (No Autocast-key registration is needed for that: an op without one falls through the key, and input and
+// weight arrive as the caller holds them.)  Returns SHIFTND_WEIGHTS_F32 for that one combination and 0 for tensors of the same
+// type; every other pair raises check_same's error.  grad_weights is allocated like the weights, so it comes back fp32.
+int weights_flag(const char *fn, const Tensor &t, const char *tn, const Tensor &weights) {
+    const bool half = t.scalar_type() == at::kHalf || t.scalar_type() == at::kBFloat16;
+    if (!(half && weights.scalar_type() == at::kFloat && t.get_device() == weights.get_device())) {
+        check_same(fn, t, tn, weights, "weights");
+        return 0;
+    }
+    return SHIFTND_WEIGHTS_F32;
+}
+
 // ---- channels-last inputs ---------------------------------------------------------------------------------------
 // The reference's CUDA backend walks a channels-last input through its strides (cuda/shifts_cuda.cu:217-262:
 // uncoalesced) and returns an NCHW-contiguous result.  Here a dense channels-last tensor is first brought to the
@@ -256,13 +269,13 @@ template <int ND> Tensor shift_forward_hip(const Tensor &input_, const Tensor &w
                                            at::IntArrayRef new_size, int64_t padding_mode, bool active_flag) {
     TORCH_CHECK(input_.is_cuda(), "input must be a CUDA tensor");
     TORCH_CHECK(weights.is_cuda(), "weights must be a CUDA tensor");
-    check_same("shiftnd_forward_cuda", input_, "input", weights, "weights");
+    const int mixed = weights_flag("shiftnd_forward_cuda", input_, "input", weights);
     TORCH_CHECK(input_.dim() == ND + 2, "shift", ND, "d: expected a ", ND + 2, "-D input");
     TORCH_CHECK(weights.dim() == 2 && weights.size(0) == input_.size(1) && weights.size(1) == ND,
                 "shift", ND, "d: weights must have shape [C, ", ND, "]");
     if (padding_mode < 0 || padding_mode > 4) return Tensor();  // the reference's switch has no default
     c10::DeviceGuard device_guard(input_.device());
-    const int dtype = to_shiftnd_dtype(input_.scalar_type(), "shiftnd_forward_cuda");
+    const int dtype = to_shiftnd_dtype(input_.scalar_type(), "shiftnd_forward_cuda") | mixed;
     int32_t b[6];
     if (static_cast<int>(new_size.size()) == ND + 2) read_borders_for(borders, input_, new_size.slice(2), ND, b);
     else read_borders(borders, b);
@@ -293,7 +306,7 @@ std::tuple<Tensor, Tensor> shift_backward_hip(const Tensor &grad_, const Tensor 
     TORCH_CHECK(input_.is_cuda(), "input must be a CUDA tensor");
     TORCH_CHECK(weights.is_cuda(), "weights must be a CUDA tensor");
     check_same("shiftnd_backward_cuda", grad_, "grad", input_, "input");
-    check_same("shiftnd_backward_cuda", grad_, "grad", weights, "weights");
+    const int mixed = weights_flag("shiftnd_backward_cuda", grad_, "grad", weights);
     TORCH_CHECK(input_.dim() == ND + 2 && grad_.dim() == ND + 2, "shift", ND, "d backward: expected ", ND + 2, "-D tensors");
     if (padding_mode < 0 || padding_mode > 4) return std::make_tuple(Tensor(), Tensor());
     c10::DeviceGuard device_guard(grad_.device());
@@ -301,9 +314,9 @@ std::tuple<Tensor, Tensor> shift_backward_hip(const Tensor &grad_, const Tensor 
     read_borders_for(borders, input_, grad_.sizes().slice(2), ND, b);
     for (int r = 0; r < ND; ++r)
         TORCH_CHECK(grad_.size(2 + r) == b[2 * r + 1] - b[2 * r], "shift", ND, "d backward: grad does not match borders");
-    const int dtype = to_shiftnd_dtype(grad_.scalar_type(), "shiftnd_backward_cuda");
+    const int dtype = to_shiftnd_dtype(grad_.scalar_type(), "shiftnd_backward_cuda") | mixed;
     Tensor w = weights.contiguous();
-    Tensor grad_weights = at::empty_like(w, at::MemoryFormat::Contiguous);
+    Tensor grad_weights = at::empty_like(w, at::MemoryFormat::Contiguous);   // (the weights' dtype: fp32 for a mixed call)
     // saved input dense channels-last, incoming gradient channels-last too or NCHW-contiguous (what follows the reference's
     // float forward, which returns NCHW for a channels-last input): the library may have a kernel for that layout
     // (shiftnd_cl_tiled.hip; grad_x comes out in the input's layout); otherwise change the layout once, then the
@@ -405,7 +418,7 @@ template <int ND> Tensor pool_forward_hip(const Tensor &input_, const Tensor &we
     check_pool<ND>(pool);
     TORCH_CHECK(input_.is_cuda(), "input must be a CUDA tensor");
     TORCH_CHECK(weights.is_cuda(), "weights must be a CUDA tensor");
-    check_same("shiftnd_pool_forward_cuda", input_, "input", weights, "weights");
+    const int mixed = weights_flag("shiftnd_pool_forward_cuda", input_, "input", weights);
     TORCH_CHECK(input_.dim() == ND + 2, "shift", ND, "d_pool: expected a ", ND + 2, "-D input");
     TORCH_CHECK(weights.dim() == 2 && weights.size(0) == input_.size(1) && weights.size(1) == ND,
                 "shift", ND, "d_pool: weights must have shape [C, ", ND, "]");
@@ -413,7 +426,7 @@ template <int ND> Tensor pool_forward_hip(const Tensor &input_, const Tensor &we
     c10::DeviceGuard device_guard(input_.device());
     const Tensor input = is_channels_last_dense(input_) ? channels_last_to_contiguous(input_) : input_;
     if (!input.is_contiguous()) return pool_forward_composed<ND>(input, weights, borders, new_size, pool, padding_mode, active_flag);
-    const int dtype = to_shiftnd_dtype(input.scalar_type(), "shiftnd_pool_forward_cuda");
+    const int dtype = to_shiftnd_dtype(input.scalar_type(), "shiftnd_pool_forward_cuda") | mixed;
     int32_t b[6], k[3] = {1, 1, 1};
     read_borders(borders, b);
     for (int r = 0; r < ND; ++r) k[r] = static_cast<int32_t>(pool[r]);
@@ -442,14 +455,14 @@ std::tuple<Tensor, Tensor> pool_backward_hip(const Tensor &grad, const Tensor &w
     TORCH_CHECK(input_.is_cuda(), "input must be a CUDA tensor");
     TORCH_CHECK(weights.is_cuda(), "weights must be a CUDA tensor");
     check_same("shiftnd_pool_backward_cuda", grad, "grad", input_, "input");
-    check_same("shiftnd_pool_backward_cuda", grad, "grad", weights, "weights");
+    const int mixed = weights_flag("shiftnd_pool_backward_cuda", grad, "grad", weights);
     TORCH_CHECK(input_.dim() == ND + 2 && grad.dim() == ND + 2, "shift", ND, "d_pool backward: expected ", ND + 2, "-D tensors");
     if (padding_mode < 0 || padding_mode > 4) return std::make_tuple(Tensor(), Tensor());
     c10::DeviceGuard device_guard(grad.device());
     const Tensor input = is_channels_last_dense(input_) ? channels_last_to_contiguous(input_) : input_;
     if (!input.is_contiguous())
         return pool_backward_composed<ND>(grad, weights, input, borders, pool, padding_mode, active_flag);
-    const int dtype = to_shiftnd_dtype(grad.scalar_type(), "shiftnd_pool_backward_cuda");
+    const int dtype = to_shiftnd_dtype(grad.scalar_type(), "shiftnd_pool_backward_cuda") | mixed;
     int32_t b[6], k[3] = {1, 1, 1};
     read_borders(borders, b);
     for (int r = 0; r < ND; ++r) k[r] = static_cast<int32_t>(pool[r]);
@@ -463,7 +476,7 @@ std::tuple<Tensor, Tensor> pool_backward_hip(const Tensor &grad, const Tensor &w
     Tensor g = grad.contiguous();
     Tensor w = weights.contiguous();
     Tensor grad_input = at::empty_like(input, at::MemoryFormat::Contiguous);
-    Tensor grad_weights = at::empty_like(w, at::MemoryFormat::Contiguous);
+    Tensor grad_weights = at::empty_like(w, at::MemoryFormat::Contiguous);   // (the weights' dtype)
     const size_t ws_bytes = shiftnd_backward_pooled_workspace_bytes(&p, k);  // (the pooled plan, not the plain one)
     Tensor workspace = at::empty({static_cast<int64_t>(ws_bytes)}, input.options().dtype(at::kByte));
     rc = shiftnd_backward_pooled(&p, k, g.data_ptr(), input.data_ptr(), w.data_ptr(), grad_input.data_ptr(),

@@ -14,6 +14,7 @@ import torch
 _LIB_PATH = os.environ.get("SHIFTND_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libshiftnd_hip.so")
 
 F32, F64, F16, BF16, I8, U8, I32 = range(7)
+WEIGHTS_F32 = 0x100   # SHIFTND_WEIGHTS_F32: OR-ed onto F16 / BF16 -- fp32 weights (and grad_w) with 16-bit tensors
 PATH_NONE, PATH_EMPTY, PATH_PLANE, PATH_STRIDED, PATH_SWEEP, PATH_CL = range(6)
 
 DTYPES = {torch.float32: F32, torch.float64: F64, torch.float16: F16, torch.bfloat16: BF16,
@@ -126,10 +127,13 @@ def check_borders(sizes, user, ndim):
     return list(out), list(new)[:shift + min(ndim, 3)]
 
 
-def problem(x, pad, active, borders, dtype=None):
+def problem(x, pad, active, borders, dtype=None, w=None):
+    """w: the weights of the call, if it has float weights -- fp32 weights with an fp16 / bf16 `x` set WEIGHTS_F32 (mixed precision)"""
     p = Problem()
     p.ndim = x.dim() - 2
     p.dtype = DTYPES[x.dtype] if dtype is None else dtype
+    if w is not None and w.dtype == torch.float32 and x.dtype in (torch.float16, torch.bfloat16):
+        p.dtype |= WEIGHTS_F32
     p.padding_mode = int(pad)
     p.active = int(bool(active))
     for i in range(5):
@@ -150,8 +154,9 @@ def _stream():
 
 
 def forward(x, w, pad, active, borders=None, out=None):
-    """x, w: device tensors (float dtypes).  Returns a new contiguous output (or fills `out`)."""
-    p = problem(x, pad, active, borders)
+    """x, w: device tensors (float dtypes; w of x's dtype, or fp32 with an fp16 / bf16 x).  Returns a new contiguous output (or
+    fills `out`)."""
+    p = problem(x, pad, active, borders, w=w)
     if out is None:
         out = _new(out_shape(x, borders), x)
     w = w.contiguous()
@@ -166,7 +171,8 @@ def backward_workspace(x, pad, active, borders=None):
 
 
 def backward(grad_out, w, x, pad, active, borders=None, grad_x=None, grad_w=None, workspace=None):
-    p = problem(x, pad, active, borders)
+    """grad_w comes back in w's dtype (fp32 for fp32 weights with a 16-bit x)"""
+    p = problem(x, pad, active, borders, w=w)
     w = w.contiguous()
     if grad_x is None:
         grad_x = _new(x.shape, x)
@@ -225,7 +231,7 @@ def pooled_shape(x, pool, borders=None):
 def forward_pooled(x, w, pad, active, pool, borders=None, out=None):
     """Fused shift + avg_pool(kernel = stride = pool, ceil_mode=True); x, w contiguous device tensors."""
     assert x.is_contiguous()
-    p = problem(x, pad, active, borders)
+    p = problem(x, pad, active, borders, w=w)
     if out is None:
         out = _new(pooled_shape(x, pool, borders), x)
     w = w.contiguous()
@@ -258,7 +264,7 @@ def backward_pooled_workspace_bytes(x, pad, active, pool, borders=None):
 
 def backward_pooled(grad_pooled, w, x, pad, active, pool, borders=None, grad_x=None, grad_w=None, workspace=None):
     assert x.is_contiguous() and grad_pooled.is_contiguous()
-    p = problem(x, pad, active, borders)
+    p = problem(x, pad, active, borders, w=w)
     w = w.contiguous()
     if grad_x is None:
         grad_x = _new(x.shape, x)

@@ -23,7 +23,8 @@
  *     of the INPUT (unused trailing spatial dims = 1) and element strides[5] in the same order
  *     (unused = 0).  ndim = number of spatial dims (1..3).
  *   - weights: device pointer to a contiguous [C, ndim] array of the input's dtype
- *     (column s shifts spatial dim s: H, W, D -- functional.py:76-77).
+ *     (column s shifts spatial dim s: H, W, D -- functional.py:76-77); fp32 for fp16 / bf16 tensors
+ *     when p->dtype carries SHIFTND_WEIGHTS_F32 (mixed precision, below).
  *   - borders: 6 HOST ints {l_i, r_i, l_j, r_j, l_k, r_k}, the absolute [l, r) window that
  *     check_borders produces; the output has spatial sizes r - l.
  *   - padding_mode: 0 zeros, 1 border, 2 periodic, 3 reflect, 4 symmetric
@@ -39,6 +40,13 @@
  *     multiply-add per lerp) and rounded once (RNE) on store; the weight gradient sums products in
  *     the compute type (fused multiply-add), accumulates them in fp64 by a deterministic two-stage
  *     reduction and rounds once to the tensor dtype.
+ *   - Mixed precision (SHIFTND_WEIGHTS_F32): the fp32 weight enters the 16-bit kernels' compute type
+ *     (fp32) as it is and is never rounded to 16 bits: the sparse shift is rintf(w), the backward
+ *     prepares its shift and fractions from the fp32 value, the interpolation fractions are the fp32
+ *     ones.  out and grad_x keep the tensor dtype under the 16-bit contract above (widened,
+ *     interpolated in fp32, rounded once); grad_w is fp32, the fp64 sum narrowed once.  With weights
+ *     that 16 bits hold exactly a mixed call runs the same kernel as the same-dtype call and returns
+ *     the same bits in out and grad_x.
  */
 #ifndef SHIFTND_HIP_H_
 #define SHIFTND_HIP_H_
@@ -63,6 +71,21 @@ typedef enum shiftnd_dtype {
     SHIFTND_I32 = 6  /* qint32 int_repr */
 } shiftnd_dtype;
 
+/*
+ * Mixed precision (what torch.autocast produces: 16-bit activations, fp32 parameters).  OR-ed onto SHIFTND_F16 or SHIFTND_BF16
+ * in shiftnd_problem.dtype: `weights` is a const float [C, ndim] array and `grad_w` a float [C, ndim] array; x, out, grad_out
+ * and grad_x keep the 16-bit type.  No other combination of tensor and weight types exists.
+ *   Honoured by shiftnd_forward, shiftnd_backward, shiftnd_forward_pooled, shiftnd_backward_pooled; shiftnd_pooled_sizes, both
+ *   *_workspace_bytes and both *_serves_channels_last give the answer they give without the flag.
+ *   Errors, before anything is launched:
+ *     - on any other dtype (F32, F64, the quantized types), and on the quantized entry points: SHIFTND_ERR_UNSUPPORTED_DTYPE
+ *       (the workspace queries and *_serves_channels_last, which return no status, answer 0);
+ *     - together with the x == NULL && grad_w == NULL forms of shiftnd_backward / shiftnd_backward_pooled:
+ *       SHIFTND_ERR_INVALID_ARGUMENT (a fixed table is converted to the tensor dtype by its owner).
+ * Without the flag nothing changes.
+ */
+#define SHIFTND_WEIGHTS_F32 0x100
+
 typedef enum shiftnd_status {
     SHIFTND_OK = 0,
     SHIFTND_ERR_INVALID_ARGUMENT = -1,
@@ -86,7 +109,7 @@ typedef enum shiftnd_path {
 /* Problem geometry shared by the entry points. */
 typedef struct shiftnd_problem {
     int32_t ndim;          /* spatial dims: 1, 2 or 3 */
-    int32_t dtype;         /* shiftnd_dtype of input/output (and of float weights) */
+    int32_t dtype;         /* shiftnd_dtype of input/output (and of float weights), optionally | SHIFTND_WEIGHTS_F32 */
     int32_t padding_mode;  /* 0..4 */
     int32_t active;        /* 0: sparse shift (rounded integer shift); 1: active (interpolated) */
     int64_t sizes[5];      /* input N, C, H, W, D */
@@ -155,7 +178,7 @@ SHIFTND_API int shiftnd_backward_serves_channels_last(const shiftnd_problem *p, 
                                                       const int64_t grad_x_strides[5]);
 
 /*
- * Forward, float dtypes (F32, F64, F16, BF16).
+ * Forward, float dtypes (F32, F64, F16, BF16; F16 / BF16 also with SHIFTND_WEIGHTS_F32).
  * out has sizes {N, C, r_i-l_i, r_j-l_j, r_k-l_k}; out_strides are its element strides.
  */
 SHIFTND_API int shiftnd_forward(const shiftnd_problem *p,
@@ -166,7 +189,8 @@ SHIFTND_API int shiftnd_forward(const shiftnd_problem *p,
 
 /*
  * Backward, float dtypes.  grad_out has the forward output's sizes; grad_x the input's sizes;
- * grad_w is a contiguous [C, ndim] array of the tensor dtype and is fully overwritten.
+ * grad_w is a contiguous [C, ndim] array of the weights' dtype (the tensor dtype; fp32 with SHIFTND_WEIGHTS_F32) and is fully
+ * overwritten.
  * workspace: device scratch of at least shiftnd_backward_workspace_bytes(p) bytes
  * (fp64 partial sums of the weight gradient); its contents need not be initialised.
  *
