@@ -213,6 +213,12 @@ bool gradx_embed_eligible(const Geometry &g, int dtype, const void *go, const vo
 int gradx_embed(const Geometry &g, int dtype, const void *go, const void *w, void *gx, hipStream_t st);
 int gradx_gather(const Geometry &g, int dtype, const void *go, const void *w, void *gx, hipStream_t st);
 
+// ---- segment-major tensors (shiftnd_segment.hip): the sparse shift of float tensors whose memory order is N, S0, C, S1, S2 (a
+// temporal shift of [N*T, C, H, W] seen as [N, C, T, H*W]), x and out in the same dense layout, whole window; planes are copied
+// or filled, or gathered element by element where the table also shifts an inner dim
+bool segment_forward_eligible(const Geometry &g, int dtype, const void *x, const void *out);
+int segment_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, void *out, hipStream_t st);
+
 // ---- layout change (shiftnd_transpose.hip): dst[n][c][r] = src[n][r][c], dense tensors ---------------------------
 int transpose_planes(const void *src, void *dst, int64_t N, int64_t rows, int64_t cols, int esize, hipStream_t st);
 

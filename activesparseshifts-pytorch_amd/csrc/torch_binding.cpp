@@ -891,6 +891,115 @@ template <int ND> Tensor shift_fixed_pool_backward_hip(const Tensor &grad_, cons
     return grad_input;
 }
 
+// ---- temporal shift (TSM, arXiv 1811.08383): fixed shifts across the frames of [N*T, C, ...] --------------------------------
+// temporal_shift(input, shifts, n_segment, padding_mode): every run of n_segment consecutive rows of dim 0 is one clip, and
+// channel c of frame t is channel c of frame pad(t - shifts[c]) of the same clip -- shift2d_fixed of the [N, C, T, M] view under
+// the table (s_c, 0), without the two layout changes that view would cost.  The autograd node keeps the table alone; the backward
+// is _temporal_shift_backward, the same gather under -s.  On HIP tensors both are ONE shiftnd_forward / shiftnd_backward
+// (x == NULL form) call on the strides {T*C*M, M, C*M, 1}, which shiftnd_segment.hip serves at copy rate.
+using temporal_sig = Tensor(const Tensor &, const Tensor &, int64_t, int64_t);
+Tensor call_temporal(const char *name, const Tensor &t, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    auto op = c10::Dispatcher::singleton().findSchemaOrThrow(name, "").typed<temporal_sig>();
+    return op.call(t, shifts, n_segment, padding_mode);
+}
+
+void temporal_check(const Tensor &input, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    TORCH_CHECK(!input.is_quantized(), "temporal_shift: quantized inputs are not supported");
+    TORCH_CHECK(input.dim() >= 2 && input.dim() <= 5, "temporal_shift: expected a [N*T, C, ...] tensor of 2 to 5 dims");
+    TORCH_CHECK(n_segment >= 1 && input.size(0) % n_segment == 0, "temporal_shift: dim 0 (", input.size(0),
+                ") must be a multiple of n_segment (", n_segment, ")");
+    TORCH_CHECK((shifts.dim() == 1 || (shifts.dim() == 2 && shifts.size(1) == 1)) && shifts.size(0) == input.size(1),
+                "temporal_shift: shifts must have shape [C] or [C, 1]");
+    TORCH_CHECK(shifts.device() == input.device(), "temporal_shift: shifts must be on the input's device");
+    TORCH_CHECK(at::isFloatingType(shifts.scalar_type()) || at::isIntegralType(shifts.scalar_type(), false),
+                "temporal_shift: shifts must be integers or floats");
+    TORCH_CHECK(padding_mode >= 0 && padding_mode <= 4, "temporal_shift: padding_mode must be 0..4");
+}
+
+struct TemporalShiftFunction : public torch::autograd::Function<TemporalShiftFunction> {
+    static variable_list forward(AutogradContext *ctx, const Tensor &input, const Tensor &shifts, int64_t n_segment,
+                                 int64_t padding_mode) {
+        at::AutoDispatchBelowADInplaceOrView guard;
+        auto output = call_temporal("torchshifts::temporal_shift", input, shifts, n_segment, padding_mode);
+        ctx->saved_data["n_segment"] = n_segment;
+        ctx->saved_data["padding_mode"] = padding_mode;
+        ctx->save_for_backward({shifts.detach()});
+        return {output};
+    }
+    static variable_list backward(AutogradContext *ctx, const variable_list &grad_output) {
+        auto saved = ctx->get_saved_variables();
+        return {call_temporal("torchshifts::_temporal_shift_backward", grad_output[0], saved[0], ctx->saved_data["n_segment"].toInt(),
+                              ctx->saved_data["padding_mode"].toInt()),
+                Tensor(), Tensor(), Tensor()};
+    }
+};
+
+struct TemporalShiftBackwardFunction : public torch::autograd::Function<TemporalShiftBackwardFunction> {
+    static variable_list forward(AutogradContext *ctx, const Tensor &grad, const Tensor &shifts, int64_t n_segment,
+                                 int64_t padding_mode) {
+        at::AutoDispatchBelowADInplaceOrView guard;
+        return {call_temporal("torchshifts::_temporal_shift_backward", grad, shifts, n_segment, padding_mode)};
+    }
+    static variable_list backward(AutogradContext *, const variable_list &) {
+        TORCH_CHECK(0, "double backwards on temporal_shift not supported");
+    }
+};
+
+Tensor temporal_autograd(const Tensor &input, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    temporal_check(input, shifts, n_segment, padding_mode);
+    return TemporalShiftFunction::apply(input, shifts, n_segment, padding_mode)[0];
+}
+
+Tensor temporal_autograd_backward(const Tensor &grad, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    temporal_check(grad, shifts, n_segment, padding_mode);
+    return TemporalShiftBackwardFunction::apply(grad, shifts, n_segment, padding_mode)[0];
+}
+
+// one C-ABI call on the segment-major strides; sign = -1: the input gradient (x == NULL form, the table negated in the workspace)
+Tensor temporal_hip(const Tensor &t_, const Tensor &shifts, int64_t n_segment, int64_t padding_mode, bool backward) {
+    TORCH_CHECK(t_.is_cuda(), "temporal_shift: expected a CUDA tensor");
+    temporal_check(t_, shifts, n_segment, padding_mode);
+    c10::DeviceGuard device_guard(t_.device());
+    const int dtype = to_shiftnd_dtype(t_.scalar_type(), "temporal_shift_cuda");
+    const Tensor t = t_.contiguous();
+    Tensor out = at::empty(t.sizes(), t.options(), at::MemoryFormat::Contiguous);
+    if (t.numel() == 0) return out;
+    const int64_t T = n_segment, C = t.size(1), N = t.size(0) / T, M = t.numel() / (t.size(0) * C);
+    // [C, 2] of the tensor dtype, column 1 (the planes' own dim) zero: built on the device, no host sync.  Like fixed_table: exact
+    // for |s| <= 256 in bf16, <= 2048 in fp16 (the x == NULL form of shiftnd_backward takes no fp32 table for a 16-bit tensor)
+    Tensor w = at::zeros({C, 2}, t.options());
+    w.select(1, 0).copy_(shifts.detach().reshape({C}));
+    shiftnd_problem p;
+    p.ndim = 2;
+    p.dtype = dtype;
+    p.padding_mode = static_cast<int32_t>(padding_mode);
+    p.active = 0;
+    const int64_t sizes[5] = {N, C, T, M, 1};
+    const int32_t borders[6] = {0, static_cast<int32_t>(T), 0, static_cast<int32_t>(M), 0, 1};
+    for (int i = 0; i < 5; ++i) p.sizes[i] = sizes[i];
+    for (int i = 0; i < 6; ++i) p.borders[i] = borders[i];
+    TORCH_CHECK(T <= INT32_MAX && M <= INT32_MAX, "temporal_shift: n_segment and the frame size must fit 32 bits");
+    const int64_t st[5] = {T * C * M, M, C * M, 1, 0};
+    int rc;
+    if (!backward) {
+        rc = shiftnd_forward(&p, t.data_ptr(), st, w.data_ptr(), out.data_ptr(), st, current_stream(t));
+    } else {
+        const size_t ws_bytes = static_cast<size_t>(w.numel()) * w.element_size();
+        Tensor workspace = at::empty({static_cast<int64_t>(ws_bytes)}, t.options().dtype(at::kByte));
+        rc = shiftnd_backward(&p, t.data_ptr(), st, nullptr, nullptr, w.data_ptr(), out.data_ptr(), st, nullptr, workspace.data_ptr(),
+                              ws_bytes, current_stream(t));
+    }
+    TORCH_CHECK(rc == SHIFTND_OK, "temporal_shift (HIP): ", shiftnd_status_string(rc));
+    return out;
+}
+
+Tensor temporal_forward_hip(const Tensor &input, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    return temporal_hip(input, shifts, n_segment, padding_mode, false);
+}
+Tensor temporal_backward_hip(const Tensor &grad, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    return temporal_hip(grad, shifts, n_segment, padding_mode, true);
+}
+
 int64_t cuda_version() { return -1; }  // no CUDA toolkit: extension.py only compares when torch.version.cuda is set
 int64_t hip_version() { return HIP_VERSION; }
 
@@ -935,9 +1044,14 @@ TORCH_LIBRARY(torchshifts, m) {
     m.def("torchshifts::_shift1d_fixed_pool_backward(Tensor grad, Tensor shifts, Tensor borders, int[] input_size, int[] pool, int padding_mode) -> Tensor");
     m.def("torchshifts::_shift2d_fixed_pool_backward(Tensor grad, Tensor shifts, Tensor borders, int[] input_size, int[] pool, int padding_mode) -> Tensor");
     m.def("torchshifts::_shift3d_fixed_pool_backward(Tensor grad, Tensor shifts, Tensor borders, int[] input_size, int[] pool, int padding_mode) -> Tensor");
+    // temporal shift (TSM): fixed shifts across the frames of [N*T, C, ...] (not in the reference)
+    m.def("torchshifts::temporal_shift(Tensor input, Tensor shifts, int n_segment, int padding_mode) -> Tensor");
+    m.def("torchshifts::_temporal_shift_backward(Tensor grad, Tensor shifts, int n_segment, int padding_mode) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(torchshifts, Autograd, m) {
+    m.impl("temporal_shift", TORCH_FN(temporal_autograd));
+    m.impl("_temporal_shift_backward", TORCH_FN(temporal_autograd_backward));
     m.impl("_shift1d_fixed_backward", TORCH_FN(fixed_autograd_backward<1>));
     m.impl("_shift2d_fixed_backward", TORCH_FN(fixed_autograd_backward<2>));
     m.impl("_shift3d_fixed_backward", TORCH_FN(fixed_autograd_backward<3>));
@@ -969,6 +1083,8 @@ TORCH_LIBRARY_IMPL(torchshifts, CPU, m) {
 }
 
 TORCH_LIBRARY_IMPL(torchshifts, CUDA, m) {
+    m.impl("temporal_shift", TORCH_FN(temporal_forward_hip));
+    m.impl("_temporal_shift_backward", TORCH_FN(temporal_backward_hip));
     m.impl("_shift1d_fixed_backward", TORCH_FN(shift_fixed_backward_hip<1>));
     m.impl("_shift2d_fixed_backward", TORCH_FN(shift_fixed_backward_hip<2>));
     m.impl("_shift3d_fixed_backward", TORCH_FN(shift_fixed_backward_hip<3>));

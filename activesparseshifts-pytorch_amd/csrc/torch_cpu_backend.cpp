@@ -421,6 +421,47 @@ template <int ND> Tensor shift_fixed_pool_backward_cpu(const Tensor &grad, const
     return shift_fixed_backward_cpu<ND>(g, shifts, borders, input_size, padding_mode);
 }
 
+// ---- temporal shift: out[(n, t), c] = in[(n, pad(t - sign * s_c)), c], whole planes of `plane_bytes` bytes (any float type: a
+// plane is copied or zero-filled, and zero is all-zero bits) ---------------------------------------------------------------
+}  // namespace cpu
+void temporal_check(const at::Tensor &input, const at::Tensor &shifts, int64_t n_segment, int64_t padding_mode);   // torch_binding.cpp
+namespace cpu {
+
+Tensor temporal_gather_cpu(const Tensor &t_, const Tensor &shifts, int64_t T, int64_t padding_mode, int sign) {
+    TORCH_CHECK(t_.device().is_cpu() && shifts.device().is_cpu(), "temporal_shift_cpu: expected CPU tensors");
+    temporal_check(t_, shifts, T, padding_mode);
+    TORCH_CHECK(at::isFloatingType(t_.scalar_type()), "\"temporal_shift_cpu\" not implemented for '", c10::toString(t_.scalar_type()), "'");
+    const Tensor t = t_.contiguous();
+    Tensor out = at::empty(t.sizes(), t.options(), at::MemoryFormat::Contiguous);
+    if (t.numel() == 0) return out;
+    const int64_t C = t.size(1), N = t.size(0) / T;
+    const size_t plane_bytes = static_cast<size_t>(t.numel() / (t.size(0) * C)) * t.element_size();
+    // rint of the table (half to even), like the sparse shift's weights
+    const Tensor table = shifts.detach().reshape({C}).to(at::kDouble).round().to(at::kLong).contiguous();
+    const int64_t *s = table.data_ptr<int64_t>();
+    const char *src = static_cast<const char *>(t.data_ptr());
+    char *dst = static_cast<char *>(out.data_ptr());
+    at::parallel_for(0, N * T, 1, [&](int64_t begin, int64_t end) {
+        for (int64_t nt = begin; nt < end; ++nt) {
+            const int64_t n = nt / T, tt = nt % T;
+            for (int64_t c = 0; c < C; ++c) {
+                const int64_t ts = T == 1 ? 0 : pad_index(tt - sign * s[c], T, static_cast<int>(padding_mode));   // (a size-1 dim ignores its shift)
+                char *d = dst + static_cast<size_t>(nt * C + c) * plane_bytes;
+                if (ts < 0) std::memset(d, 0, plane_bytes);
+                else std::memcpy(d, src + static_cast<size_t>((n * T + ts) * C + c) * plane_bytes, plane_bytes);
+            }
+        }
+    });
+    return out;
+}
+
+Tensor temporal_forward_cpu(const Tensor &input, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    return temporal_gather_cpu(input, shifts, n_segment, padding_mode, +1);
+}
+Tensor temporal_backward_cpu(const Tensor &grad, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    return temporal_gather_cpu(grad, shifts, n_segment, padding_mode, -1);
+}
+
 template <int ND> Tensor qshift_forward_cpu(const Tensor &input, const Tensor &weights, const Tensor &borders,
                                             at::IntArrayRef new_size, int64_t padding_mode, bool /*active_flag*/) {
     TORCH_CHECK(input.is_quantized() && weights.is_quantized(), "q_shiftnd_cpu: expected quantized tensors");
@@ -459,6 +500,8 @@ std::tuple<Tensor, Tensor> qshift_backward_cpu(const Tensor &, const Tensor &, c
 using namespace torchshifts_amd::cpu;
 
 TORCH_LIBRARY_IMPL(torchshifts, CPU, m) {
+    m.impl("temporal_shift", TORCH_FN(temporal_forward_cpu));
+    m.impl("_temporal_shift_backward", TORCH_FN(temporal_backward_cpu));
     m.impl("_shift1d_forward", TORCH_FN(shift_forward_cpu<1>));
     m.impl("_shift1d_backward", TORCH_FN(shift_backward_cpu<1>));
     m.impl("_shift2d_forward", TORCH_FN(shift_forward_cpu<2>));

@@ -150,3 +150,32 @@ def shift3d_fixed_pool_func(input: Tensor, shifts: Tensor, padding_mode: int, po
     """Shift a [N, C, H, W, D] tensor by the integers of shifts [C, 3] (H, W, D), then avg_pool3d(kernel_size=pool, stride=pool, ceil_mode=True),
     as one op; pool: an int or 3 window sizes; borders [3, 2] = (cut_left, cut_right) per dim."""
     return _shift_fixed_func(3, input, shifts, padding_mode, borders, pool)
+
+
+# ---- temporal shift (TSM, arXiv 1811.08383): fixed shifts across the frames of a [N * n_segment, C, ...] tensor -----------------
+# Every run of n_segment consecutive rows of dim 0 is one clip; channel c of frame t becomes channel c of frame
+# pad(t - shifts[c]) of the same clip.  The result equals
+#   shift2d_fixed_func(x.view(N, T, C, M).permute(0, 2, 1, 3), stack([shifts, 0], 1), padding_mode).permute(0, 2, 1, 3).reshape(x.shape)
+# without either layout change: on HIP tensors one pass that copies or zero-fills whole frames' channel planes, forward and
+# backward.  The autograd node keeps the table alone.  `shifts`: [n_channels] (or [n_channels, 1]) integers, or floats that hold
+# integers.  Nothing validates a float table: an entry that is not an integer is rounded half to even, like the sparse shift's
+# weights and the tables of shift{N}d_fixed_func.  On HIP tensors the table is converted to the input's dtype, like those tables:
+# exact for |shift| <= 256 in bfloat16 and <= 2048 in float16 (clips of more frames than that in a 16-bit tensor, or larger shifts
+# under periodic / reflect / symmetric padding, would be rounded; the CPU op uses the integers as they are).
+def temporal_shift_func(input: Tensor, shifts: Tensor, n_segment: int, padding_mode: int = 0) -> Tensor:
+    """Shift the channels of a [N * n_segment, C, ...] tensor (2 to 5 dims) across the n_segment frames of each clip."""
+    name = "temporal_shift_func()"
+    _assert_has_ops()
+    assert padding_mode in [0, 1, 2, 3, 4], f"{name} expected padding_mode can be {_PADDING_DOC}"
+    assert 2 <= len(input.shape) <= 5, f"{name}: expected a 2D to 5D tensor as input, but it is shape is {input.shape}"
+    assert isinstance(n_segment, int) and n_segment >= 1 and input.shape[0] % n_segment == 0, \
+        f"{name}: expected dim 0 of the input ({input.shape[0]}) to be a multiple of n_segment ({n_segment})"
+    assert len(shifts.shape) == 1 or (len(shifts.shape) == 2 and shifts.shape[1] == 1), \
+        f"{name}: expected [n_channels] tensor as shifts, but it is shape is {shifts.shape}"
+    assert input.shape[1] == shifts.shape[0], \
+        (f"{name}: expected that input and shifts have equal number of channels, but input have "
+         f"{input.shape[1]} and shifts have {shifts.shape[0]} channels.")
+    assert input.device == shifts.device, \
+        (f"{name}: expected input and shifts to be on same device, but input is  on {input.device} "
+         f"and shifts is on {shifts.device}")
+    return torch.ops.torchshifts.temporal_shift(input, shifts, n_segment, padding_mode)

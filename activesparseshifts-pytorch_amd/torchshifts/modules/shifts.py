@@ -13,7 +13,7 @@ from torch import nn
 
 from torchshifts.functional import (shift1d_fixed_func, shift1d_fixed_pool_func, shift1d_func, shift1d_pool_func, shift2d_fixed_func,
                                     shift2d_fixed_pool_func, shift2d_func, shift2d_pool_func, shift3d_fixed_func,
-                                    shift3d_fixed_pool_func, shift3d_func, shift3d_pool_func)
+                                    shift3d_fixed_pool_func, shift3d_func, shift3d_pool_func, temporal_shift_func)
 
 paddings_dict = {'zeros': 0, 'border': 1, 'periodic': 2, 'reflect': 3, 'symmetric': 4}
 
@@ -281,3 +281,55 @@ class GroupedShift2d(_GroupedShiftnd):
 class GroupedShift3d(_GroupedShiftnd):
     """Fixed per-channel (H, W, D) shift of a [N, C, H, W, D] tensor.  forward(x) -> (out, None)."""
     dim = 3
+
+
+class TemporalShift(nn.Module):
+    """Temporal Shift Module (arXiv 1811.08383): fixed shifts across the frames of a [N * n_segment, C, ...] tensor, nothing to
+    learn.  The table is the persistent buffer `shifts` (int64 [in_channels]): channel c of frame t becomes channel c of frame
+    t - shifts[c] of the same clip.  It travels in state_dict and with .to(device); the module has no parameters, and the autograd
+    node keeps the table alone.
+
+    Arguments:
+        n_segment (int): frames per clip, T.
+        in_channels (int): channels of the input.
+        fold_div (int): the default table moves the first in_channels // fold_div channels one frame back (shift -1: frame t
+            shows frame t + 1), the next in_channels // fold_div one frame forward (+1) and leaves the rest. Default 8.
+        shifts (tensor / list): [in_channels] integers that replace the default table (fold_div is then unused); floats are
+            rounded half to even, not validated.  On HIP tensors |shift| <= 256 is exact in bfloat16, <= 2048 in float16.
+        padding (str): 'zeros' | 'border' | 'periodic' | 'reflect' | 'symmetric'. Default 'zeros' (the published module).
+    forward(x) -> output, the tensor alone: the module sits inside nn.Sequential in front of a convolution.
+    """
+
+    def __init__(self, n_segment, in_channels, fold_div=8, shifts=None, padding='zeros'):
+        super().__init__()
+        assert padding.lower() in paddings_dict.keys(), f'incorrect padding option: {padding}'
+        assert int(n_segment) >= 1, 'n_segment must be >= 1'
+        self.padding = paddings_dict[padding.lower()]
+        self.n_segment = int(n_segment)
+        self.in_channels = in_channels
+        self.fold_div = int(fold_div)
+        if shifts is None:
+            table = self.default_table(in_channels, self.fold_div)
+        else:
+            table = torch.as_tensor(shifts)
+            assert tuple(table.shape) == (in_channels,), f'shifts must have shape [{in_channels}]'
+            if table.is_floating_point():
+                table = torch.round(table)
+            table = table.detach().to(torch.int64).clone()
+        self.register_buffer('shifts', table, persistent=True)
+
+    @staticmethod
+    def default_table(in_channels, fold_div):
+        fold = in_channels // fold_div
+        table = torch.zeros(in_channels, dtype=torch.int64)
+        table[:fold] = -1
+        table[fold:2 * fold] = 1
+        return table
+
+    def forward(self, input):
+        return temporal_shift_func(input, self.shifts, self.n_segment, self.padding)
+
+    def extra_repr(self):
+        pad = {v: k for k, v in paddings_dict.items()}[self.padding]
+        return (f'n_segment={self.n_segment}, in_channels={self.in_channels}, fold_div={self.fold_div}, padding_method={pad}, '
+                'fixed integer shifts')

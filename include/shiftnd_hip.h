@@ -180,6 +180,16 @@ SHIFTND_API int shiftnd_backward_serves_channels_last(const shiftnd_problem *p, 
 /*
  * Forward, float dtypes (F32, F64, F16, BF16; F16 / BF16 also with SHIFTND_WEIGHTS_F32).
  * out has sizes {N, C, r_i-l_i, r_j-l_j, r_k-l_k}; out_strides are its element strides.
+ *
+ * Segment-major tensors: x and out in memory order N, S0, C, S1, S2 -- the first spatial dim OUTSIDE the channel dim, i.e. dense
+ * strides {S0*C*inner, inner, C*inner, [S2,] 1} with inner = the product of the spatial sizes after the first.  That is a video
+ * tensor [N*T, C, H, W] seen as the problem {ndim 2, sizes N, C, T, H*W} with strides {T*C*M, M, C*M, 1}: a shift of column 0 moves
+ * channels across the T frames of a clip (the Temporal Shift Module).  A sparse shift (active == 0) of float tensors in this layout,
+ * whole window, ndim >= 2, C > 1, S0 > 1, same layout on both sides, under 2^32 bytes, is served at copy rate by the kernels of
+ * csrc/shiftnd_segment.hip (shiftnd_last_kernel: segment_forward for planes of whole 16-byte pieces at 16-byte-aligned bases,
+ * segment_forward_ragged otherwise; SHIFTND_PATH_PLANE), for any [C, ndim] table -- planes whose channel also shifts an inner dim are
+ * gathered element by element inside the same kernel.  So is shiftnd_backward's x == NULL form on such strides (whole window).  Every
+ * other call with these strides keeps the strided kernels.
  */
 SHIFTND_API int shiftnd_forward(const shiftnd_problem *p,
                     const void *x, const int64_t x_strides[5],

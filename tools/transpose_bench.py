@@ -22,7 +22,9 @@ def ev(fn, it=10):
 
 
 for shape, dt in [((16, 256, 224, 224), torch.float32), ((64, 512, 224, 224), torch.float16), ((128, 512, 56, 56), torch.uint8),
-                  ((8, 128, 16, 112, 112), torch.bfloat16), ((3, 70, 13, 9), torch.float32), ((2, 5, 7, 3), torch.int8)]:
+                  ((8, 128, 16, 112, 112), torch.bfloat16), ((3, 70, 13, 9), torch.float32), ((2, 5, 7, 3), torch.int8),
+                  # 8-byte elements (one kernel for both forms): whole pieces, ragged rows, a few workgroups
+                  ((16, 256, 112, 112), torch.float64), ((16, 250, 55, 55), torch.float64), ((3, 70, 13, 9), torch.float64)]:
     x = (torch.rand(shape, device="cuda") * 100).to(dt)
     fmt = torch.channels_last if len(shape) == 4 else torch.channels_last_3d
     xc = x.contiguous(memory_format=fmt)
