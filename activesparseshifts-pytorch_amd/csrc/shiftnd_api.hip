@@ -267,6 +267,61 @@ int forward_common(const shiftnd_problem *p, const void *x, const int64_t *xs, c
     return finish(strided_forward(g, p->dtype, x, w, wkind, wzp, fill, out, st));
 }
 
+// ---- SHIFTND_SHIFT_DIM0: the learnable temporal shift (shiftnd_tshift.hip).  `weights` / `grad_w` are [C] arrays and the shift acts
+// on spatial dim 0 of dense segment-major tensors.  No routing and no fallback: the call is served by the tshift kernels or refused
+// before anything is launched.  -> the problem without the flag bits in `q`, the weights' type in `wkind`
+int tshift_problem(const shiftnd_problem *p, shiftnd_problem &q, int &wkind) {
+    shiftnd_problem r = *p;
+    r.dtype = p->dtype & ~SHIFTND_SHIFT_DIM0;
+    if (split_dtype(&r, q, wkind) != SHIFTND_OK || !is_float_dtype(q.dtype)) return SHIFTND_ERR_UNSUPPORTED_DTYPE;
+    return SHIFTND_OK;
+}
+
+int tshift_forward_call(const shiftnd_problem *p, const void *x, const int64_t *xs, const void *w, void *out, const int64_t *os,
+                        void *stream) {
+    shiftnd_problem q;
+    int wkind;
+    int rc = tshift_problem(p, q, wkind);
+    if (rc != SHIFTND_OK) return rc;
+    Geometry g;
+    rc = build_geometry(&q, xs, os, nullptr, g);
+    if (rc != SHIFTND_OK) return rc;
+    if (!tshift_geometry_ok(g, q.dtype)) return SHIFTND_ERR_INVALID_ARGUMENT;
+    if (empty_problem(g)) {
+        g_last_path = SHIFTND_PATH_EMPTY;
+        return SHIFTND_OK;
+    }
+    if (!x || !w || !out) return SHIFTND_ERR_INVALID_ARGUMENT;
+    if (!tshift_tensor_ok(g, q.dtype, x, g.xs) || !tshift_tensor_ok(g, q.dtype, out, g.os)) return SHIFTND_ERR_INVALID_ARGUMENT;
+    g_last_path = SHIFTND_PATH_PLANE;
+    return finish(tshift_forward(g, q.dtype, x, w, wkind, out, static_cast<hipStream_t>(stream)));
+}
+
+int tshift_backward_call(const shiftnd_problem *p, const void *go, const int64_t *gos, const void *x, const int64_t *xs, const void *w,
+                         void *gx, const int64_t *gxs, void *gw, void *workspace, size_t workspace_bytes, void *stream) {
+    shiftnd_problem q;
+    int wkind;
+    int rc = tshift_problem(p, q, wkind);
+    if (rc != SHIFTND_OK) return rc;
+    if (!x || !xs || !gw) return SHIFTND_ERR_INVALID_ARGUMENT;   // (the x == NULL form does not exist under the flag)
+    Geometry g;
+    rc = build_geometry(&q, xs, gos, gxs, g);
+    if (rc != SHIFTND_OK) return rc;
+    if (!tshift_geometry_ok(g, q.dtype)) return SHIFTND_ERR_INVALID_ARGUMENT;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (g.N == 0 || g.C == 0 || g.S[0] * g.S[1] * g.S[2] == 0) {
+        g_last_path = SHIFTND_PATH_EMPTY;
+        if (g.C > 0 && hipMemsetAsync(gw, 0, static_cast<size_t>(g.C) * dtype_size(wkind), st) != hipSuccess) return SHIFTND_ERR_LAUNCH_FAILED;
+        return SHIFTND_OK;
+    }
+    if (!go || !w || !gx || !workspace) return SHIFTND_ERR_INVALID_ARGUMENT;
+    if (!tshift_tensor_ok(g, q.dtype, go, g.os) || !tshift_tensor_ok(g, q.dtype, x, g.xs) || !tshift_tensor_ok(g, q.dtype, gx, g.gs))
+        return SHIFTND_ERR_INVALID_ARGUMENT;
+    if (tshift_backward_workspace(g, q.dtype) > workspace_bytes) return SHIFTND_ERR_WORKSPACE_TOO_SMALL;
+    g_last_path = SHIFTND_PATH_PLANE;
+    return finish(tshift_backward(g, q.dtype, go, x, w, wkind, gx, gw, workspace, st));
+}
+
 }  // namespace
 
 namespace shiftnd {
@@ -387,6 +442,7 @@ int shiftnd_backward_serves_channels_last(const shiftnd_problem *p, const void *
 int shiftnd_forward(const shiftnd_problem *p, const void *x, const int64_t x_strides[5], const void *weights, void *out,
                     const int64_t out_strides[5], void *stream) {
     if (!p || !x_strides || !out_strides) return SHIFTND_ERR_INVALID_ARGUMENT;
+    if (p->dtype & SHIFTND_SHIFT_DIM0) return tshift_forward_call(p, x, x_strides, weights, out, out_strides, stream);
     shiftnd_problem q;
     int wkind;
     if (split_dtype(p, q, wkind) != SHIFTND_OK || !is_float_dtype(q.dtype)) return SHIFTND_ERR_UNSUPPORTED_DTYPE;
@@ -426,6 +482,14 @@ size_t shiftnd_backward_workspace_bytes(const shiftnd_problem *p) {
     if (!p) return 0;
     shiftnd_problem q;
     int wkind;
+    if (p->dtype & SHIFTND_SHIFT_DIM0) {   // the walk's plan alone: no other family runs under the flag, no knob shapes it
+        const int64_t unit[5] = {0, 0, 0, 0, 0};
+        Geometry g;
+        if (tshift_problem(p, q, wkind) != SHIFTND_OK || build_geometry(&q, unit, unit, unit, g) != SHIFTND_OK) return 0;
+        if (!tshift_geometry_ok(g, q.dtype)) return 0;
+        if (g.N == 0 || g.C == 0 || g.S[0] * g.S[1] * g.S[2] == 0) return sizeof(double);
+        return tshift_backward_workspace(g, q.dtype);
+    }
     if (split_dtype(p, q, wkind) != SHIFTND_OK) return 0;
     p = &q;   // (the records are fp64 whatever the weights are: the same bytes with and without SHIFTND_WEIGHTS_F32)
     // the layout of the partial-sum buffer depends only on the geometry: evaluate every family's plan
@@ -448,6 +512,11 @@ static int backward_planned(const shiftnd_problem *p, const void *grad_out, cons
 int shiftnd_backward(const shiftnd_problem *p, const void *grad_out, const int64_t grad_out_strides[5], const void *x,
                      const int64_t x_strides[5], const void *weights, void *grad_x, const int64_t grad_x_strides[5],
                      void *grad_w, void *workspace, size_t workspace_bytes, void *stream) {
+    if (p && (p->dtype & SHIFTND_SHIFT_DIM0)) {
+        if (!grad_out_strides || !grad_x_strides) return SHIFTND_ERR_INVALID_ARGUMENT;
+        return tshift_backward_call(p, grad_out, grad_out_strides, x, x_strides, weights, grad_x, grad_x_strides, grad_w, workspace,
+                                    workspace_bytes, stream);
+    }
     int rc = backward_planned(p, grad_out, grad_out_strides, x, x_strides, weights, grad_x, grad_x_strides, grad_w, workspace,
                               workspace_bytes, stream);
     if (rc == SHIFTND_ERR_WORKSPACE_TOO_SMALL && knobs_touched()) {

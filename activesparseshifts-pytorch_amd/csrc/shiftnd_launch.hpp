@@ -219,6 +219,16 @@ int gradx_gather(const Geometry &g, int dtype, const void *go, const void *w, vo
 bool segment_forward_eligible(const Geometry &g, int dtype, const void *x, const void *out);
 int segment_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, void *out, hipStream_t st);
 
+// ---- the learnable temporal shift (shiftnd_tshift.hip; SHIFTND_SHIFT_DIM0): a 1-D sparse / interpolating shift along S0 of
+// segment-major float tensors, `w` and `gw` [C] arrays, whole window.  tshift_geometry_ok: the sizes; tshift_tensor_ok: one tensor's
+// base and strides (normalised order).  No fallback: C, S0 or planes of size 1 are served too.
+bool tshift_geometry_ok(const Geometry &g, int dtype);
+bool tshift_tensor_ok(const Geometry &g, int dtype, const void *p, const int64_t *strides);
+int tshift_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, void *out, hipStream_t st);
+size_t tshift_backward_workspace(const Geometry &g, int dtype);
+int tshift_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw,
+                    void *workspace, hipStream_t st);
+
 // ---- layout change (shiftnd_transpose.hip): dst[n][c][r] = src[n][r][c], dense tensors ---------------------------
 int transpose_planes(const void *src, void *dst, int64_t N, int64_t rows, int64_t cols, int esize, hipStream_t st);
 

@@ -157,13 +157,16 @@ __global__ __launch_bounds__(kThreads) void strided_active_forward(Geometry g, c
 }
 
 // backward: one workgroup per (n, c) plane ---------------------------------------------------------
-template <typename T, int ND, bool ACTIVE>
+// (ACTIVE is launch-uniform and a run-time argument: one kernel per type and ND instead of two -- nothing routes here by default,
+// and the 12 kernels saved pay for shiftnd_tshift.hip's)
+template <typename T, int ND>
 __global__ __launch_bounds__(kThreads) void strided_backward(Geometry g, const typename T::S *__restrict__ go,
                                                              const typename T::S *__restrict__ x,
                                                              const void *__restrict__ w, int wkind,
                                                              typename T::S *__restrict__ gx,
                                                              double *__restrict__ partials) {
     using CT = typename T::C;
+    const bool ACTIVE = g.active != 0;
     __shared__ double scratch[kThreads / 64];
     const int64_t plane = blockIdx.x;
     const int64_t c = plane % g.C, n = plane / g.C;
@@ -231,14 +234,8 @@ int launch_strided_backward_nd(const Geometry &g, const void *go, const void *x,
     using S = typename T::S;
     const int64_t planes = g.N * g.C;
     if (planes > 0x7fffffffLL) return SHIFTND_ERR_TOO_LARGE;
-    if (g.active)
-        hipLaunchKernelGGL((strided_backward<T, ND, true>), dim3(static_cast<unsigned>(planes)), dim3(kThreads), 0, st, g,
-                           static_cast<const S *>(go), static_cast<const S *>(x), w, wkind,
-                           static_cast<S *>(gx), partials);
-    else
-        hipLaunchKernelGGL((strided_backward<T, ND, false>), dim3(static_cast<unsigned>(planes)), dim3(kThreads), 0, st, g,
-                           static_cast<const S *>(go), static_cast<const S *>(x), w, wkind,
-                           static_cast<S *>(gx), partials);
+    hipLaunchKernelGGL((strided_backward<T, ND>), dim3(static_cast<unsigned>(planes)), dim3(kThreads), 0, st, g,
+                       static_cast<const S *>(go), static_cast<const S *>(x), w, wkind, static_cast<S *>(gx), partials);
     launch_reduce_weight_grads(wkind, partials, static_cast<int>(g.N), static_cast<int>(g.C), g.nd, gw, st);
     return SHIFTND_OK;
 }

@@ -1000,6 +1000,181 @@ Tensor temporal_backward_hip(const Tensor &grad, const Tensor &shifts, int64_t n
     return temporal_hip(grad, shifts, n_segment, padding_mode, true);
 }
 
+// ---- learnable temporal shift: a TRAINED per-channel shift across the frames of [N*T, C, ...] ------------------------------------
+// temporal_shift_learnable(input, weights, n_segment, padding_mode, active_flag) ==
+//     shift1d(x.view(N, T, C, M).permute(0, 3, 2, 1).reshape(N*M, C, T), weights.view(C, 1), padding_mode, active_flag)
+//         .view(N, M, C, T).permute(0, 3, 2, 1).reshape(x.shape)
+// and its gradients are that expression's.  The CPU key is literally that, on the CPU 1-D ops; on HIP tensors forward and backward
+// are ONE shiftnd_forward / shiftnd_backward call each under SHIFTND_SHIFT_DIM0 on the strides {T*C*M, M, C*M, 1}
+// (shiftnd_tshift.hip): no layout change, no table.  The autograd node keeps the input and the weights.
+using tsl_forward_sig = Tensor(const Tensor &, const Tensor &, int64_t, int64_t, bool);
+using tsl_backward_sig = std::tuple<Tensor, Tensor>(const Tensor &, const Tensor &, const Tensor &, int64_t, int64_t, bool);
+Tensor call_tsl_forward(const Tensor &input, const Tensor &weights, int64_t n_segment, int64_t padding_mode, bool active_flag) {
+    static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("torchshifts::_temporal_shift_learnable_forward", "").typed<tsl_forward_sig>();
+    return op.call(input, weights, n_segment, padding_mode, active_flag);
+}
+std::tuple<Tensor, Tensor> call_tsl_backward(const Tensor &grad, const Tensor &weights, const Tensor &input, int64_t n_segment,
+                                             int64_t padding_mode, bool active_flag) {
+    static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("torchshifts::_temporal_shift_learnable_backward", "").typed<tsl_backward_sig>();
+    return op.call(grad, weights, input, n_segment, padding_mode, active_flag);
+}
+
+void tsl_check(const Tensor &input, const Tensor &weights, int64_t n_segment, int64_t padding_mode) {
+    TORCH_CHECK(!input.is_quantized(), "temporal_shift_learnable: quantized inputs are not supported");
+    TORCH_CHECK(input.dim() >= 2 && input.dim() <= 5, "temporal_shift_learnable: expected a [N*T, C, ...] tensor of 2 to 5 dims");
+    TORCH_CHECK(n_segment >= 1 && input.size(0) % n_segment == 0, "temporal_shift_learnable: dim 0 (", input.size(0),
+                ") must be a multiple of n_segment (", n_segment, ")");
+    TORCH_CHECK((weights.dim() == 1 || (weights.dim() == 2 && weights.size(1) == 1)) && weights.size(0) == input.size(1),
+                "temporal_shift_learnable: weights must have shape [C] or [C, 1]");
+    TORCH_CHECK(weights.device() == input.device(), "temporal_shift_learnable: weights must be on the input's device");
+    TORCH_CHECK(at::isFloatingType(weights.scalar_type()), "temporal_shift_learnable: weights must be floats");
+    TORCH_CHECK(padding_mode >= 0 && padding_mode <= 4, "temporal_shift_learnable: padding_mode must be 0..4");
+}
+
+Tensor tsl_public(const Tensor &input, const Tensor &weights, int64_t n_segment, int64_t padding_mode, bool active_flag) {
+    tsl_check(input, weights, n_segment, padding_mode);
+    return call_tsl_forward(input, weights, n_segment, padding_mode, active_flag);
+}
+
+struct LearnableTemporalShiftFunction : public torch::autograd::Function<LearnableTemporalShiftFunction> {
+    static variable_list forward(AutogradContext *ctx, const Tensor &input, const Tensor &weights, int64_t n_segment,
+                                 int64_t padding_mode, bool active_flag) {
+        at::AutoDispatchBelowADInplaceOrView guard;
+        auto output = call_tsl_forward(input, weights, n_segment, padding_mode, active_flag);
+        ctx->saved_data["n_segment"] = n_segment;
+        ctx->saved_data["padding_mode"] = padding_mode;
+        ctx->saved_data["active_flag"] = active_flag;
+        ctx->save_for_backward({input, weights});
+        return {output};
+    }
+    static variable_list backward(AutogradContext *ctx, const variable_list &grad_output) {
+        auto saved = ctx->get_saved_variables();
+        auto result = call_tsl_backward(grad_output[0], saved[1], saved[0], ctx->saved_data["n_segment"].toInt(),
+                                        ctx->saved_data["padding_mode"].toInt(), ctx->saved_data["active_flag"].toBool());
+        return {std::get<0>(result), std::get<1>(result), Tensor(), Tensor(), Tensor()};
+    }
+};
+
+struct LearnableTemporalShiftBackwardFunction : public torch::autograd::Function<LearnableTemporalShiftBackwardFunction> {
+    static variable_list forward(AutogradContext *ctx, const Tensor &grad, const Tensor &weights, const Tensor &input,
+                                 int64_t n_segment, int64_t padding_mode, bool active_flag) {
+        at::AutoDispatchBelowADInplaceOrView guard;
+        auto result = call_tsl_backward(grad, weights, input, n_segment, padding_mode, active_flag);
+        return {std::get<0>(result), std::get<1>(result)};
+    }
+    static variable_list backward(AutogradContext *, const variable_list &) {
+        TORCH_CHECK(0, "double backwards on temporal_shift_learnable not supported");
+    }
+};
+
+Tensor tsl_autograd(const Tensor &input, const Tensor &weights, int64_t n_segment, int64_t padding_mode, bool active_flag) {
+    tsl_check(input, weights, n_segment, padding_mode);
+    return LearnableTemporalShiftFunction::apply(input, weights, n_segment, padding_mode, active_flag)[0];
+}
+std::tuple<Tensor, Tensor> tsl_autograd_backward(const Tensor &grad, const Tensor &weights, const Tensor &input, int64_t n_segment,
+                                                 int64_t padding_mode, bool active_flag) {
+    tsl_check(input, weights, n_segment, padding_mode);
+    auto result = LearnableTemporalShiftBackwardFunction::apply(grad, weights, input, n_segment, padding_mode, active_flag);
+    return std::make_tuple(result[0], result[1]);
+}
+
+// CPU tensors: the definition, on the CPU key's 1-D forward / backward (torch_cpu_backend.cpp) for the dtypes they take
+Tensor tsl_lines(const Tensor &t, int64_t T) {   // [N*T, C, ...] -> [N*M, C, T], contiguous
+    const int64_t C = t.size(1), N = t.size(0) / T, M = t.numel() / (t.size(0) * C);
+    return t.contiguous().view({N, T, C, M}).permute({0, 3, 2, 1}).reshape({N * M, C, T});
+}
+Tensor tsl_frames(const Tensor &lines, at::IntArrayRef sizes, int64_t T) {   // ... and back
+    const int64_t C = sizes[1], N = sizes[0] / T, M = lines.size(0) / N;
+    return lines.view({N, M, C, T}).permute({0, 3, 2, 1}).reshape(sizes);
+}
+Tensor tsl_borders(int64_t T) {
+    Tensor b = at::empty({6}, at::TensorOptions().dtype(at::kInt).device(at::kCPU));
+    const int32_t v[6] = {0, static_cast<int32_t>(T), 0, 1, 0, 1};
+    for (int i = 0; i < 6; ++i) b.data_ptr<int32_t>()[i] = v[i];
+    return b;
+}
+
+Tensor tsl_forward_cpu(const Tensor &input, const Tensor &weights, int64_t n_segment, int64_t padding_mode, bool active_flag) {
+    TORCH_CHECK(input.device().is_cpu() && weights.device().is_cpu(), "temporal_shift_learnable_cpu: expected CPU tensors");
+    tsl_check(input, weights, n_segment, padding_mode);
+    if (input.numel() == 0) return at::empty(input.sizes(), input.options(), at::MemoryFormat::Contiguous);
+    const Tensor lines = tsl_lines(input, n_segment);
+    const Tensor out = call_forward<1>(lines, weights.reshape({input.size(1), 1}), tsl_borders(n_segment), lines.sizes(), padding_mode,
+                                       active_flag);
+    return tsl_frames(out, input.sizes(), n_segment);
+}
+
+std::tuple<Tensor, Tensor> tsl_backward_cpu(const Tensor &grad, const Tensor &weights, const Tensor &input, int64_t n_segment,
+                                            int64_t padding_mode, bool active_flag) {
+    TORCH_CHECK(grad.device().is_cpu() && input.device().is_cpu() && weights.device().is_cpu(),
+                "temporal_shift_learnable_cpu: expected CPU tensors");
+    tsl_check(input, weights, n_segment, padding_mode);
+    TORCH_CHECK(grad.sizes() == input.sizes(), "temporal_shift_learnable backward: grad does not match the input");
+    if (input.numel() == 0)
+        return std::make_tuple(at::empty(input.sizes(), input.options(), at::MemoryFormat::Contiguous), at::zeros_like(weights));
+    auto result = call_backward<1>(tsl_lines(grad, n_segment), weights.reshape({input.size(1), 1}), tsl_lines(input, n_segment),
+                                   tsl_borders(n_segment), padding_mode, active_flag);
+    return std::make_tuple(tsl_frames(std::get<0>(result), input.sizes(), n_segment), std::get<1>(result).reshape(weights.sizes()));
+}
+
+// HIP tensors: one flagged C-ABI call on the segment-major strides
+void tsl_problem(shiftnd_problem &p, int64_t st[5], const Tensor &t, int64_t T, int64_t padding_mode, bool active_flag, int dtype) {
+    const int64_t C = t.size(1), N = t.size(0) / T, M = t.numel() / (t.size(0) * C);
+    TORCH_CHECK(T <= INT32_MAX && M <= INT32_MAX, "temporal_shift_learnable: n_segment and the frame size must fit 32 bits");
+    p.ndim = 2;
+    p.dtype = dtype | SHIFTND_SHIFT_DIM0;
+    p.padding_mode = static_cast<int32_t>(padding_mode);
+    p.active = active_flag ? 1 : 0;
+    const int64_t sizes[5] = {N, C, T, M, 1};
+    const int32_t borders[6] = {0, static_cast<int32_t>(T), 0, static_cast<int32_t>(M), 0, 1};
+    const int64_t strides[5] = {T * C * M, M, C * M, 1, 0};
+    for (int i = 0; i < 5; ++i) p.sizes[i] = sizes[i], st[i] = strides[i];
+    for (int i = 0; i < 6; ++i) p.borders[i] = borders[i];
+}
+
+Tensor tsl_forward_hip(const Tensor &input_, const Tensor &weights, int64_t n_segment, int64_t padding_mode, bool active_flag) {
+    TORCH_CHECK(input_.is_cuda(), "temporal_shift_learnable: expected a CUDA tensor");
+    tsl_check(input_, weights, n_segment, padding_mode);
+    const int mixed = weights_flag("temporal_shift_learnable_cuda", input_, "input", weights);
+    c10::DeviceGuard device_guard(input_.device());
+    const int dtype = to_shiftnd_dtype(input_.scalar_type(), "temporal_shift_learnable_cuda") | mixed;
+    const Tensor input = input_.contiguous();
+    Tensor output = at::empty(input.sizes(), input.options(), at::MemoryFormat::Contiguous);
+    if (input.numel() == 0) return output;
+    const Tensor w = weights.contiguous();
+    shiftnd_problem p;
+    int64_t st[5];
+    tsl_problem(p, st, input, n_segment, padding_mode, active_flag, dtype);
+    const int rc = shiftnd_forward(&p, input.data_ptr(), st, w.data_ptr(), output.data_ptr(), st, current_stream(input));
+    TORCH_CHECK(rc == SHIFTND_OK, "temporal_shift_learnable (HIP): ", shiftnd_status_string(rc));
+    return output;
+}
+
+std::tuple<Tensor, Tensor> tsl_backward_hip(const Tensor &grad_, const Tensor &weights, const Tensor &input_, int64_t n_segment,
+                                            int64_t padding_mode, bool active_flag) {
+    TORCH_CHECK(grad_.is_cuda() && input_.is_cuda(), "temporal_shift_learnable: expected CUDA tensors");
+    tsl_check(input_, weights, n_segment, padding_mode);
+    check_same("temporal_shift_learnable_backward_cuda", grad_, "grad", input_, "input");
+    const int mixed = weights_flag("temporal_shift_learnable_backward_cuda", grad_, "grad", weights);
+    TORCH_CHECK(grad_.sizes() == input_.sizes(), "temporal_shift_learnable backward: grad does not match the input");
+    c10::DeviceGuard device_guard(grad_.device());
+    const int dtype = to_shiftnd_dtype(grad_.scalar_type(), "temporal_shift_learnable_backward_cuda") | mixed;
+    const Tensor input = input_.contiguous(), grad = grad_.contiguous();
+    const Tensor w = weights.contiguous();
+    Tensor grad_input = at::empty(input.sizes(), input.options(), at::MemoryFormat::Contiguous);
+    Tensor grad_weights = at::empty_like(w, at::MemoryFormat::Contiguous);   // (the weights' dtype: fp32 for a mixed call)
+    if (input.numel() == 0) return std::make_tuple(grad_input, grad_weights.zero_());
+    shiftnd_problem p;
+    int64_t st[5];
+    tsl_problem(p, st, input, n_segment, padding_mode, active_flag, dtype);
+    const size_t ws_bytes = shiftnd_backward_workspace_bytes(&p);
+    Tensor workspace = at::empty({static_cast<int64_t>(ws_bytes)}, input.options().dtype(at::kByte));
+    const int rc = shiftnd_backward(&p, grad.data_ptr(), st, input.data_ptr(), st, w.data_ptr(), grad_input.data_ptr(), st,
+                                    grad_weights.data_ptr(), workspace.data_ptr(), ws_bytes, current_stream(grad));
+    TORCH_CHECK(rc == SHIFTND_OK, "temporal_shift_learnable backward (HIP): ", shiftnd_status_string(rc));
+    return std::make_tuple(grad_input, grad_weights);
+}
+
 int64_t cuda_version() { return -1; }  // no CUDA toolkit: extension.py only compares when torch.version.cuda is set
 int64_t hip_version() { return HIP_VERSION; }
 
@@ -1047,9 +1222,15 @@ TORCH_LIBRARY(torchshifts, m) {
     // temporal shift (TSM): fixed shifts across the frames of [N*T, C, ...] (not in the reference)
     m.def("torchshifts::temporal_shift(Tensor input, Tensor shifts, int n_segment, int padding_mode) -> Tensor");
     m.def("torchshifts::_temporal_shift_backward(Tensor grad, Tensor shifts, int n_segment, int padding_mode) -> Tensor");
+    // learnable temporal shift: a trained per-channel shift across the frames, sparse or interpolating (not in the reference)
+    m.def("torchshifts::temporal_shift_learnable(Tensor input, Tensor weights, int n_segment, int padding_mode, bool active_flag) -> Tensor", &tsl_public);
+    m.def("torchshifts::_temporal_shift_learnable_forward(Tensor input, Tensor weights, int n_segment, int padding_mode, bool active_flag) -> Tensor");
+    m.def("torchshifts::_temporal_shift_learnable_backward(Tensor grad, Tensor weights, Tensor input, int n_segment, int padding_mode, bool active_flag) -> (Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(torchshifts, Autograd, m) {
+    m.impl("_temporal_shift_learnable_forward", TORCH_FN(tsl_autograd));
+    m.impl("_temporal_shift_learnable_backward", TORCH_FN(tsl_autograd_backward));
     m.impl("temporal_shift", TORCH_FN(temporal_autograd));
     m.impl("_temporal_shift_backward", TORCH_FN(temporal_autograd_backward));
     m.impl("_shift1d_fixed_backward", TORCH_FN(fixed_autograd_backward<1>));
@@ -1074,6 +1255,8 @@ TORCH_LIBRARY_IMPL(torchshifts, Autograd, m) {
 
 // CPU tensors: the reference's two-step sequence (shift op on the CPU key, then ATen's pool)
 TORCH_LIBRARY_IMPL(torchshifts, CPU, m) {
+    m.impl("_temporal_shift_learnable_forward", TORCH_FN(tsl_forward_cpu));
+    m.impl("_temporal_shift_learnable_backward", TORCH_FN(tsl_backward_cpu));
     m.impl("_shift1d_pool_forward", TORCH_FN(pool_forward_composed<1>));
     m.impl("_shift1d_pool_backward", TORCH_FN(pool_backward_composed<1>));
     m.impl("_shift2d_pool_forward", TORCH_FN(pool_forward_composed<2>));
@@ -1083,6 +1266,8 @@ TORCH_LIBRARY_IMPL(torchshifts, CPU, m) {
 }
 
 TORCH_LIBRARY_IMPL(torchshifts, CUDA, m) {
+    m.impl("_temporal_shift_learnable_forward", TORCH_FN(tsl_forward_hip));
+    m.impl("_temporal_shift_learnable_backward", TORCH_FN(tsl_backward_hip));
     m.impl("temporal_shift", TORCH_FN(temporal_forward_hip));
     m.impl("_temporal_shift_backward", TORCH_FN(temporal_backward_hip));
     m.impl("_shift1d_fixed_backward", TORCH_FN(shift_fixed_backward_hip<1>));

@@ -15,6 +15,7 @@ _LIB_PATH = os.environ.get("SHIFTND_HIP_LIB") or os.path.join(os.path.dirname(os
 
 F32, F64, F16, BF16, I8, U8, I32 = range(7)
 WEIGHTS_F32 = 0x100   # SHIFTND_WEIGHTS_F32: OR-ed onto F16 / BF16 -- fp32 weights (and grad_w) with 16-bit tensors
+SHIFT_DIM0 = 0x200    # SHIFTND_SHIFT_DIM0: weights / grad_w are [C]; a 1-D shift along spatial dim 0 of segment-major tensors
 PATH_NONE, PATH_EMPTY, PATH_PLANE, PATH_STRIDED, PATH_SWEEP, PATH_CL = range(6)
 
 DTYPES = {torch.float32: F32, torch.float64: F64, torch.float16: F16, torch.bfloat16: BF16,
@@ -127,13 +128,16 @@ def check_borders(sizes, user, ndim):
     return list(out), list(new)[:shift + min(ndim, 3)]
 
 
-def problem(x, pad, active, borders, dtype=None, w=None):
-    """w: the weights of the call, if it has float weights -- fp32 weights with an fp16 / bf16 `x` set WEIGHTS_F32 (mixed precision)"""
+def problem(x, pad, active, borders, dtype=None, w=None, shift_dim0=False):
+    """w: the weights of the call, if it has float weights -- fp32 weights with an fp16 / bf16 `x` set WEIGHTS_F32 (mixed precision);
+    shift_dim0: set SHIFT_DIM0 (the learnable temporal shift: w is [C])"""
     p = Problem()
     p.ndim = x.dim() - 2
     p.dtype = DTYPES[x.dtype] if dtype is None else dtype
     if w is not None and w.dtype == torch.float32 and x.dtype in (torch.float16, torch.bfloat16):
         p.dtype |= WEIGHTS_F32
+    if shift_dim0:
+        p.dtype |= SHIFT_DIM0
     p.padding_mode = int(pad)
     p.active = int(bool(active))
     for i in range(5):
@@ -153,10 +157,10 @@ def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def forward(x, w, pad, active, borders=None, out=None):
+def forward(x, w, pad, active, borders=None, out=None, shift_dim0=False):
     """x, w: device tensors (float dtypes; w of x's dtype, or fp32 with an fp16 / bf16 x).  Returns a new contiguous output (or
-    fills `out`)."""
-    p = problem(x, pad, active, borders, w=w)
+    fills `out`).  shift_dim0: the flagged call (w [C]; x and out segment-major views)."""
+    p = problem(x, pad, active, borders, w=w, shift_dim0=shift_dim0)
     if out is None:
         out = _new(out_shape(x, borders), x)
     w = w.contiguous()
@@ -165,21 +169,21 @@ def forward(x, w, pad, active, borders=None, out=None):
     return out
 
 
-def backward_workspace(x, pad, active, borders=None):
-    p = problem(x, pad, active, borders)
+def backward_workspace(x, pad, active, borders=None, shift_dim0=False):
+    p = problem(x, pad, active, borders, shift_dim0=shift_dim0)
     return torch.empty(int(lib().shiftnd_backward_workspace_bytes(ctypes.byref(p))), dtype=torch.uint8, device=x.device)
 
 
-def backward(grad_out, w, x, pad, active, borders=None, grad_x=None, grad_w=None, workspace=None):
+def backward(grad_out, w, x, pad, active, borders=None, grad_x=None, grad_w=None, workspace=None, shift_dim0=False):
     """grad_w comes back in w's dtype (fp32 for fp32 weights with a 16-bit x)"""
-    p = problem(x, pad, active, borders, w=w)
+    p = problem(x, pad, active, borders, w=w, shift_dim0=shift_dim0)
     w = w.contiguous()
     if grad_x is None:
         grad_x = _new(x.shape, x)
     if grad_w is None:
         grad_w = _new(w.shape, w)
     if workspace is None:
-        workspace = backward_workspace(x, pad, active, borders)
+        workspace = backward_workspace(x, pad, active, borders, shift_dim0)
     check(lib().shiftnd_backward(ctypes.byref(p), grad_out.data_ptr(), strides5(grad_out), x.data_ptr(), strides5(x),
                                  w.data_ptr(), grad_x.data_ptr(), strides5(grad_x), grad_w.data_ptr(),
                                  workspace.data_ptr(), workspace.numel(), _stream()), "shiftnd_backward")

@@ -179,3 +179,33 @@ def temporal_shift_func(input: Tensor, shifts: Tensor, n_segment: int, padding_m
         (f"{name}: expected input and shifts to be on same device, but input is  on {input.device} "
          f"and shifts is on {shifts.device}")
     return torch.ops.torchshifts.temporal_shift(input, shifts, n_segment, padding_mode)
+
+
+# ---- learnable temporal shift: a TRAINED per-channel shift across the frames of a [N * n_segment, C, ...] tensor -----------------
+# The sparse (rounded) or active (interpolated) 1-D shift of shift1d_func, applied along the frames of each clip.  The result, and
+# the gradients of input and weights, equal those of
+#   shift1d_func(x.view(N, T, C, M).permute(0, 3, 2, 1).reshape(N * M, C, T), weights.view(C, 1), padding_mode, active_flag)
+#       .view(N, M, C, T).permute(0, 3, 2, 1).reshape(x.shape)
+# without either layout change and without a permuted copy of the input in the autograd node: on HIP tensors one kernel per pass.
+# (The [N, C, T, M] view through shift2d_func with weights (w, 0) is NOT the same thing: the 2-D rule wires a difference along the
+# second dim into the first dim's weight gradient.)  `weights`: [n_channels] or [n_channels, 1] floats of the input's dtype, or
+# float32 with a float16 / bfloat16 input (torch.autocast); weights.grad has the weights' dtype.
+def temporal_shift_learnable_func(input: Tensor, weights: Tensor, n_segment: int, padding_mode: int = 0,
+                                  active_flag: bool = False) -> Tensor:
+    """Shift the channels of a [N * n_segment, C, ...] tensor (2 to 5 dims) across the n_segment frames of each clip by weights[c]."""
+    name = "temporal_shift_learnable_func()"
+    _assert_has_ops()
+    assert padding_mode in [0, 1, 2, 3, 4], f"{name} expected padding_mode can be {_PADDING_DOC}"
+    assert 2 <= len(input.shape) <= 5, f"{name}: expected a 2D to 5D tensor as input, but it is shape is {input.shape}"
+    assert isinstance(n_segment, int) and n_segment >= 1 and input.shape[0] % n_segment == 0, \
+        f"{name}: expected dim 0 of the input ({input.shape[0]}) to be a multiple of n_segment ({n_segment})"
+    assert len(weights.shape) == 1 or (len(weights.shape) == 2 and weights.shape[1] == 1), \
+        f"{name}: expected [n_channels] or [n_channels,1] tensor as weight, but it is shape is {weights.shape}"
+    assert input.shape[1] == weights.shape[0], \
+        (f"{name}: expected that input and weight have equal number of channels, but input have "
+         f"{input.shape[1]} and weight have {weights.shape[0]} channels.")
+    assert weights.is_floating_point(), f"{name}: expected float weights, but they are {weights.dtype}"
+    assert input.device == weights.device, \
+        (f"{name}: expected input and weights to be on same device, but input is  on {input.device} "
+         f"and weights is on {weights.device}")
+    return torch.ops.torchshifts.temporal_shift_learnable(input, weights, n_segment, padding_mode, bool(active_flag))

@@ -13,7 +13,8 @@ from torch import nn
 
 from torchshifts.functional import (shift1d_fixed_func, shift1d_fixed_pool_func, shift1d_func, shift1d_pool_func, shift2d_fixed_func,
                                     shift2d_fixed_pool_func, shift2d_func, shift2d_pool_func, shift3d_fixed_func,
-                                    shift3d_fixed_pool_func, shift3d_func, shift3d_pool_func, temporal_shift_func)
+                                    shift3d_fixed_pool_func, shift3d_func, shift3d_pool_func, temporal_shift_func,
+                                    temporal_shift_learnable_func)
 
 paddings_dict = {'zeros': 0, 'border': 1, 'periodic': 2, 'reflect': 3, 'symmetric': 4}
 
@@ -326,6 +327,17 @@ class TemporalShift(nn.Module):
         table[fold:2 * fold] = 1
         return table
 
+    @classmethod
+    def from_shift(cls, module):
+        """Freeze a trained, non-active LearnableTemporalShift: round(weight) (half to even, the kernels' rounding), its n_segment
+        and padding.  Output and input gradient are the learnable module's, bit for bit."""
+        assert isinstance(module, LearnableTemporalShift), 'expected a LearnableTemporalShift module'
+        if module._active_flag:
+            raise ValueError('an active shift interpolates: it cannot be frozen into integer shifts')
+        pad = {v: k for k, v in paddings_dict.items()}[module.padding]
+        table = torch.round(module.weight.detach().reshape(-1)).to(torch.int64)
+        return cls(module.n_segment, module.in_channels, shifts=table.cpu(), padding=pad).to(module.weight.device)
+
     def forward(self, input):
         return temporal_shift_func(input, self.shifts, self.n_segment, self.padding)
 
@@ -333,3 +345,53 @@ class TemporalShift(nn.Module):
         pad = {v: k for k, v in paddings_dict.items()}[self.padding]
         return (f'n_segment={self.n_segment}, in_channels={self.in_channels}, fold_div={self.fold_div}, padding_method={pad}, '
                 'fixed integer shifts')
+
+
+class LearnableTemporalShift(nn.Module):
+    """Learnable per-channel shift across the frames of a [N * n_segment, C, ...] tensor: Shift1d along the frames of each clip
+    (the temporal half of learnable-shift video models), without a layout change.  `weight` is a [in_channels, 1] parameter,
+    initialised like Shift1d's; with active_flag the forward interpolates between two frames, without it the shift is
+    round(weight) and TemporalShift.from_shift freezes the trained layer into the fixed module.
+
+    Arguments:
+        n_segment (int): frames per clip, T.
+        in_channels (int): channels of the input.
+        padding (str): 'zeros' | 'border' | 'periodic' | 'reflect' | 'symmetric'. Default 'zeros'.
+        init_shift (float): bound of the uniform weight initialisation. Default 1.
+        sparsity_term (float): strength of the L1 sparsity loss returned by forward. Default 5e-4.
+        active_flag (bool): interpolate on the forward pass (active shift). Default False.
+        init_thumb_rule (int): as Shift1d's (both values initialise with uniform(-init_shift, init_shift)).
+    forward(x) -> (output, loss): the pair convention of Shift{N}d; loss is None when sparsity_term == 0.
+    """
+
+    def __init__(self, n_segment, in_channels, padding='zeros', init_shift=1, sparsity_term=5e-4, active_flag=False,
+                 init_thumb_rule=1):
+        super().__init__()
+        assert padding.lower() in paddings_dict.keys(), f'incorrect padding option: {padding}'
+        assert int(n_segment) >= 1, 'n_segment must be >= 1'
+        self.padding = paddings_dict[padding.lower()]
+        self.n_segment = int(n_segment)
+        self.in_channels = in_channels
+        self.sparsity_term = sparsity_term
+        self._active_flag = active_flag
+        self.init_shift = torch.tensor(_wrap_dim(init_shift, 1, 'init_shift'), requires_grad=False)
+        self.weight = nn.Parameter(torch.Tensor(in_channels, 1))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        self.weight.data[:, 0] = _Shiftnd._init_thumb_rule_1(self.init_shift[0], self.in_channels)
+
+    def _compute_weight_loss(self):
+        return self.sparsity_term * torch.sum(torch.abs(self.weight))
+
+    def forward(self, input):
+        """Returns (output, loss); loss is None when sparsity_term == 0."""
+        loss = self._compute_weight_loss() if bool(self.sparsity_term) else None
+        return temporal_shift_learnable_func(input, self.weight, self.n_segment, self.padding, self._active_flag), loss
+
+    def extra_repr(self):
+        pad = {v: k for k, v in paddings_dict.items()}[self.padding]
+        active = f'Active shift on forward pass: {"Yes" if self._active_flag else "No"}'
+        sparse = ('Sparse shift: Yes - sparsity strength: {}'.format(self.sparsity_term)
+                  if bool(self.sparsity_term) else 'Sparse shift: No')
+        return f'n_segment={self.n_segment}, in_channels={self.in_channels}, padding_method={pad}, {active}, {sparse}'

@@ -86,6 +86,26 @@ typedef enum shiftnd_dtype {
  */
 #define SHIFTND_WEIGHTS_F32 0x100
 
+/*
+ * The learnable temporal shift (a trained per-channel shift across the frames of a video tensor [N*T, C, H, W], seen as the
+ * problem [N, C, T, H*W] with strides {T*C*M, M, C*M, 1}).  OR-ed onto a float dtype in shiftnd_problem.dtype: `weights` and
+ * `grad_w` are [C] arrays, ONE entry per channel; the 1-D shift (sparse or interpolating, p->active) acts on spatial dim 0 only
+ * and every other spatial dim is untouched.  out, grad_x and grad_w are those of the 1-D problem [N * S1 * S2, C, S0] on the
+ * permuted tensors.  Combines with SHIFTND_WEIGHTS_F32.
+ *   Honoured by shiftnd_forward, shiftnd_backward and shiftnd_backward_workspace_bytes (which then sizes this plan alone).
+ *   Accepted: ndim 2 or 3; F32, F64, F16, BF16; both values of p->active; every padding mode; the whole window; all tensors
+ *   (x, out, grad_out, grad_x) dense in memory order N, S0, C, S1, S2 (a dim of size 1 has no stride to check) at element-aligned
+ *   bases; N, C, S1 * S2 and N * S0 * C below 2^31, S0 below 2^30, fewer than 2^31 - 16 two-byte units in the tensor.  There is
+ *   no fallback under the flag: C == 1, S0 == 1 and S1 * S2 == 1 are served by the same kernels (shiftnd_last_kernel():
+ *   tshift_forward / tshift_backward, *_ragged for planes that are not whole 16-byte pieces or bases off the 16-byte grid;
+ *   shiftnd_last_path(): SHIFTND_PATH_PLANE).
+ *   Errors, before anything is launched: the quantized types SHIFTND_ERR_UNSUPPORTED_DTYPE (the workspace query answers 0);
+ *   ndim 1, a cut window, any other layout, a size beyond the limits, the x == NULL && grad_w == NULL form of shiftnd_backward:
+ *   SHIFTND_ERR_INVALID_ARGUMENT.  Every other entry point refuses the flag as an unknown dtype.
+ * Without the flag nothing changes.
+ */
+#define SHIFTND_SHIFT_DIM0 0x200
+
 typedef enum shiftnd_status {
     SHIFTND_OK = 0,
     SHIFTND_ERR_INVALID_ARGUMENT = -1,
@@ -109,7 +129,7 @@ typedef enum shiftnd_path {
 /* Problem geometry shared by the entry points. */
 typedef struct shiftnd_problem {
     int32_t ndim;          /* spatial dims: 1, 2 or 3 */
-    int32_t dtype;         /* shiftnd_dtype of input/output (and of float weights), optionally | SHIFTND_WEIGHTS_F32 */
+    int32_t dtype;         /* shiftnd_dtype of input/output (and of float weights), optionally | SHIFTND_WEIGHTS_F32 | SHIFTND_SHIFT_DIM0 */
     int32_t padding_mode;  /* 0..4 */
     int32_t active;        /* 0: sparse shift (rounded integer shift); 1: active (interpolated) */
     int64_t sizes[5];      /* input N, C, H, W, D */
