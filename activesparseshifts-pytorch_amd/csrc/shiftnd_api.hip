@@ -258,10 +258,10 @@ int forward_common(const shiftnd_problem *p, const void *x, const int64_t *xs, c
         return finish(cl_forward(g, p->dtype, x, w, wkind, wzp, fill, out, st));
     }
     // segment-major tensors (memory order N, S0, C, S1, S2: a temporal shift of [N*T, C, H, W]): plane copies at stream rate
-    // instead of one element per thread
-    if (g_policy == 0 && wkind <= SHIFTND_BF16 && segment_forward_eligible(g, p->dtype, x, out)) {
+    // instead of one element per thread; quantized tensors with their zero point as the fill
+    if (g_policy == 0 && segment_forward_eligible(g, p->dtype, x, out)) {
         g_last_path = SHIFTND_PATH_PLANE;
-        return finish(segment_forward(g, p->dtype, x, w, wkind, out, st));
+        return finish(segment_forward(g, p->dtype, x, w, wkind, wzp, fill, out, st));
     }
     g_last_path = SHIFTND_PATH_STRIDED;
     return finish(strided_forward(g, p->dtype, x, w, wkind, wzp, fill, out, st));

@@ -213,11 +213,12 @@ bool gradx_embed_eligible(const Geometry &g, int dtype, const void *go, const vo
 int gradx_embed(const Geometry &g, int dtype, const void *go, const void *w, void *gx, hipStream_t st);
 int gradx_gather(const Geometry &g, int dtype, const void *go, const void *w, void *gx, hipStream_t st);
 
-// ---- segment-major tensors (shiftnd_segment.hip): the sparse shift of float tensors whose memory order is N, S0, C, S1, S2 (a
-// temporal shift of [N*T, C, H, W] seen as [N, C, T, H*W]), x and out in the same dense layout, whole window; planes are copied
-// or filled, or gathered element by element where the table also shifts an inner dim
+// ---- segment-major tensors (shiftnd_segment.hip): the sparse shift of float and quantized (I8, U8, I32) tensors whose memory order
+// is N, S0, C, S1, S2 (a temporal shift of [N*T, C, H, W] seen as [N, C, T, H*W]), x and out in the same dense layout, whole window;
+// planes are copied or filled with `fill_bits`, or gathered element by element where the table also shifts an inner dim
 bool segment_forward_eligible(const Geometry &g, int dtype, const void *x, const void *out);
-int segment_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, void *out, hipStream_t st);
+int segment_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, int64_t wzp, uint64_t fill_bits, void *out,
+                    hipStream_t st);
 
 // ---- the learnable temporal shift (shiftnd_tshift.hip; SHIFTND_SHIFT_DIM0): a 1-D sparse / interpolating shift along S0 of
 // segment-major float tensors, `w` and `gw` [C] arrays, whole window.  tshift_geometry_ok: the sizes; tshift_tensor_ok: one tensor's

@@ -3,22 +3,29 @@
 // A video tensor [N*T, C, H, W] whose clips of T frames are shifted along T (the Temporal Shift Module, arXiv 1811.08383) is, seen as
 // a shift problem, [N, C, T, H*W] with strides {T*C*M, M, C*M, 1}: the shifted dim lies OUTSIDE the channel dim.  For every
 // (n, t, c) the op copies one contiguous plane of `inner` elements from segment pad(t - s_c) of the same sample, or fills it with
-// zeros: no arithmetic, no dependence on the element type (zero is all-zero bits in every float type).  The kernels stream the
-// output flat in aligned 16-byte pieces and find each piece's plane with three multiply-shift divisions; before them this stride
-// pattern ended in strided_gather_forward (one element per thread, 64-bit divisions).
+// the fill value: no arithmetic, and of the element type only its size and its fill pattern (all-zero bits in every float type;
+// the zero point of a quantized tensor, one byte for int8 / uint8 and a dword for int32 -- a dword pattern in the params, the byte
+// splatted four times).  The kernels stream the output flat in aligned 16-byte pieces and find each piece's plane with three
+// multiply-shift divisions on a count of UNITS: the element where it is one byte, two bytes elsewhere (every other element size
+// is a multiple, and a 32-bit unit count then covers 4 GiB of them).  Before these kernels this stride pattern ended in
+// strided_gather_forward (one element per thread, 64-bit divisions).
 //
 // The host routes by strides alone and cannot read the device table, so the kernels are right for EVERY [C, ndim] table: a
-// plane whose channel also shifts an inner dim is gathered through pad_index, two bytes at a time (slow, exact), inside the same
-// kernel; planes with zero inner shifts (every plane of a temporal shift) are the plane copy / fill.
+// plane whose channel also shifts an inner dim is gathered through pad_index, one unit at a time (slow, exact), inside the same
+// kernel; planes with zero inner shifts (every plane of a temporal shift) are the plane copy / fill.  The table is any kind
+// gather_shift reads: floats rounded half to even, or I8 / U8 / I32 integers minus their zero point (quantized calls).
 //
 // One kernel, two forms (shiftnd_last_kernel() names the form):
 //   segment_forward          planes of whole 16-byte pieces, 16-byte-aligned bases: one 16-byte nontemporal load and store per piece
-//   segment_forward_ragged   everything else (7 x 7 and 14 x 14 planes of 16-bit elements, bases offset by an element): aligned
+//   segment_forward_ragged   everything else (7 x 7 and 14 x 14 planes of 8- and 16-bit elements, bases offset by an element, which
+//                            for one-byte elements is any byte, with planes of an odd number of bytes): aligned
 //                            16-byte stores; a piece lies in one plane or straddles two, and each part is funnelled out of the
 //                            (at most two) ALIGNED 16-byte pieces of x that hold its source bytes.  Every load and store is
 //                            naturally aligned, and a load is issued only when it holds a byte the result needs, so none leaves
 //                            the 16-byte granules the tensor itself touches.  Partial pieces at the two ends of the tensor and
-//                            pieces over more than two planes (planes under 16 bytes) move two bytes at a time.
+//                            pieces over more than two planes (planes under 16 bytes) move one unit at a time.  A filled
+//                            part is the fill pattern: an int32 plane starts at a multiple of 4 bytes of the 4-byte-aligned
+//                            tensor, so the dwords of an aligned output piece are whole elements.
 // The backward of a fixed shift (shiftnd_backward's x == NULL form, whole window) is the forward under the negated table and
 // arrives here through forward_common with the gradient's strides.
 #include "shiftnd_common.hpp"
@@ -32,10 +39,13 @@ constexpr int kRaggedInFlight = 2;   // (up to four loads per piece)
 
 struct SegmentParams {
     int nd, pad, wkind, es_log2;       // es: element bytes (the per-element gather only)
-    uint32_t T, C, hpp;                // segments, channels, halfwords (2 bytes) per plane
-    FastDiv d_hpp, d_C, d_T, d_per;    // d_per: by map_period(T, pad)
+    uint32_t T, C, upp;                // segments, channels, units per plane
+    FastDiv d_upp, d_C, d_T, d_per;    // d_per: by map_period(T, pad)
     int64_t A, B;                      // the plane as [A][B] elements (A = 1 for ndim 2)
     int64_t plane_bytes, total_bytes;
+    int64_t wzp;                       // zero point of an integer table
+    int unit_log2;                     // the stream unit: 0 (one byte) for 1-byte elements, 1 (two bytes) otherwise
+    uint32_t fill;                     // what a filled plane holds, as a dword pattern (0 for floats)
 };
 
 struct Place {
@@ -50,9 +60,9 @@ __device__ __forceinline__ Place place_plane(const SegmentParams &q, const void 
     p.n = fdiv(nt, q.d_T);
     p.t = nt - p.n * q.T;
     const int64_t row = static_cast<int64_t>(p.c) * q.nd;
-    p.s0 = gather_shift(w, q.wkind, 0, row);
-    p.sA = q.nd == 3 ? gather_shift(w, q.wkind, 0, row + 1) : 0;
-    p.sB = gather_shift(w, q.wkind, 0, row + q.nd - 1);
+    p.s0 = gather_shift(w, q.wkind, q.wzp, row);
+    p.sA = q.nd == 3 ? gather_shift(w, q.wkind, q.wzp, row + 1) : 0;
+    p.sB = gather_shift(w, q.wkind, q.wzp, row + q.nd - 1);
     return p;
 }
 
@@ -69,16 +79,17 @@ __device__ __forceinline__ int64_t source_plane(const SegmentParams &q, const Pl
     return ts < 0 ? -1 : ((static_cast<int64_t>(p.n) * q.T + ts) * q.C + p.c) * q.plane_bytes;
 }
 
-// The 16 output bytes from stream byte `sb` on, two at a time, the part inside the tensor: every padding map through pad_index,
-// the inner dims included.
-__device__ __forceinline__ void slow_halfwords(const SegmentParams &q, const char *x, const void *w, char *out, int64_t sb) {
+// The 16 output bytes from stream byte `sb` on, one unit at a time, the part inside the tensor: every padding map through
+// pad_index, the inner dims included.
+__device__ __forceinline__ void slow_units(const SegmentParams &q, const char *x, const void *w, char *out, int64_t sb) {
+    const int ul = q.unit_log2, step = 1 << ul;
 #pragma unroll 1
-    for (int k = 0; k < 8; ++k) {
-        const int64_t b = sb + 2 * k;
+    for (int k = 0; k < 16; k += step) {
+        const int64_t b = sb + k;
         if (b < 0 || b >= q.total_bytes) continue;
-        const uint32_t h = static_cast<uint32_t>(b >> 1);
-        const uint32_t plane = fdiv(h, q.d_hpp);
-        const int64_t at = static_cast<int64_t>(h - plane * q.hpp) * 2;   // byte in the plane
+        const uint32_t u = static_cast<uint32_t>(b >> ul);
+        const uint32_t plane = fdiv(u, q.d_upp);
+        const int64_t at = static_cast<int64_t>(u - plane * q.upp) << ul;   // byte in the plane
         const Place p = place_plane(q, w, plane);
         const int64_t ts = pad_index(static_cast<int64_t>(p.t) - p.s0, q.T, q.pad);
         int64_t e = at >> q.es_log2;                                       // element in the plane
@@ -91,9 +102,17 @@ __device__ __forceinline__ void slow_halfwords(const SegmentParams &q, const cha
             valid = valid && as >= 0 && bs >= 0;
             e = as * q.B + bs;
         }
-        uint16_t v = 0;
-        if (valid) v = *reinterpret_cast<const uint16_t *>(x + ((static_cast<int64_t>(p.n) * q.T + ts) * q.C + p.c) * q.plane_bytes + (e << q.es_log2) + in_element);
-        *reinterpret_cast<uint16_t *>(out + b) = v;
+        const char *from = x + ((static_cast<int64_t>(p.n) * q.T + ts) * q.C + p.c) * q.plane_bytes + (e << q.es_log2) + in_element;
+        const uint32_t f = q.fill >> (8 * (static_cast<int>(in_element) & 3));   // (the unit's bytes of the element's fill)
+        if (ul == 0) {
+            uint8_t v = static_cast<uint8_t>(f);
+            if (valid) v = *reinterpret_cast<const uint8_t *>(from);
+            *reinterpret_cast<uint8_t *>(out + b) = v;
+        } else {
+            uint16_t v = static_cast<uint16_t>(f);
+            if (valid) v = *reinterpret_cast<const uint16_t *>(from);
+            *reinterpret_cast<uint16_t *>(out + b) = v;
+        }
     }
 }
 
@@ -112,16 +131,16 @@ __device__ __forceinline__ void whole_pieces_body(const SegmentParams &q, const 
             src[k] = kPast;
             continue;
         }
-        const uint32_t h = static_cast<uint32_t>(i) * 8;
-        const uint32_t plane = fdiv(h, q.d_hpp);
+        const uint32_t u = static_cast<uint32_t>(i) << (4 - q.unit_log2);
+        const uint32_t plane = fdiv(u, q.d_upp);
         const Place p = place_plane(q, w, plane);
         const int64_t from = source_plane(q, p);
-        src[k] = inner_shift(q, p) ? kSlow : (from < 0 ? kFill : from + static_cast<int64_t>(h - plane * q.hpp) * 2);
+        src[k] = inner_shift(q, p) ? kSlow : (from < 0 ? kFill : from + (static_cast<int64_t>(u - plane * q.upp) << q.unit_log2));
     }
     shiftnd_u4 v[kWholeInFlight];
 #pragma unroll
     for (int k = 0; k < kWholeInFlight; ++k) {
-        v[k] = shiftnd_u4(0);
+        v[k] = shiftnd_u4(q.fill);
         if (src[k] >= 0) v[k] = __builtin_nontemporal_load(reinterpret_cast<const shiftnd_u4 *>(x + src[k]));   // (a filled plane issues no load)
     }
     uint32_t slow = 0;   // (one copy of the slow path in the code, and no dynamically indexed array)
@@ -132,7 +151,7 @@ __device__ __forceinline__ void whole_pieces_body(const SegmentParams &q, const 
     }
 #pragma unroll 1
     for (int k = 0; k < kWholeInFlight; ++k)
-        if (slow >> k & 1) slow_halfwords(q, x, w, out, (first + k * kThreads) * 16);
+        if (slow >> k & 1) slow_units(q, x, w, out, (first + k * kThreads) * 16);
 }
 
 __device__ __forceinline__ uint32_t pick4(uint32_t i, uint32_t a0, uint32_t a1, uint32_t a2, uint32_t a3) {
@@ -162,7 +181,8 @@ __device__ __forceinline__ void ragged_pieces_body(const SegmentParams &q, const
     const int64_t pieces = (lead + q.total_bytes + 15) >> 4;
     const int64_t first = static_cast<int64_t>(blockIdx.x) * (kThreads * kRaggedInFlight) + threadIdx.x;
     // a piece = bytes [0, cut) of plane A + bytes [cut, 16) of the next plane B.  fromA / fromB: the ADDRESS output byte 0 of the piece
-    // would be read from if the part's plane went on in both directions (0: the part is filled, or absent)
+    // would be read from if the part's plane went on in both directions.  0: the part is filled, or absent -- no load is issued, and
+    // the pieces, which start out as the fill pattern, funnel at offset 0 to the pattern itself
     uintptr_t fromA[kRaggedInFlight], fromB[kRaggedInFlight];
     int cut[kRaggedInFlight];
     int kind[kRaggedInFlight];   // 0, kSlow or kPast
@@ -174,9 +194,9 @@ __device__ __forceinline__ void ragged_pieces_body(const SegmentParams &q, const
         cut[k] = 16;
         kind[k] = static_cast<int>(i >= pieces ? kPast : ((sb < 0 || sb + 16 > q.total_bytes) ? kSlow : 0));
         if (kind[k] != 0) continue;
-        const uint32_t h = static_cast<uint32_t>(sb >> 1);
-        const uint32_t plane = fdiv(h, q.d_hpp);
-        const int64_t at = static_cast<int64_t>(h - plane * q.hpp) * 2;   // byte in plane A
+        const uint32_t u = static_cast<uint32_t>(sb >> q.unit_log2);
+        const uint32_t plane = fdiv(u, q.d_upp);
+        const int64_t at = static_cast<int64_t>(u - plane * q.upp) << q.unit_log2;   // byte in plane A (any byte, for 1-byte elements)
         const int64_t left = q.plane_bytes - at;
         const bool two = left < 16;
         cut[k] = two ? static_cast<int>(left) : 16;
@@ -195,7 +215,7 @@ __device__ __forceinline__ void ragged_pieces_body(const SegmentParams &q, const
     shiftnd_u4 a0[kRaggedInFlight], a1[kRaggedInFlight], b0[kRaggedInFlight], b1[kRaggedInFlight];
 #pragma unroll
     for (int k = 0; k < kRaggedInFlight; ++k) {
-        a0[k] = a1[k] = b0[k] = b1[k] = shiftnd_u4(0);
+        a0[k] = a1[k] = b0[k] = b1[k] = shiftnd_u4(q.fill);
         const uintptr_t pa = fromA[k] & ~static_cast<uintptr_t>(15), pb = fromB[k] & ~static_cast<uintptr_t>(15);
         const int offa = static_cast<int>(fromA[k] & 15), offb = static_cast<int>(fromB[k] & 15);
         if (fromA[k]) a0[k] = __builtin_nontemporal_load(reinterpret_cast<const shiftnd_u4 *>(pa));
@@ -221,7 +241,7 @@ __device__ __forceinline__ void ragged_pieces_body(const SegmentParams &q, const
     }
 #pragma unroll 1
     for (int k = 0; k < kRaggedInFlight; ++k)
-        if (slow >> k & 1) slow_halfwords(q, x, w, out, (first + k * kThreads) * 16 - lead);
+        if (slow >> k & 1) slow_units(q, x, w, out, (first + k * kThreads) * 16 - lead);
 }
 
 // ONE kernel for both forms (`ragged` is launch-uniform: a scalar branch), because the library's kernel budget has room for one
@@ -249,34 +269,41 @@ bool whole_pieces(const Geometry &g, int dtype, const void *x, const void *out) 
 
 }  // namespace
 
+// float tensors, and the int_repr of quantized ones (I8, U8, I32: the caller passes their fill pattern and an integer table)
 bool segment_forward_eligible(const Geometry &g, int dtype, const void *x, const void *out) {
-    if (g.active || dtype > SHIFTND_BF16 || cropped(g) || g.nd < 2) return false;
+    if (g.active || dtype < SHIFTND_F32 || dtype > SHIFTND_I32 || cropped(g) || g.nd < 2) return false;
     const int64_t T = g.S[3 - g.nd], inner = (g.nd == 3 ? g.S[1] : 1) * g.S[2], es = dtype_size(dtype);
     if (g.C <= 1 || T <= 1 || !segment_major(g, g.xs) || !segment_major(g, g.os)) return false;
     if (!aligned_to(x, es) || !aligned_to(out, es)) return false;
-    // 32-bit plane and halfword counts (FastDiv: below 2^31); T also enters the 32-bit padding map (periods of 2 T)
+    // 32-bit plane and unit counts (FastDiv: below 2^31; the unit is the element where it is one byte, two bytes elsewhere, so a
+    // 1-byte tensor of 2^31 - 16 bytes or more keeps the strided kernel); T also enters the 32-bit padding map (periods of 2 T)
     const int64_t limit = 1LL << 31;
     if (T >= (1LL << 30) || inner >= limit || g.N >= limit || g.C >= limit || g.N * T >= limit) return false;
     const int64_t planes = g.N * T * g.C;   // (every factor is below 2^31 here: no overflow)
-    return planes < limit && planes * (inner * es / 2) + 16 < limit;
+    return planes < limit && planes * (es == 1 ? inner : inner * es / 2) + 16 < limit;
 }
 
-int segment_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, void *out, hipStream_t st) {
+int segment_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, int64_t wzp, uint64_t fill_bits, void *out,
+                    hipStream_t st) {
     const bool whole = whole_pieces(g, dtype, x, out);
     const int es = dtype_size(dtype);
     SegmentParams q;
     q.nd = g.nd;
     q.pad = g.pad;
     q.wkind = wkind;
-    q.es_log2 = es == 8 ? 3 : (es == 4 ? 2 : 1);
+    q.wzp = wzp;
+    q.es_log2 = es == 8 ? 3 : (es == 4 ? 2 : (es == 2 ? 1 : 0));
+    q.unit_log2 = es == 1 ? 0 : 1;
+    // the fill as a dword pattern: a byte four times, the dword itself (floats: fill_bits == 0)
+    q.fill = es == 1 ? static_cast<uint32_t>(fill_bits & 0xff) * 0x01010101u : static_cast<uint32_t>(fill_bits);
     q.T = static_cast<uint32_t>(g.S[3 - g.nd]);
     q.C = static_cast<uint32_t>(g.C);
     q.A = g.nd == 3 ? g.S[1] : 1;
     q.B = g.S[2];
     q.plane_bytes = q.A * q.B * es;
-    q.hpp = static_cast<uint32_t>(q.plane_bytes / 2);
+    q.upp = static_cast<uint32_t>(q.plane_bytes >> q.unit_log2);
     q.total_bytes = g.N * q.T * q.C * q.plane_bytes;
-    q.d_hpp = make_fastdiv(q.hpp);
+    q.d_upp = make_fastdiv(q.upp);
     q.d_C = make_fastdiv(q.C);
     q.d_T = make_fastdiv(q.T);
     q.d_per = make_fastdiv(static_cast<uint32_t>(map_period(static_cast<int>(q.T), g.pad)));

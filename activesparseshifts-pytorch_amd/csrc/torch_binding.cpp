@@ -1000,6 +1000,56 @@ Tensor temporal_backward_hip(const Tensor &grad, const Tensor &shifts, int64_t n
     return temporal_hip(grad, shifts, n_segment, padding_mode, true);
 }
 
+// ---- quantized temporal shift: temporal_shift_quantized(input, shifts, n_segment, padding_mode) -------------------------------------
+// The gather of temporal_shift on the int_repr of a per-tensor quantized tensor (quint8, qint8, qint32): a plane is copied, or
+// filled with the input's zero point, which dequantizes to exactly 0.  Scale and zero point pass through -- no requantization, no
+// gradient.  A separate op: temporal_shift itself refuses quantized tensors.
+void temporal_quantized_check(const Tensor &input, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    TORCH_CHECK(input.is_quantized(), "temporal_shift_quantized: expected a quantized input");
+    TORCH_CHECK(input.qscheme() == at::kPerTensorAffine, "temporal_shift_quantized: expected a per-tensor quantized input");
+    TORCH_CHECK(input.dim() >= 2 && input.dim() <= 5, "temporal_shift_quantized: expected a [N*T, C, ...] tensor of 2 to 5 dims");
+    TORCH_CHECK(n_segment >= 1 && input.size(0) % n_segment == 0, "temporal_shift_quantized: dim 0 (", input.size(0),
+                ") must be a multiple of n_segment (", n_segment, ")");
+    TORCH_CHECK((shifts.dim() == 1 || (shifts.dim() == 2 && shifts.size(1) == 1)) && shifts.size(0) == input.size(1),
+                "temporal_shift_quantized: shifts must have shape [C] or [C, 1]");
+    TORCH_CHECK(shifts.device() == input.device(), "temporal_shift_quantized: shifts must be on the input's device");
+    TORCH_CHECK(!shifts.is_quantized() && (at::isFloatingType(shifts.scalar_type()) || at::isIntegralType(shifts.scalar_type(), false)),
+                "temporal_shift_quantized: shifts must be integers or floats");
+    TORCH_CHECK(padding_mode >= 0 && padding_mode <= 4, "temporal_shift_quantized: padding_mode must be 0..4");
+}
+
+// ONE shiftnd_forward_quantized call on the segment-major strides (shiftnd_segment.hip).  The table is [C, 2] int32 with column 1
+// zero, built on the device without a host sync: unlike the float op's table of the tensor dtype, exact for every shift
+Tensor temporal_quantized_hip(const Tensor &input_, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    TORCH_CHECK(input_.is_cuda(), "temporal_shift_quantized: expected a CUDA tensor");
+    temporal_quantized_check(input_, shifts, n_segment, padding_mode);
+    c10::DeviceGuard device_guard(input_.device());
+    const int dtype = quant_dtype(input_.scalar_type(), "temporal_shift_quantized_cuda");
+    const Tensor t = input_.contiguous();
+    Tensor out = at::_empty_affine_quantized(t.sizes(), t.options().memory_format(at::MemoryFormat::Contiguous), t.q_scale(),
+                                             t.q_zero_point(), c10::nullopt);
+    if (t.numel() == 0) return out;
+    const int64_t T = n_segment, C = t.size(1), N = t.size(0) / T, M = t.numel() / (t.size(0) * C);
+    TORCH_CHECK(T <= INT32_MAX && M <= INT32_MAX, "temporal_shift_quantized: n_segment and the frame size must fit 32 bits");
+    Tensor w = at::zeros({C, 2}, t.options().dtype(at::kInt));
+    const Tensor s = shifts.detach().reshape({C});
+    w.select(1, 0).copy_(at::isFloatingType(s.scalar_type()) ? at::round(s) : s);   // (half to even, like the sparse shift's weights)
+    shiftnd_problem p;
+    p.ndim = 2;
+    p.dtype = dtype;
+    p.padding_mode = static_cast<int32_t>(padding_mode);
+    p.active = 0;
+    const int64_t sizes[5] = {N, C, T, M, 1};
+    const int32_t borders[6] = {0, static_cast<int32_t>(T), 0, static_cast<int32_t>(M), 0, 1};
+    for (int i = 0; i < 5; ++i) p.sizes[i] = sizes[i];
+    for (int i = 0; i < 6; ++i) p.borders[i] = borders[i];
+    const int64_t st[5] = {T * C * M, M, C * M, 1, 0};
+    const int rc = shiftnd_forward_quantized(&p, t.data_ptr(), st, w.data_ptr(), SHIFTND_I32, 0, t.q_zero_point(), out.data_ptr(), st,
+                                             current_stream(t));
+    TORCH_CHECK(rc == SHIFTND_OK, "temporal_shift_quantized (HIP): ", shiftnd_status_string(rc));
+    return out;
+}
+
 // ---- learnable temporal shift: a TRAINED per-channel shift across the frames of [N*T, C, ...] ------------------------------------
 // temporal_shift_learnable(input, weights, n_segment, padding_mode, active_flag) ==
 //     shift1d(x.view(N, T, C, M).permute(0, 3, 2, 1).reshape(N*M, C, T), weights.view(C, 1), padding_mode, active_flag)
@@ -1222,6 +1272,8 @@ TORCH_LIBRARY(torchshifts, m) {
     // temporal shift (TSM): fixed shifts across the frames of [N*T, C, ...] (not in the reference)
     m.def("torchshifts::temporal_shift(Tensor input, Tensor shifts, int n_segment, int padding_mode) -> Tensor");
     m.def("torchshifts::_temporal_shift_backward(Tensor grad, Tensor shifts, int n_segment, int padding_mode) -> Tensor");
+    // ... of a per-tensor quantized tensor: the same gather on the int_repr, the zero point as the fill (QuantizedCPU / QuantizedCUDA)
+    m.def("torchshifts::temporal_shift_quantized(Tensor input, Tensor shifts, int n_segment, int padding_mode) -> Tensor");
     // learnable temporal shift: a trained per-channel shift across the frames, sparse or interpolating (not in the reference)
     m.def("torchshifts::temporal_shift_learnable(Tensor input, Tensor weights, int n_segment, int padding_mode, bool active_flag) -> Tensor", &tsl_public);
     m.def("torchshifts::_temporal_shift_learnable_forward(Tensor input, Tensor weights, int n_segment, int padding_mode, bool active_flag) -> Tensor");
@@ -1291,6 +1343,7 @@ TORCH_LIBRARY_IMPL(torchshifts, CUDA, m) {
 }
 
 TORCH_LIBRARY_IMPL(torchshifts, QuantizedCUDA, m) {
+    m.impl("temporal_shift_quantized", TORCH_FN(temporal_quantized_hip));
     m.impl("_shift1d_forward", TORCH_FN(qshift_forward_hip<1>));
     m.impl("_shift1d_backward", TORCH_FN(qshift_backward));
     m.impl("_shift2d_forward", TORCH_FN(qshift_forward_hip<2>));

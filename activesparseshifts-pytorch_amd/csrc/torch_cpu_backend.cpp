@@ -16,6 +16,7 @@
 #include <ATen/Parallel.h>
 #include <torch/library.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <tuple>
@@ -425,7 +426,26 @@ template <int ND> Tensor shift_fixed_pool_backward_cpu(const Tensor &grad, const
 // plane is copied or zero-filled, and zero is all-zero bits) ---------------------------------------------------------------
 }  // namespace cpu
 void temporal_check(const at::Tensor &input, const at::Tensor &shifts, int64_t n_segment, int64_t padding_mode);   // torch_binding.cpp
+void temporal_quantized_check(const at::Tensor &input, const at::Tensor &shifts, int64_t n_segment, int64_t padding_mode);
 namespace cpu {
+
+// the planes of a contiguous [N*T, C, plane] tensor, copied or filled; `fill`: the element's bit pattern (0, or a quantized tensor's
+// zero point: one byte, or an int32)
+void temporal_planes(const char *src, char *dst, int64_t N, int64_t T, int64_t C, size_t plane_bytes, const int64_t *s, int sign,
+                     int64_t padding_mode, size_t element_size, int32_t fill) {
+    at::parallel_for(0, N * T, 1, [&](int64_t begin, int64_t end) {
+        for (int64_t nt = begin; nt < end; ++nt) {
+            const int64_t n = nt / T, tt = nt % T;
+            for (int64_t c = 0; c < C; ++c) {
+                const int64_t ts = T == 1 ? 0 : pad_index(tt - sign * s[c], T, static_cast<int>(padding_mode));   // (a size-1 dim ignores its shift)
+                char *d = dst + static_cast<size_t>(nt * C + c) * plane_bytes;
+                if (ts >= 0) std::memcpy(d, src + static_cast<size_t>((n * T + ts) * C + c) * plane_bytes, plane_bytes);
+                else if (fill == 0 || element_size == 1) std::memset(d, fill, plane_bytes);
+                else std::fill_n(reinterpret_cast<int32_t *>(d), plane_bytes / sizeof(int32_t), fill);
+            }
+        }
+    });
+}
 
 Tensor temporal_gather_cpu(const Tensor &t_, const Tensor &shifts, int64_t T, int64_t padding_mode, int sign) {
     TORCH_CHECK(t_.device().is_cpu() && shifts.device().is_cpu(), "temporal_shift_cpu: expected CPU tensors");
@@ -439,19 +459,8 @@ Tensor temporal_gather_cpu(const Tensor &t_, const Tensor &shifts, int64_t T, in
     // rint of the table (half to even), like the sparse shift's weights
     const Tensor table = shifts.detach().reshape({C}).to(at::kDouble).round().to(at::kLong).contiguous();
     const int64_t *s = table.data_ptr<int64_t>();
-    const char *src = static_cast<const char *>(t.data_ptr());
-    char *dst = static_cast<char *>(out.data_ptr());
-    at::parallel_for(0, N * T, 1, [&](int64_t begin, int64_t end) {
-        for (int64_t nt = begin; nt < end; ++nt) {
-            const int64_t n = nt / T, tt = nt % T;
-            for (int64_t c = 0; c < C; ++c) {
-                const int64_t ts = T == 1 ? 0 : pad_index(tt - sign * s[c], T, static_cast<int>(padding_mode));   // (a size-1 dim ignores its shift)
-                char *d = dst + static_cast<size_t>(nt * C + c) * plane_bytes;
-                if (ts < 0) std::memset(d, 0, plane_bytes);
-                else std::memcpy(d, src + static_cast<size_t>((n * T + ts) * C + c) * plane_bytes, plane_bytes);
-            }
-        }
-    });
+    temporal_planes(static_cast<const char *>(t.data_ptr()), static_cast<char *>(out.data_ptr()), N, T, C, plane_bytes, s, sign,
+                    padding_mode, t.element_size(), 0);
     return out;
 }
 
@@ -460,6 +469,27 @@ Tensor temporal_forward_cpu(const Tensor &input, const Tensor &shifts, int64_t n
 }
 Tensor temporal_backward_cpu(const Tensor &grad, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
     return temporal_gather_cpu(grad, shifts, n_segment, padding_mode, -1);
+}
+
+// temporal_shift_quantized: the same plane copy on the raw element bytes of a per-tensor quantized tensor, filled planes hold the
+// zero point; scale and zero point pass through
+Tensor temporal_quantized_cpu(const Tensor &input, const Tensor &shifts, int64_t T, int64_t padding_mode) {
+    TORCH_CHECK(input.device().is_cpu() && shifts.device().is_cpu(), "temporal_shift_quantized_cpu: expected CPU tensors");
+    temporal_quantized_check(input, shifts, T, padding_mode);
+    const at::ScalarType st = input.scalar_type();
+    TORCH_CHECK(st == at::kQUInt8 || st == at::kQInt8 || st == at::kQInt32, "\"temporal_shift_quantized_cpu\" not implemented for '",
+                c10::toString(st), "'");
+    const Tensor t = input.contiguous();
+    Tensor out = at::_empty_affine_quantized(t.sizes(), t.options().memory_format(at::MemoryFormat::Contiguous), t.q_scale(),
+                                             t.q_zero_point(), c10::nullopt);
+    if (t.numel() == 0) return out;
+    const int64_t C = t.size(1), N = t.size(0) / T;
+    const size_t plane_bytes = static_cast<size_t>(t.numel() / (t.size(0) * C)) * t.element_size();
+    const Tensor table = shifts.detach().reshape({C}).to(at::kDouble).round().to(at::kLong).contiguous();
+    const int32_t zp = static_cast<int32_t>(t.q_zero_point());
+    temporal_planes(static_cast<const char *>(t.data_ptr()), static_cast<char *>(out.data_ptr()), N, T, C, plane_bytes,
+                    table.data_ptr<int64_t>(), +1, padding_mode, t.element_size(), t.element_size() == 1 ? (zp & 0xff) : zp);
+    return out;
 }
 
 template <int ND> Tensor qshift_forward_cpu(const Tensor &input, const Tensor &weights, const Tensor &borders,
@@ -517,6 +547,7 @@ TORCH_LIBRARY_IMPL(torchshifts, CPU, m) {
 }
 
 TORCH_LIBRARY_IMPL(torchshifts, QuantizedCPU, m) {
+    m.impl("temporal_shift_quantized", TORCH_FN(temporal_quantized_cpu));
     m.impl("_shift1d_forward", TORCH_FN(qshift_forward_cpu<1>));
     m.impl("_shift1d_backward", TORCH_FN(qshift_backward_cpu));
     m.impl("_shift2d_forward", TORCH_FN(qshift_forward_cpu<2>));

@@ -1,4 +1,7 @@
 """Quantized functional wrappers (reference torchshifts/quantized/functional.py:3-15)."""
+import torch
+
+from torchshifts.extension import _assert_has_ops
 from torchshifts.functional import shift1d_func, shift2d_func, shift3d_func
 
 
@@ -18,3 +21,15 @@ def shift2d_quantized(input, weight, padding_mode, cut_borders=None):
 
 def shift3d_quantized(input, weight, padding_mode, cut_borders=None):
     return _quantized('shift3d_quantized', shift3d_func, input, weight, padding_mode, cut_borders)
+
+
+def temporal_shift_quantized(input, shifts, n_segment, padding_mode=0):
+    """The temporal shift (torchshifts.functional.temporal_shift_func) of a per-tensor quantized [N * n_segment, C, ...] tensor
+    (quint8, qint8, qint32; 2 to 5 dims): the same gather on the int_repr, with the input's zero point where zeros padding fills
+    (it dequantizes to exactly 0).  Scale and zero point are the input's -- nothing is requantized -- and the result is
+    contiguous.  `shifts`: [n_channels] or [n_channels, 1] integers, or floats rounded half to even.  On HIP tensors the table
+    is converted to int32, exact for every shift (the float op's table has the tensor's 16-bit dtype).  No gradient."""
+    if not input.is_quantized:
+        raise ValueError("Input to 'temporal_shift_quantized' must be quantized!")
+    _assert_has_ops()
+    return torch.ops.torchshifts.temporal_shift_quantized(input, shifts, int(n_segment), int(padding_mode))

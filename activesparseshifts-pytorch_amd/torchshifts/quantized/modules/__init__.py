@@ -1,6 +1,7 @@
 new_quant_mapping = {}
 
-from .shifts import Shift1d, Shift2d, Shift3d  # noqa: E402
+from .shifts import Shift1d, Shift2d, Shift3d, TemporalShift  # noqa: E402
 import torchshifts.modules.shifts as shifts  # noqa: E402
 
-new_quant_mapping.update({shifts.Shift1d: Shift1d, shifts.Shift2d: Shift2d, shifts.Shift3d: Shift3d})
+new_quant_mapping.update({shifts.Shift1d: Shift1d, shifts.Shift2d: Shift2d, shifts.Shift3d: Shift3d,
+                          shifts.TemporalShift: TemporalShift, shifts.LearnableTemporalShift: TemporalShift})

@@ -20,7 +20,7 @@ import torch
 
 import torchshifts.modules.shifts as shifts
 from torchshifts.functional import shift1d_pool_func, shift2d_pool_func, shift3d_pool_func
-from torchshifts.quantized.functional import shift1d_quantized, shift2d_quantized, shift3d_quantized
+from torchshifts.quantized.functional import shift1d_quantized, shift2d_quantized, shift3d_quantized, temporal_shift_quantized
 
 _POOL_FUNCS = {1: shift1d_pool_func, 2: shift2d_pool_func, 3: shift3d_pool_func}
 
@@ -141,3 +141,28 @@ class Shift3d(_QuantizedShiftMixin, shifts.Shift3d):
     def __init__(self, in_channels, padding='zeros'):
         super().__init__(in_channels, padding, 1, 0, False)
         self._init_quantized()
+
+
+class TemporalShift(shifts.TemporalShift):
+    """Quantized Temporal Shift Module: the float TemporalShift on per-tensor quantized tensors (quint8, qint8, qint32).  The table
+    is the same persistent int64 buffer `shifts`, so a float TemporalShift checkpoint loads as it is; there are no quantized
+    weights, because the table holds integers already.  The output keeps the input's scale and zero point, and zeros padding
+    fills with the zero point.  On HIP tensors the table is passed as int32: every shift is exact.
+
+    forward(x) -> output, the tensor alone.  from_float converts a TemporalShift, or a non-active LearnableTemporalShift
+    (frozen through TemporalShift.from_shift: round(weight), half to even); an active one interpolates and raises ValueError.
+    """
+
+    def forward(self, input):
+        return temporal_shift_quantized(input, self.shifts, self.n_segment, self.padding)
+
+    def _get_name(self):
+        return 'QuantizedTemporalShift'
+
+    @classmethod
+    def from_float(cls, mod):
+        if isinstance(mod, shifts.LearnableTemporalShift):
+            mod = shifts.TemporalShift.from_shift(mod)
+        assert isinstance(mod, shifts.TemporalShift), 'expected a TemporalShift or LearnableTemporalShift module'
+        qshift = cls(mod.n_segment, mod.in_channels, fold_div=mod.fold_div, shifts=mod.shifts.detach().cpu(), padding=rp_dict[mod.padding])
+        return qshift.to(mod.shifts.device)

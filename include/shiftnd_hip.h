@@ -210,6 +210,12 @@ SHIFTND_API int shiftnd_backward_serves_channels_last(const shiftnd_problem *p, 
  * segment_forward_ragged otherwise; SHIFTND_PATH_PLANE), for any [C, ndim] table -- planes whose channel also shifts an inner dim are
  * gathered element by element inside the same kernel.  So is shiftnd_backward's x == NULL form on such strides (whole window).  Every
  * other call with these strides keeps the strided kernels.
+ *
+ * shiftnd_forward_quantized takes the same route under the same conditions: I8 / U8 / I32 tensors with an I8 / U8 / I32 table, the
+ * shift of a row its entries minus w_zero_point, a filled plane the input's zero point.  One-byte elements are streamed in units of
+ * one byte (planes of an odd number of bytes, bases on any byte; a one-byte tensor of 2^31 - 16 bytes or more keeps the strided
+ * kernel), and the kernel names and the path are those above.  Tensors the channel-fastest kernels take first (inner == 1: memory
+ * order N, S0, C is channels-last) stay with them, as for floats.
  */
 SHIFTND_API int shiftnd_forward(const shiftnd_problem *p,
                     const void *x, const int64_t x_strides[5],
