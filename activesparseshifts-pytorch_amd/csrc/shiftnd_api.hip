@@ -268,8 +268,10 @@ int forward_common(const shiftnd_problem *p, const void *x, const int64_t *xs, c
 }
 
 // ---- SHIFTND_SHIFT_DIM0: the learnable temporal shift (shiftnd_tshift.hip).  `weights` / `grad_w` are [C] arrays and the shift acts
-// on spatial dim 0 of dense segment-major tensors.  No routing and no fallback: the call is served by the tshift kernels or refused
-// before anything is launched.  -> the problem without the flag bits in `q`, the weights' type in `wkind`
+// on spatial dim 0 of dense segment-major tensors; the forward's sparse shift also takes dense channels-last tensors (the fixed
+// temporal shift of an NHWC tensor, shiftnd_frames.hip), and so does shiftnd_forward_quantized.  No routing and no fallback: the call
+// is served by the kernels of its layout or refused before anything is launched.
+// -> the problem without the flag bits in `q`, the weights' type in `wkind`
 int tshift_problem(const shiftnd_problem *p, shiftnd_problem &q, int &wkind) {
     shiftnd_problem r = *p;
     r.dtype = p->dtype & ~SHIFTND_SHIFT_DIM0;
@@ -286,15 +288,44 @@ int tshift_forward_call(const shiftnd_problem *p, const void *x, const int64_t *
     Geometry g;
     rc = build_geometry(&q, xs, os, nullptr, g);
     if (rc != SHIFTND_OK) return rc;
-    if (!tshift_geometry_ok(g, q.dtype)) return SHIFTND_ERR_INVALID_ARGUMENT;
+    // two layouts are served: segment-major (the tshift kernels, sparse and interpolating) and, for the sparse shift, channels-last
+    // (shiftnd_frames.hip).  A tensor both describe (planes or channels of size 1) stays with the tshift kernels
+    const bool segment_sizes = tshift_geometry_ok(g, q.dtype), frames_sizes = frames_geometry_ok(g, q.dtype);
+    if (!segment_sizes && !frames_sizes) return SHIFTND_ERR_INVALID_ARGUMENT;
     if (empty_problem(g)) {
         g_last_path = SHIFTND_PATH_EMPTY;
         return SHIFTND_OK;
     }
     if (!x || !w || !out) return SHIFTND_ERR_INVALID_ARGUMENT;
-    if (!tshift_tensor_ok(g, q.dtype, x, g.xs) || !tshift_tensor_ok(g, q.dtype, out, g.os)) return SHIFTND_ERR_INVALID_ARGUMENT;
-    g_last_path = SHIFTND_PATH_PLANE;
-    return finish(tshift_forward(g, q.dtype, x, w, wkind, out, static_cast<hipStream_t>(stream)));
+    if (segment_sizes && tshift_tensor_ok(g, q.dtype, x, g.xs) && tshift_tensor_ok(g, q.dtype, out, g.os)) {
+        g_last_path = SHIFTND_PATH_PLANE;
+        return finish(tshift_forward(g, q.dtype, x, w, wkind, out, static_cast<hipStream_t>(stream)));
+    }
+    if (frames_sizes && frames_tensor_ok(g, q.dtype, x, g.xs) && frames_tensor_ok(g, q.dtype, out, g.os)) {
+        g_last_path = SHIFTND_PATH_CL;
+        return finish(frames_forward(g, q.dtype, x, w, wkind, 0, 0ull, out, static_cast<hipStream_t>(stream)));
+    }
+    return SHIFTND_ERR_INVALID_ARGUMENT;
+}
+
+// shiftnd_forward_quantized under the flag: the channels-last layout alone (I8 / U8 / I32 tensors, an integer [C] table)
+int frames_quantized_call(const shiftnd_problem *p, const void *x, const int64_t *xs, const void *wq, int wq_dtype, int64_t wzp,
+                          uint64_t fill, void *out, const int64_t *os, void *stream) {
+    shiftnd_problem q = *p;
+    q.dtype = p->dtype & ~SHIFTND_SHIFT_DIM0;
+    q.active = 0;
+    Geometry g;
+    const int rc = build_geometry(&q, xs, os, nullptr, g);
+    if (rc != SHIFTND_OK) return rc;
+    if (!frames_geometry_ok(g, q.dtype)) return SHIFTND_ERR_INVALID_ARGUMENT;
+    if (empty_problem(g)) {
+        g_last_path = SHIFTND_PATH_EMPTY;
+        return SHIFTND_OK;
+    }
+    if (!x || !wq || !out) return SHIFTND_ERR_INVALID_ARGUMENT;
+    if (!frames_tensor_ok(g, q.dtype, x, g.xs) || !frames_tensor_ok(g, q.dtype, out, g.os)) return SHIFTND_ERR_INVALID_ARGUMENT;
+    g_last_path = SHIFTND_PATH_CL;
+    return finish(frames_forward(g, q.dtype, x, wq, wq_dtype, wzp, fill, out, static_cast<hipStream_t>(stream)));
 }
 
 int tshift_backward_call(const shiftnd_problem *p, const void *go, const int64_t *gos, const void *x, const int64_t *xs, const void *w,
@@ -453,14 +484,17 @@ int shiftnd_forward_quantized(const shiftnd_problem *p, const void *x, const int
                               int32_t wq_dtype, int64_t w_zero_point, int64_t x_zero_point, void *out,
                               const int64_t out_strides[5], void *stream) {
     if (!p || !x_strides || !out_strides) return SHIFTND_ERR_INVALID_ARGUMENT;
-    if (!is_quant_dtype(p->dtype) || !is_quant_dtype(wq_dtype)) return SHIFTND_ERR_UNSUPPORTED_DTYPE;
+    const int dtype = p->dtype & ~SHIFTND_SHIFT_DIM0;   // (the flag with a float dtype or with SHIFTND_WEIGHTS_F32: no quantized dtype)
+    if (!is_quant_dtype(dtype) || !is_quant_dtype(wq_dtype)) return SHIFTND_ERR_UNSUPPORTED_DTYPE;
     shiftnd_problem q = *p;
     q.active = 0;
     // fill value = input zero point, as the element type's bit pattern
     uint64_t fill = 0;
-    if (p->dtype == SHIFTND_I8) fill = static_cast<uint8_t>(static_cast<int8_t>(x_zero_point));
-    else if (p->dtype == SHIFTND_U8) fill = static_cast<uint8_t>(x_zero_point);
+    if (dtype == SHIFTND_I8) fill = static_cast<uint8_t>(static_cast<int8_t>(x_zero_point));
+    else if (dtype == SHIFTND_U8) fill = static_cast<uint8_t>(x_zero_point);
     else fill = static_cast<uint32_t>(static_cast<int32_t>(x_zero_point));
+    if (p->dtype & SHIFTND_SHIFT_DIM0)
+        return frames_quantized_call(p, x, x_strides, wq, wq_dtype, w_zero_point, fill, out, out_strides, stream);
     return forward_common(&q, x, x_strides, wq, wq_dtype, w_zero_point, fill, out, out_strides, stream);
 }
 

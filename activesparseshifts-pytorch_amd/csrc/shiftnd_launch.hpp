@@ -230,6 +230,15 @@ size_t tshift_backward_workspace(const Geometry &g, int dtype);
 int tshift_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw,
                     void *workspace, hipStream_t st);
 
+// ---- the temporal shift of channels-last tensors (shiftnd_frames.hip; SHIFTND_SHIFT_DIM0 on a channels-last view): the sparse shift
+// along S0 of float and quantized (I8, U8, I32) tensors in memory order N, S0, S1, S2, C, `w` a [C] table, whole window; channel
+// pieces are copied from the same pixel of another frame or filled with `fill_bits`.  frames_geometry_ok: the sizes (and
+// active == 0); frames_tensor_ok: one tensor's base and strides (normalised order).  No fallback: every such call is served.
+bool frames_geometry_ok(const Geometry &g, int dtype);
+bool frames_tensor_ok(const Geometry &g, int dtype, const void *p, const int64_t *strides);
+int frames_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, int64_t wzp, uint64_t fill_bits, void *out,
+                   hipStream_t st);
+
 // ---- layout change (shiftnd_transpose.hip): dst[n][c][r] = src[n][r][c], dense tensors ---------------------------
 int transpose_planes(const void *src, void *dst, int64_t N, int64_t rows, int64_t cols, int esize, hipStream_t st);
 

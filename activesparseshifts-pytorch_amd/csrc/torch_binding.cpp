@@ -1050,6 +1050,146 @@ Tensor temporal_quantized_hip(const Tensor &input_, const Tensor &shifts, int64_
     return out;
 }
 
+// ---- channels-last temporal shift: temporal_shift_cl / _temporal_shift_cl_backward / temporal_shift_quantized_cl ----------------
+// The values of temporal_shift / temporal_shift_quantized with the layout of the argument kept (memory_format=torch.preserve_format
+// in the Python wrappers): a dense channels-last tensor (is_channels_last_dense: 3 to 5 dims, unit channel stride) comes back in its
+// own strides, every other tensor exactly as the plain ops return it.  On HIP tensors a channels-last tensor is ONE flagged C-ABI
+// call on the tensor as it lies (SHIFTND_SHIFT_DIM0 on the strides {T*M*C, 1, M*C, C}: shiftnd_frames.hip), no layout change in
+// either direction; the gradient is the same call on the gradient under the negated table.  On CPU tensors the plain op computes
+// and the result is laid out in the argument's strides.
+Tensor empty_with_strides_of(const Tensor &t) {
+    if (!t.is_quantized()) return at::empty_strided(t.sizes(), t.strides(), t.options());
+    // quantized: dense storage in memory order (dim 0, spatial dims, channels), seen with the channels as dim 1
+    std::vector<int64_t> sizes{t.size(0)}, order{0, t.dim() - 1};
+    for (int64_t d = 2; d < t.dim(); ++d) {
+        sizes.push_back(t.size(d));
+        order.push_back(d - 1);
+    }
+    sizes.push_back(t.size(1));
+    Tensor out = at::_empty_affine_quantized(sizes, t.options().memory_format(at::MemoryFormat::Contiguous), t.q_scale(), t.q_zero_point(),
+                                             c10::nullopt)
+                     .permute(order);
+    return out.strides() == t.strides() ? out : out.as_strided(t.sizes(), t.strides());   // (dims of size 1: the argument's own strides)
+}
+
+Tensor in_layout_of(const Tensor &values, const Tensor &like) {
+    if (!is_channels_last_dense(like)) return values;
+    Tensor out = empty_with_strides_of(like);
+    out.copy_(values);
+    return out;
+}
+
+struct TemporalShiftClFunction : public torch::autograd::Function<TemporalShiftClFunction> {
+    static variable_list forward(AutogradContext *ctx, const Tensor &input, const Tensor &shifts, int64_t n_segment,
+                                 int64_t padding_mode) {
+        at::AutoDispatchBelowADInplaceOrView guard;
+        auto output = call_temporal("torchshifts::temporal_shift_cl", input, shifts, n_segment, padding_mode);
+        ctx->saved_data["n_segment"] = n_segment;
+        ctx->saved_data["padding_mode"] = padding_mode;
+        ctx->save_for_backward({shifts.detach()});
+        return {output};
+    }
+    static variable_list backward(AutogradContext *ctx, const variable_list &grad_output) {
+        auto saved = ctx->get_saved_variables();
+        return {call_temporal("torchshifts::_temporal_shift_cl_backward", grad_output[0], saved[0], ctx->saved_data["n_segment"].toInt(),
+                              ctx->saved_data["padding_mode"].toInt()),
+                Tensor(), Tensor(), Tensor()};
+    }
+};
+
+struct TemporalShiftClBackwardFunction : public torch::autograd::Function<TemporalShiftClBackwardFunction> {
+    static variable_list forward(AutogradContext *ctx, const Tensor &grad, const Tensor &shifts, int64_t n_segment,
+                                 int64_t padding_mode) {
+        at::AutoDispatchBelowADInplaceOrView guard;
+        return {call_temporal("torchshifts::_temporal_shift_cl_backward", grad, shifts, n_segment, padding_mode)};
+    }
+    static variable_list backward(AutogradContext *, const variable_list &) {
+        TORCH_CHECK(0, "double backwards on temporal_shift_cl not supported");
+    }
+};
+
+Tensor temporal_cl_autograd(const Tensor &input, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    temporal_check(input, shifts, n_segment, padding_mode);
+    return TemporalShiftClFunction::apply(input, shifts, n_segment, padding_mode)[0];
+}
+
+Tensor temporal_cl_autograd_backward(const Tensor &grad, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    temporal_check(grad, shifts, n_segment, padding_mode);
+    return TemporalShiftClBackwardFunction::apply(grad, shifts, n_segment, padding_mode)[0];
+}
+
+// CPU tensors (reached below the Autograd key): the plain ops' values in the argument's layout
+Tensor temporal_cl_forward_cpu(const Tensor &input, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    return in_layout_of(call_temporal("torchshifts::temporal_shift", input, shifts, n_segment, padding_mode), input);
+}
+Tensor temporal_cl_backward_cpu(const Tensor &grad, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    return in_layout_of(call_temporal("torchshifts::_temporal_shift_backward", grad, shifts, n_segment, padding_mode), grad);
+}
+Tensor temporal_quantized_cl_cpu(const Tensor &input, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    return in_layout_of(call_temporal("torchshifts::temporal_shift_quantized", input, shifts, n_segment, padding_mode), input);
+}
+
+// the problem [N, C, T, M] of a dense channels-last [N*T, C, ...] tensor and its strides {T*M*C, 1, M*C, C}
+void temporal_cl_problem(const Tensor &t, int64_t T, int64_t padding_mode, int dtype, shiftnd_problem &p, int64_t st[5]) {
+    const int64_t C = t.size(1), N = t.size(0) / T, M = t.numel() / (t.size(0) * C);
+    TORCH_CHECK(T <= INT32_MAX && M <= INT32_MAX, "temporal_shift: n_segment and the frame size must fit 32 bits");
+    p.ndim = 2;
+    p.dtype = dtype | SHIFTND_SHIFT_DIM0;
+    p.padding_mode = static_cast<int32_t>(padding_mode);
+    p.active = 0;
+    const int64_t sizes[5] = {N, C, T, M, 1}, strides[5] = {T * M * C, 1, M * C, C, 0};
+    const int32_t borders[6] = {0, static_cast<int32_t>(T), 0, static_cast<int32_t>(M), 0, 1};
+    for (int i = 0; i < 5; ++i) p.sizes[i] = sizes[i], st[i] = strides[i];
+    for (int i = 0; i < 6; ++i) p.borders[i] = borders[i];
+}
+
+// a dense channels-last tensor: ONE flagged shiftnd_forward on the tensor as it lies; backward: the same call under the negated
+// table (grad_x[t] = grad_out[pad(t + s)]).  The [C] table is built on the device without a host sync: fp32 for 16-bit tensors
+// (SHIFTND_WEIGHTS_F32: every shift exact), the tensor's dtype for fp32 / fp64.  Every other tensor: the plain op.
+Tensor temporal_cl_hip(const Tensor &t, const Tensor &shifts, int64_t n_segment, int64_t padding_mode, bool backward) {
+    if (!is_channels_last_dense(t)) return temporal_hip(t, shifts, n_segment, padding_mode, backward);
+    TORCH_CHECK(t.is_cuda(), "temporal_shift_cl: expected a CUDA tensor");
+    temporal_check(t, shifts, n_segment, padding_mode);
+    c10::DeviceGuard device_guard(t.device());
+    const bool half = t.scalar_type() == at::kHalf || t.scalar_type() == at::kBFloat16;
+    const int dtype = to_shiftnd_dtype(t.scalar_type(), "temporal_shift_cl_cuda") | (half ? SHIFTND_WEIGHTS_F32 : 0);
+    Tensor out = at::empty_strided(t.sizes(), t.strides(), t.options());
+    Tensor w = shifts.detach().reshape({t.size(1)}).to(half ? at::kFloat : t.scalar_type());
+    w = backward ? w.neg() : w.contiguous();
+    shiftnd_problem p;
+    int64_t st[5];
+    temporal_cl_problem(t, n_segment, padding_mode, dtype, p, st);
+    const int rc = shiftnd_forward(&p, t.data_ptr(), st, w.data_ptr(), out.data_ptr(), st, current_stream(t));
+    TORCH_CHECK(rc == SHIFTND_OK, "temporal_shift_cl (HIP): ", shiftnd_status_string(rc));
+    return out;
+}
+
+Tensor temporal_cl_forward_hip(const Tensor &input, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    return temporal_cl_hip(input, shifts, n_segment, padding_mode, false);
+}
+Tensor temporal_cl_backward_hip(const Tensor &grad, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    return temporal_cl_hip(grad, shifts, n_segment, padding_mode, true);
+}
+
+// ... of a quantized tensor: ONE flagged shiftnd_forward_quantized, an int32 [C] table, the zero point as the fill
+Tensor temporal_quantized_cl_hip(const Tensor &t, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    if (!is_channels_last_dense(t)) return temporal_quantized_hip(t, shifts, n_segment, padding_mode);
+    TORCH_CHECK(t.is_cuda(), "temporal_shift_quantized_cl: expected a CUDA tensor");
+    temporal_quantized_check(t, shifts, n_segment, padding_mode);
+    c10::DeviceGuard device_guard(t.device());
+    const int dtype = quant_dtype(t.scalar_type(), "temporal_shift_quantized_cl_cuda");
+    Tensor out = empty_with_strides_of(t);
+    const Tensor s = shifts.detach().reshape({t.size(1)});
+    const Tensor w = (at::isFloatingType(s.scalar_type()) ? at::round(s) : s).to(at::kInt).contiguous();   // (half to even)
+    shiftnd_problem p;
+    int64_t st[5];
+    temporal_cl_problem(t, n_segment, padding_mode, dtype, p, st);
+    const int rc = shiftnd_forward_quantized(&p, t.data_ptr(), st, w.data_ptr(), SHIFTND_I32, 0, t.q_zero_point(), out.data_ptr(), st,
+                                             current_stream(t));
+    TORCH_CHECK(rc == SHIFTND_OK, "temporal_shift_quantized_cl (HIP): ", shiftnd_status_string(rc));
+    return out;
+}
+
 // ---- learnable temporal shift: a TRAINED per-channel shift across the frames of [N*T, C, ...] ------------------------------------
 // temporal_shift_learnable(input, weights, n_segment, padding_mode, active_flag) ==
 //     shift1d(x.view(N, T, C, M).permute(0, 3, 2, 1).reshape(N*M, C, T), weights.view(C, 1), padding_mode, active_flag)
@@ -1274,6 +1414,10 @@ TORCH_LIBRARY(torchshifts, m) {
     m.def("torchshifts::_temporal_shift_backward(Tensor grad, Tensor shifts, int n_segment, int padding_mode) -> Tensor");
     // ... of a per-tensor quantized tensor: the same gather on the int_repr, the zero point as the fill (QuantizedCPU / QuantizedCUDA)
     m.def("torchshifts::temporal_shift_quantized(Tensor input, Tensor shifts, int n_segment, int padding_mode) -> Tensor");
+    // ... with the argument's layout kept: a dense channels-last tensor comes back channels-last (memory_format=torch.preserve_format)
+    m.def("torchshifts::temporal_shift_cl(Tensor input, Tensor shifts, int n_segment, int padding_mode) -> Tensor");
+    m.def("torchshifts::_temporal_shift_cl_backward(Tensor grad, Tensor shifts, int n_segment, int padding_mode) -> Tensor");
+    m.def("torchshifts::temporal_shift_quantized_cl(Tensor input, Tensor shifts, int n_segment, int padding_mode) -> Tensor");
     // learnable temporal shift: a trained per-channel shift across the frames, sparse or interpolating (not in the reference)
     m.def("torchshifts::temporal_shift_learnable(Tensor input, Tensor weights, int n_segment, int padding_mode, bool active_flag) -> Tensor", &tsl_public);
     m.def("torchshifts::_temporal_shift_learnable_forward(Tensor input, Tensor weights, int n_segment, int padding_mode, bool active_flag) -> Tensor");
@@ -1285,6 +1429,8 @@ TORCH_LIBRARY_IMPL(torchshifts, Autograd, m) {
     m.impl("_temporal_shift_learnable_backward", TORCH_FN(tsl_autograd_backward));
     m.impl("temporal_shift", TORCH_FN(temporal_autograd));
     m.impl("_temporal_shift_backward", TORCH_FN(temporal_autograd_backward));
+    m.impl("temporal_shift_cl", TORCH_FN(temporal_cl_autograd));
+    m.impl("_temporal_shift_cl_backward", TORCH_FN(temporal_cl_autograd_backward));
     m.impl("_shift1d_fixed_backward", TORCH_FN(fixed_autograd_backward<1>));
     m.impl("_shift2d_fixed_backward", TORCH_FN(fixed_autograd_backward<2>));
     m.impl("_shift3d_fixed_backward", TORCH_FN(fixed_autograd_backward<3>));
@@ -1307,6 +1453,8 @@ TORCH_LIBRARY_IMPL(torchshifts, Autograd, m) {
 
 // CPU tensors: the reference's two-step sequence (shift op on the CPU key, then ATen's pool)
 TORCH_LIBRARY_IMPL(torchshifts, CPU, m) {
+    m.impl("temporal_shift_cl", TORCH_FN(temporal_cl_forward_cpu));
+    m.impl("_temporal_shift_cl_backward", TORCH_FN(temporal_cl_backward_cpu));
     m.impl("_temporal_shift_learnable_forward", TORCH_FN(tsl_forward_cpu));
     m.impl("_temporal_shift_learnable_backward", TORCH_FN(tsl_backward_cpu));
     m.impl("_shift1d_pool_forward", TORCH_FN(pool_forward_composed<1>));
@@ -1322,6 +1470,8 @@ TORCH_LIBRARY_IMPL(torchshifts, CUDA, m) {
     m.impl("_temporal_shift_learnable_backward", TORCH_FN(tsl_backward_hip));
     m.impl("temporal_shift", TORCH_FN(temporal_forward_hip));
     m.impl("_temporal_shift_backward", TORCH_FN(temporal_backward_hip));
+    m.impl("temporal_shift_cl", TORCH_FN(temporal_cl_forward_hip));
+    m.impl("_temporal_shift_cl_backward", TORCH_FN(temporal_cl_backward_hip));
     m.impl("_shift1d_fixed_backward", TORCH_FN(shift_fixed_backward_hip<1>));
     m.impl("_shift2d_fixed_backward", TORCH_FN(shift_fixed_backward_hip<2>));
     m.impl("_shift3d_fixed_backward", TORCH_FN(shift_fixed_backward_hip<3>));
@@ -1342,8 +1492,13 @@ TORCH_LIBRARY_IMPL(torchshifts, CUDA, m) {
     m.impl("_shift3d_pool_backward", TORCH_FN(pool_backward_hip<3>));
 }
 
+TORCH_LIBRARY_IMPL(torchshifts, QuantizedCPU, m) {
+    m.impl("temporal_shift_quantized_cl", TORCH_FN(temporal_quantized_cl_cpu));
+}
+
 TORCH_LIBRARY_IMPL(torchshifts, QuantizedCUDA, m) {
     m.impl("temporal_shift_quantized", TORCH_FN(temporal_quantized_hip));
+    m.impl("temporal_shift_quantized_cl", TORCH_FN(temporal_quantized_cl_hip));
     m.impl("_shift1d_forward", TORCH_FN(qshift_forward_hip<1>));
     m.impl("_shift1d_backward", TORCH_FN(qshift_backward));
     m.impl("_shift2d_forward", TORCH_FN(qshift_forward_hip<2>));

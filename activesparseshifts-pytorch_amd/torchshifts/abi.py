@@ -16,6 +16,7 @@ _LIB_PATH = os.environ.get("SHIFTND_HIP_LIB") or os.path.join(os.path.dirname(os
 F32, F64, F16, BF16, I8, U8, I32 = range(7)
 WEIGHTS_F32 = 0x100   # SHIFTND_WEIGHTS_F32: OR-ed onto F16 / BF16 -- fp32 weights (and grad_w) with 16-bit tensors
 SHIFT_DIM0 = 0x200    # SHIFTND_SHIFT_DIM0: weights / grad_w are [C]; a 1-D shift along spatial dim 0 of segment-major tensors
+#                       (forward, sparse shift, and forward_quantized: of dense channels-last tensors too)
 PATH_NONE, PATH_EMPTY, PATH_PLANE, PATH_STRIDED, PATH_SWEEP, PATH_CL = range(6)
 
 DTYPES = {torch.float32: F32, torch.float64: F64, torch.float16: F16, torch.bfloat16: BF16,
@@ -130,7 +131,8 @@ def check_borders(sizes, user, ndim):
 
 def problem(x, pad, active, borders, dtype=None, w=None, shift_dim0=False):
     """w: the weights of the call, if it has float weights -- fp32 weights with an fp16 / bf16 `x` set WEIGHTS_F32 (mixed precision);
-    shift_dim0: set SHIFT_DIM0 (the learnable temporal shift: w is [C])"""
+    shift_dim0: set SHIFT_DIM0 (the temporal shift: w is [C] and acts on spatial dim 0; x a segment-major view, or, for the
+    sparse forward and the quantized forward, a dense channels-last view [N, C, T, M] with strides {T*M*C, 1, M*C, C})"""
     p = Problem()
     p.ndim = x.dim() - 2
     p.dtype = DTYPES[x.dtype] if dtype is None else dtype
@@ -159,7 +161,8 @@ def _stream():
 
 def forward(x, w, pad, active, borders=None, out=None, shift_dim0=False):
     """x, w: device tensors (float dtypes; w of x's dtype, or fp32 with an fp16 / bf16 x).  Returns a new contiguous output (or
-    fills `out`).  shift_dim0: the flagged call (w [C]; x and out segment-major views)."""
+    fills `out`).  shift_dim0: the flagged call (w [C]; x and out segment-major views, or -- active False -- both dense
+    channels-last views, memory order N, S0, S1, S2, C: pass `out`, a new output is contiguous)."""
     p = problem(x, pad, active, borders, w=w, shift_dim0=shift_dim0)
     if out is None:
         out = _new(out_shape(x, borders), x)
@@ -207,9 +210,10 @@ def backward_input(grad_out, w, input_shape, pad, borders=None, grad_x=None, wor
     return grad_x
 
 
-def forward_quantized(xq, wq, w_zero_point, x_zero_point, pad, borders=None, out=None):
-    """xq: int8/uint8/int32 device tensor (int_repr); wq: int8/uint8/int32 device tensor [C, nd]."""
-    p = problem(xq, pad, False, borders)
+def forward_quantized(xq, wq, w_zero_point, x_zero_point, pad, borders=None, out=None, shift_dim0=False):
+    """xq: int8/uint8/int32 device tensor (int_repr); wq: int8/uint8/int32 device tensor [C, nd].  shift_dim0: the flagged call
+    (wq [C]; xq and `out` dense channels-last views, memory order N, S0, S1, S2, C)."""
+    p = problem(xq, pad, False, borders, shift_dim0=shift_dim0)
     if out is None:
         out = _new(out_shape(xq, borders), xq)
     wq = wq.contiguous()

@@ -162,10 +162,20 @@ def shift3d_fixed_pool_func(input: Tensor, shifts: Tensor, padding_mode: int, po
 # weights and the tables of shift{N}d_fixed_func.  On HIP tensors the table is converted to the input's dtype, like those tables:
 # exact for |shift| <= 256 in bfloat16 and <= 2048 in float16 (clips of more frames than that in a 16-bit tensor, or larger shifts
 # under periodic / reflect / symmetric padding, would be rounded; the CPU op uses the integers as they are).
-def temporal_shift_func(input: Tensor, shifts: Tensor, n_segment: int, padding_mode: int = 0) -> Tensor:
+#
+# memory_format: torch.contiguous_format (the default) returns a contiguous result whatever the input's layout.  With
+# torch.preserve_format a dense channels-last input (3 to 5 dims, unit channel stride, not contiguous: torch.channels_last,
+# torch.channels_last_3d, or [N * n_segment, C, L] with strides (L * C, 1, C)) comes back in its own strides, and x.grad takes the
+# layout of the incoming gradient by the same rule; every other input gives what the default gives.  On HIP tensors the
+# channels-last tensor is shifted as it lies, one pass with no layout change in either direction, and its table is float32 for
+# 16-bit tensors: exact for every shift.
+def temporal_shift_func(input: Tensor, shifts: Tensor, n_segment: int, padding_mode: int = 0,
+                        memory_format: torch.memory_format = torch.contiguous_format) -> Tensor:
     """Shift the channels of a [N * n_segment, C, ...] tensor (2 to 5 dims) across the n_segment frames of each clip."""
     name = "temporal_shift_func()"
     _assert_has_ops()
+    assert memory_format in (torch.contiguous_format, torch.preserve_format), \
+        f"{name} expected memory_format to be torch.contiguous_format or torch.preserve_format, but it is {memory_format}"
     assert padding_mode in [0, 1, 2, 3, 4], f"{name} expected padding_mode can be {_PADDING_DOC}"
     assert 2 <= len(input.shape) <= 5, f"{name}: expected a 2D to 5D tensor as input, but it is shape is {input.shape}"
     assert isinstance(n_segment, int) and n_segment >= 1 and input.shape[0] % n_segment == 0, \
@@ -178,6 +188,8 @@ def temporal_shift_func(input: Tensor, shifts: Tensor, n_segment: int, padding_m
     assert input.device == shifts.device, \
         (f"{name}: expected input and shifts to be on same device, but input is  on {input.device} "
          f"and shifts is on {shifts.device}")
+    if memory_format == torch.preserve_format:
+        return torch.ops.torchshifts.temporal_shift_cl(input, shifts, n_segment, padding_mode)
     return torch.ops.torchshifts.temporal_shift(input, shifts, n_segment, padding_mode)
 
 

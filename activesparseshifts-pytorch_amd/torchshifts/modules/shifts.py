@@ -298,13 +298,19 @@ class TemporalShift(nn.Module):
         shifts (tensor / list): [in_channels] integers that replace the default table (fold_div is then unused); floats are
             rounded half to even, not validated.  On HIP tensors |shift| <= 256 is exact in bfloat16, <= 2048 in float16.
         padding (str): 'zeros' | 'border' | 'periodic' | 'reflect' | 'symmetric'. Default 'zeros' (the published module).
+        memory_format: torch.contiguous_format (default: a contiguous output) or torch.preserve_format (a dense channels-last
+            input comes back channels-last, shifted as it lies on HIP tensors: for channels-last models).  A plain attribute,
+            not part of state_dict.
     forward(x) -> output, the tensor alone: the module sits inside nn.Sequential in front of a convolution.
     """
 
-    def __init__(self, n_segment, in_channels, fold_div=8, shifts=None, padding='zeros'):
+    def __init__(self, n_segment, in_channels, fold_div=8, shifts=None, padding='zeros', memory_format=torch.contiguous_format):
         super().__init__()
         assert padding.lower() in paddings_dict.keys(), f'incorrect padding option: {padding}'
         assert int(n_segment) >= 1, 'n_segment must be >= 1'
+        assert memory_format in (torch.contiguous_format, torch.preserve_format), \
+            f'memory_format must be torch.contiguous_format or torch.preserve_format, not {memory_format}'
+        self.memory_format = memory_format
         self.padding = paddings_dict[padding.lower()]
         self.n_segment = int(n_segment)
         self.in_channels = in_channels
@@ -339,12 +345,12 @@ class TemporalShift(nn.Module):
         return cls(module.n_segment, module.in_channels, shifts=table.cpu(), padding=pad).to(module.weight.device)
 
     def forward(self, input):
-        return temporal_shift_func(input, self.shifts, self.n_segment, self.padding)
+        return temporal_shift_func(input, self.shifts, self.n_segment, self.padding, self.memory_format)
 
     def extra_repr(self):
         pad = {v: k for k, v in paddings_dict.items()}[self.padding]
         return (f'n_segment={self.n_segment}, in_channels={self.in_channels}, fold_div={self.fold_div}, padding_method={pad}, '
-                'fixed integer shifts')
+                f'memory_format={self.memory_format}, fixed integer shifts')
 
 
 class LearnableTemporalShift(nn.Module):

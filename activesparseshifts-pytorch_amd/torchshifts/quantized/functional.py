@@ -23,13 +23,19 @@ def shift3d_quantized(input, weight, padding_mode, cut_borders=None):
     return _quantized('shift3d_quantized', shift3d_func, input, weight, padding_mode, cut_borders)
 
 
-def temporal_shift_quantized(input, shifts, n_segment, padding_mode=0):
+def temporal_shift_quantized(input, shifts, n_segment, padding_mode=0, memory_format=torch.contiguous_format):
     """The temporal shift (torchshifts.functional.temporal_shift_func) of a per-tensor quantized [N * n_segment, C, ...] tensor
     (quint8, qint8, qint32; 2 to 5 dims): the same gather on the int_repr, with the input's zero point where zeros padding fills
     (it dequantizes to exactly 0).  Scale and zero point are the input's -- nothing is requantized -- and the result is
     contiguous.  `shifts`: [n_channels] or [n_channels, 1] integers, or floats rounded half to even.  On HIP tensors the table
-    is converted to int32, exact for every shift (the float op's table has the tensor's 16-bit dtype).  No gradient."""
+    is converted to int32, exact for every shift (the float op's table has the tensor's 16-bit dtype).  No gradient.
+    memory_format=torch.preserve_format: a dense channels-last input comes back in its own strides (on HIP tensors shifted as it
+    lies, one pass); every other input, and the default torch.contiguous_format, give the contiguous result."""
     if not input.is_quantized:
         raise ValueError("Input to 'temporal_shift_quantized' must be quantized!")
     _assert_has_ops()
+    assert memory_format in (torch.contiguous_format, torch.preserve_format), \
+        f"temporal_shift_quantized expected memory_format to be torch.contiguous_format or torch.preserve_format, but it is {memory_format}"
+    if memory_format == torch.preserve_format:
+        return torch.ops.torchshifts.temporal_shift_quantized_cl(input, shifts, int(n_segment), int(padding_mode))
     return torch.ops.torchshifts.temporal_shift_quantized(input, shifts, int(n_segment), int(padding_mode))

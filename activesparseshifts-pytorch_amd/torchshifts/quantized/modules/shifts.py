@@ -151,10 +151,12 @@ class TemporalShift(shifts.TemporalShift):
 
     forward(x) -> output, the tensor alone.  from_float converts a TemporalShift, or a non-active LearnableTemporalShift
     (frozen through TemporalShift.from_shift: round(weight), half to even); an active one interpolates and raises ValueError.
+    memory_format is the float module's option (torch.preserve_format: a channels-last input comes back channels-last);
+    from_float carries the float module's value over.
     """
 
     def forward(self, input):
-        return temporal_shift_quantized(input, self.shifts, self.n_segment, self.padding)
+        return temporal_shift_quantized(input, self.shifts, self.n_segment, self.padding, self.memory_format)
 
     def _get_name(self):
         return 'QuantizedTemporalShift'
@@ -164,5 +166,6 @@ class TemporalShift(shifts.TemporalShift):
         if isinstance(mod, shifts.LearnableTemporalShift):
             mod = shifts.TemporalShift.from_shift(mod)
         assert isinstance(mod, shifts.TemporalShift), 'expected a TemporalShift or LearnableTemporalShift module'
-        qshift = cls(mod.n_segment, mod.in_channels, fold_div=mod.fold_div, shifts=mod.shifts.detach().cpu(), padding=rp_dict[mod.padding])
+        qshift = cls(mod.n_segment, mod.in_channels, fold_div=mod.fold_div, shifts=mod.shifts.detach().cpu(), padding=rp_dict[mod.padding],
+                     memory_format=mod.memory_format)
         return qshift.to(mod.shifts.device)

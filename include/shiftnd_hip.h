@@ -101,7 +101,29 @@ typedef enum shiftnd_dtype {
  *   shiftnd_last_path(): SHIFTND_PATH_PLANE).
  *   Errors, before anything is launched: the quantized types SHIFTND_ERR_UNSUPPORTED_DTYPE (the workspace query answers 0);
  *   ndim 1, a cut window, any other layout, a size beyond the limits, the x == NULL && grad_w == NULL form of shiftnd_backward:
- *   SHIFTND_ERR_INVALID_ARGUMENT.  Every other entry point refuses the flag as an unknown dtype.
+ *   SHIFTND_ERR_INVALID_ARGUMENT.  Every other entry point refuses the flag as an unknown dtype (shiftnd_forward_quantized: with
+ *   a float dtype; its own use of the flag is below).
+ *
+ * Channels-last tensors (the FIXED temporal shift of an NHWC video tensor): under the flag shiftnd_forward also takes x and out that
+ * are both dense in memory order N, S0, S1, S2, C (a dim of size 1 has no stride to check), element-aligned bases -- the video tensor
+ * [N*T, C, H, W] in channels-last memory, seen as {ndim 2, sizes N, C, T, M = H*W} with strides {T*M*C, 1, M*C, C}.  Strides alone
+ * cannot tell that call from a genuine 2-D shift of an NHWC tensor, which is why it is the flag that asks for it.
+ *   Accepted: p->active == 0 (the sparse shift: rint of the entry); ndim 2 or 3; the whole window; F32, F64, F16, BF16, the last two
+ *   also with SHIFTND_WEIGHTS_F32; every padding mode.  Bounds of the kernel's index arithmetic (64-bit byte offsets throughout;
+ *   32-bit frame and workgroup indices, the 32-bit padding map): N, C and S1 * S2 below 2^31, S0 below 2^30, N * S0 below 2^31,
+ *   N * S0 * ceil(S1 * S2 / 8) below 2^31 (the grid), the tensor below 2^46 bytes.  A tensor that both layouts describe (S1 * S2 == 1
+ *   or C == 1) stays with the tshift kernels.  Served by csrc/shiftnd_frames.hip without a fallback (shiftnd_last_kernel():
+ *   frames_forward for pixel rows -- C elements -- of whole 16-byte pieces at 16-byte-aligned bases, frames_forward_ragged
+ *   otherwise; shiftnd_last_path(): SHIFTND_PATH_CL): a thread copies its 16-byte piece of the rows from the same pixel of the
+ *   source frame, or fills it; a piece whose channels do not share one source frame is assembled element by element (exact, slow).
+ *   The input gradient of that shift is the same call on the gradient under the negated table (grad_x[t] = grad_out[pad(t + s)]);
+ *   shiftnd_backward does not take the layout.
+ *   shiftnd_forward_quantized honours the flag for this layout ALONE: I8 / U8 / I32 tensors, same sizes and limits; wq is a [C]
+ *   integer table of wq_dtype (shift = entry - w_zero_point), zeros padding fills with x_zero_point.  SHIFTND_WEIGHTS_F32 with a
+ *   quantized dtype, or a float dtype with the flag on that entry point: SHIFTND_ERR_UNSUPPORTED_DTYPE; segment-major quantized
+ *   tensors, a cut window, ndim 1, a size beyond the bounds: SHIFTND_ERR_INVALID_ARGUMENT.
+ *   Errors, before anything is launched: p->active == 1 on the channels-last layout, x and out in different layouts (channels-last
+ *   with segment-major or NCHW-dense), a size beyond the bounds: SHIFTND_ERR_INVALID_ARGUMENT.
  * Without the flag nothing changes.
  */
 #define SHIFTND_SHIFT_DIM0 0x200
