@@ -279,8 +279,69 @@ int tshift_problem(const shiftnd_problem *p, shiftnd_problem &q, int &wkind) {
     return SHIFTND_OK;
 }
 
+// ---- SHIFTND_SHIFT_DIM0 | SHIFTND_FRAMES: the same problem on dense channels-last tensors, all of them (shiftnd_frames_learn.hip; the
+// sparse forward is frames_forward).  The explicit bit takes every such call to the frame kernels -- also tensors that the
+// segment-major layout describes as well -- or refuses it.
+// -> the problem without the flag bits in `q`, the weights' type in `wkind`
+int frames_learn_problem(const shiftnd_problem *p, shiftnd_problem &q, int &wkind) {
+    shiftnd_problem r = *p;
+    r.dtype = p->dtype & ~SHIFTND_FRAMES;
+    return tshift_problem(&r, q, wkind);
+}
+
+bool empty_geometry(const Geometry &g) { return g.N == 0 || g.C == 0 || g.S[0] * g.S[1] * g.S[2] == 0; }
+
+int frames_learn_forward_call(const shiftnd_problem *p, const void *x, const int64_t *xs, const void *w, void *out, const int64_t *os,
+                              void *stream) {
+    shiftnd_problem q;
+    int wkind;
+    int rc = frames_learn_problem(p, q, wkind);
+    if (rc != SHIFTND_OK) return rc;
+    Geometry g;
+    rc = build_geometry(&q, xs, os, nullptr, g);
+    if (rc != SHIFTND_OK) return rc;
+    if (!frames_learn_geometry_ok(g, q.dtype)) return SHIFTND_ERR_INVALID_ARGUMENT;
+    if (empty_geometry(g)) {
+        g_last_path = SHIFTND_PATH_EMPTY;
+        return SHIFTND_OK;
+    }
+    if (!x || !w || !out) return SHIFTND_ERR_INVALID_ARGUMENT;
+    if (!frames_tensor_ok(g, q.dtype, x, g.xs) || !frames_tensor_ok(g, q.dtype, out, g.os)) return SHIFTND_ERR_INVALID_ARGUMENT;
+    g_last_path = SHIFTND_PATH_CL;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!g.active) return finish(frames_forward(g, q.dtype, x, w, wkind, 0, 0ull, out, st));
+    return finish(frames_active_forward(g, q.dtype, x, w, wkind, out, st));
+}
+
+int frames_learn_backward_call(const shiftnd_problem *p, const void *go, const int64_t *gos, const void *x, const int64_t *xs,
+                               const void *w, void *gx, const int64_t *gxs, void *gw, void *workspace, size_t workspace_bytes,
+                               void *stream) {
+    shiftnd_problem q;
+    int wkind;
+    int rc = frames_learn_problem(p, q, wkind);
+    if (rc != SHIFTND_OK) return rc;
+    if (!x || !xs || !gw) return SHIFTND_ERR_INVALID_ARGUMENT;   // (the x == NULL form does not exist under the flag)
+    Geometry g;
+    rc = build_geometry(&q, xs, gos, gxs, g);
+    if (rc != SHIFTND_OK) return rc;
+    if (!frames_learn_geometry_ok(g, q.dtype)) return SHIFTND_ERR_INVALID_ARGUMENT;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (empty_geometry(g)) {
+        g_last_path = SHIFTND_PATH_EMPTY;
+        if (g.C > 0 && hipMemsetAsync(gw, 0, static_cast<size_t>(g.C) * dtype_size(wkind), st) != hipSuccess) return SHIFTND_ERR_LAUNCH_FAILED;
+        return SHIFTND_OK;
+    }
+    if (!go || !w || !gx || !workspace) return SHIFTND_ERR_INVALID_ARGUMENT;
+    if (!frames_tensor_ok(g, q.dtype, go, g.os) || !frames_tensor_ok(g, q.dtype, x, g.xs) || !frames_tensor_ok(g, q.dtype, gx, g.gs))
+        return SHIFTND_ERR_INVALID_ARGUMENT;
+    if (frames_backward_workspace(g, q.dtype) > workspace_bytes) return SHIFTND_ERR_WORKSPACE_TOO_SMALL;
+    g_last_path = SHIFTND_PATH_CL;
+    return finish(frames_backward(g, q.dtype, go, x, w, wkind, gx, gw, workspace, st));
+}
+
 int tshift_forward_call(const shiftnd_problem *p, const void *x, const int64_t *xs, const void *w, void *out, const int64_t *os,
                         void *stream) {
+    if (p->dtype & SHIFTND_FRAMES) return frames_learn_forward_call(p, x, xs, w, out, os, stream);
     shiftnd_problem q;
     int wkind;
     int rc = tshift_problem(p, q, wkind);
@@ -330,6 +391,7 @@ int frames_quantized_call(const shiftnd_problem *p, const void *x, const int64_t
 
 int tshift_backward_call(const shiftnd_problem *p, const void *go, const int64_t *gos, const void *x, const int64_t *xs, const void *w,
                          void *gx, const int64_t *gxs, void *gw, void *workspace, size_t workspace_bytes, void *stream) {
+    if (p->dtype & SHIFTND_FRAMES) return frames_learn_backward_call(p, go, gos, x, xs, w, gx, gxs, gw, workspace, workspace_bytes, stream);
     shiftnd_problem q;
     int wkind;
     int rc = tshift_problem(p, q, wkind);
@@ -519,6 +581,12 @@ size_t shiftnd_backward_workspace_bytes(const shiftnd_problem *p) {
     if (p->dtype & SHIFTND_SHIFT_DIM0) {   // the walk's plan alone: no other family runs under the flag, no knob shapes it
         const int64_t unit[5] = {0, 0, 0, 0, 0};
         Geometry g;
+        if (p->dtype & SHIFTND_FRAMES) {   // ... or, with SHIFTND_FRAMES, the channels-last walk's
+            if (frames_learn_problem(p, q, wkind) != SHIFTND_OK || build_geometry(&q, unit, unit, unit, g) != SHIFTND_OK) return 0;
+            if (!frames_learn_geometry_ok(g, q.dtype)) return 0;
+            if (g.N == 0 || g.C == 0 || g.S[0] * g.S[1] * g.S[2] == 0) return sizeof(double);
+            return frames_backward_workspace(g, q.dtype);
+        }
         if (tshift_problem(p, q, wkind) != SHIFTND_OK || build_geometry(&q, unit, unit, unit, g) != SHIFTND_OK) return 0;
         if (!tshift_geometry_ok(g, q.dtype)) return 0;
         if (g.N == 0 || g.C == 0 || g.S[0] * g.S[1] * g.S[2] == 0) return sizeof(double);

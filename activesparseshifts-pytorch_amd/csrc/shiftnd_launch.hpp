@@ -239,6 +239,16 @@ bool frames_tensor_ok(const Geometry &g, int dtype, const void *p, const int64_t
 int frames_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, int64_t wzp, uint64_t fill_bits, void *out,
                    hipStream_t st);
 
+// ---- the LEARNABLE temporal shift of channels-last tensors (shiftnd_frames_learn.hip; SHIFTND_SHIFT_DIM0 | SHIFTND_FRAMES): the
+// interpolating forward and the backward (sparse and interpolating) of float tensors in memory order N, S0, S1, S2, C, `w` and `gw`
+// [C] arrays, whole window; every tensor passes frames_tensor_ok.  frames_learn_geometry_ok: the sizes (frames_geometry_ok's and the
+// backward's groups).  The workspace plan depends on the geometry alone.  No fallback: every such call is served.
+bool frames_learn_geometry_ok(const Geometry &g, int dtype);
+int frames_active_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, void *out, hipStream_t st);
+size_t frames_backward_workspace(const Geometry &g, int dtype);
+int frames_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw,
+                    void *workspace, hipStream_t st);
+
 // ---- layout change (shiftnd_transpose.hip): dst[n][c][r] = src[n][r][c], dense tensors ---------------------------
 int transpose_planes(const void *src, void *dst, int64_t N, int64_t rows, int64_t cols, int esize, hipStream_t st);
 

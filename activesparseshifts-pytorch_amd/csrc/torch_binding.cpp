@@ -1365,6 +1365,128 @@ std::tuple<Tensor, Tensor> tsl_backward_hip(const Tensor &grad_, const Tensor &w
     return std::make_tuple(grad_input, grad_weights);
 }
 
+// ---- channels-last learnable temporal shift: temporal_shift_learnable_cl / _temporal_shift_learnable_cl_forward / _backward ---------
+// The values and gradients of temporal_shift_learnable with the layout of the argument kept (memory_format=torch.preserve_format in
+// the Python wrappers).  On HIP tensors a dense channels-last input is ONE flagged C-ABI call per pass on the tensors as they lie
+// (SHIFTND_SHIFT_DIM0 | SHIFTND_FRAMES on the strides {T*M*C, 1, M*C, C}: shiftnd_frames_learn.hip), no layout change in either
+// direction; the backward takes that route when the saved input and the gradient are both dense channels-last and grad_x then has
+// the gradient's strides.  Every other tensor goes the plain op's way.  The frame kernels stage nothing, and the sizes they take
+// include every size the segment-major kernels take (those stop at 2^31 two-byte units a tensor), so the option never refuses a
+// call that the plain op serves.  The autograd node keeps the input as it lies and the weights.
+Tensor call_tsl_cl_forward(const Tensor &input, const Tensor &weights, int64_t n_segment, int64_t padding_mode, bool active_flag) {
+    static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("torchshifts::_temporal_shift_learnable_cl_forward", "").typed<tsl_forward_sig>();
+    return op.call(input, weights, n_segment, padding_mode, active_flag);
+}
+std::tuple<Tensor, Tensor> call_tsl_cl_backward(const Tensor &grad, const Tensor &weights, const Tensor &input, int64_t n_segment,
+                                                int64_t padding_mode, bool active_flag) {
+    static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("torchshifts::_temporal_shift_learnable_cl_backward", "").typed<tsl_backward_sig>();
+    return op.call(grad, weights, input, n_segment, padding_mode, active_flag);
+}
+
+Tensor tsl_cl_public(const Tensor &input, const Tensor &weights, int64_t n_segment, int64_t padding_mode, bool active_flag) {
+    tsl_check(input, weights, n_segment, padding_mode);
+    return call_tsl_cl_forward(input, weights, n_segment, padding_mode, active_flag);
+}
+
+struct LearnableTemporalShiftClFunction : public torch::autograd::Function<LearnableTemporalShiftClFunction> {
+    static variable_list forward(AutogradContext *ctx, const Tensor &input, const Tensor &weights, int64_t n_segment,
+                                 int64_t padding_mode, bool active_flag) {
+        at::AutoDispatchBelowADInplaceOrView guard;
+        auto output = call_tsl_cl_forward(input, weights, n_segment, padding_mode, active_flag);
+        ctx->saved_data["n_segment"] = n_segment;
+        ctx->saved_data["padding_mode"] = padding_mode;
+        ctx->saved_data["active_flag"] = active_flag;
+        ctx->save_for_backward({input, weights});   // (the input as it lies: no copy)
+        return {output};
+    }
+    static variable_list backward(AutogradContext *ctx, const variable_list &grad_output) {
+        auto saved = ctx->get_saved_variables();
+        auto result = call_tsl_cl_backward(grad_output[0], saved[1], saved[0], ctx->saved_data["n_segment"].toInt(),
+                                           ctx->saved_data["padding_mode"].toInt(), ctx->saved_data["active_flag"].toBool());
+        return {std::get<0>(result), std::get<1>(result), Tensor(), Tensor(), Tensor()};
+    }
+};
+
+struct LearnableTemporalShiftClBackwardFunction : public torch::autograd::Function<LearnableTemporalShiftClBackwardFunction> {
+    static variable_list forward(AutogradContext *ctx, const Tensor &grad, const Tensor &weights, const Tensor &input,
+                                 int64_t n_segment, int64_t padding_mode, bool active_flag) {
+        at::AutoDispatchBelowADInplaceOrView guard;
+        auto result = call_tsl_cl_backward(grad, weights, input, n_segment, padding_mode, active_flag);
+        return {std::get<0>(result), std::get<1>(result)};
+    }
+    static variable_list backward(AutogradContext *, const variable_list &) {
+        TORCH_CHECK(0, "double backwards on temporal_shift_learnable_cl not supported");
+    }
+};
+
+Tensor tsl_cl_autograd(const Tensor &input, const Tensor &weights, int64_t n_segment, int64_t padding_mode, bool active_flag) {
+    tsl_check(input, weights, n_segment, padding_mode);
+    return LearnableTemporalShiftClFunction::apply(input, weights, n_segment, padding_mode, active_flag)[0];
+}
+std::tuple<Tensor, Tensor> tsl_cl_autograd_backward(const Tensor &grad, const Tensor &weights, const Tensor &input, int64_t n_segment,
+                                                    int64_t padding_mode, bool active_flag) {
+    tsl_check(input, weights, n_segment, padding_mode);
+    auto result = LearnableTemporalShiftClBackwardFunction::apply(grad, weights, input, n_segment, padding_mode, active_flag);
+    return std::make_tuple(result[0], result[1]);
+}
+
+// CPU tensors: the plain op's routine computes, the results are laid into the arguments' strides (grad_x: the gradient's)
+Tensor tsl_cl_forward_cpu(const Tensor &input, const Tensor &weights, int64_t n_segment, int64_t padding_mode, bool active_flag) {
+    return in_layout_of(tsl_forward_cpu(input, weights, n_segment, padding_mode, active_flag), input);
+}
+std::tuple<Tensor, Tensor> tsl_cl_backward_cpu(const Tensor &grad, const Tensor &weights, const Tensor &input, int64_t n_segment,
+                                               int64_t padding_mode, bool active_flag) {
+    auto result = tsl_backward_cpu(grad, weights, input, n_segment, padding_mode, active_flag);
+    return std::make_tuple(in_layout_of(std::get<0>(result), grad), std::get<1>(result));
+}
+
+// HIP tensors: the problem [N, C, T, M] on the strides {T*M*C, 1, M*C, C} under both flags
+void tsl_cl_problem(shiftnd_problem &p, int64_t st[5], const Tensor &t, int64_t T, int64_t padding_mode, bool active_flag, int dtype) {
+    temporal_cl_problem(t, T, padding_mode, dtype | SHIFTND_FRAMES, p, st);
+    p.active = active_flag ? 1 : 0;
+}
+
+Tensor tsl_cl_forward_hip(const Tensor &input, const Tensor &weights, int64_t n_segment, int64_t padding_mode, bool active_flag) {
+    if (!is_channels_last_dense(input)) return tsl_forward_hip(input, weights, n_segment, padding_mode, active_flag);
+    TORCH_CHECK(input.is_cuda(), "temporal_shift_learnable_cl: expected a CUDA tensor");
+    tsl_check(input, weights, n_segment, padding_mode);
+    const int mixed = weights_flag("temporal_shift_learnable_cl_cuda", input, "input", weights);
+    c10::DeviceGuard device_guard(input.device());
+    const int dtype = to_shiftnd_dtype(input.scalar_type(), "temporal_shift_learnable_cl_cuda") | mixed;
+    Tensor output = at::empty_strided(input.sizes(), input.strides(), input.options());
+    const Tensor w = weights.contiguous();
+    shiftnd_problem p;
+    int64_t st[5];
+    tsl_cl_problem(p, st, input, n_segment, padding_mode, active_flag, dtype);
+    const int rc = shiftnd_forward(&p, input.data_ptr(), st, w.data_ptr(), output.data_ptr(), st, current_stream(input));
+    TORCH_CHECK(rc == SHIFTND_OK, "temporal_shift_learnable_cl (HIP): ", shiftnd_status_string(rc));
+    return output;
+}
+
+std::tuple<Tensor, Tensor> tsl_cl_backward_hip(const Tensor &grad, const Tensor &weights, const Tensor &input, int64_t n_segment,
+                                               int64_t padding_mode, bool active_flag) {
+    if (!is_channels_last_dense(input) || !is_channels_last_dense(grad) || grad.sizes() != input.sizes())
+        return tsl_backward_hip(grad, weights, input, n_segment, padding_mode, active_flag);   // (contiguous grad_x)
+    TORCH_CHECK(grad.is_cuda() && input.is_cuda(), "temporal_shift_learnable_cl: expected CUDA tensors");
+    tsl_check(input, weights, n_segment, padding_mode);
+    check_same("temporal_shift_learnable_cl_backward_cuda", grad, "grad", input, "input");
+    const int mixed = weights_flag("temporal_shift_learnable_cl_backward_cuda", grad, "grad", weights);
+    c10::DeviceGuard device_guard(grad.device());
+    const int dtype = to_shiftnd_dtype(grad.scalar_type(), "temporal_shift_learnable_cl_backward_cuda") | mixed;
+    const Tensor w = weights.contiguous();
+    Tensor grad_input = at::empty_strided(grad.sizes(), grad.strides(), grad.options());
+    Tensor grad_weights = at::empty_like(w, at::MemoryFormat::Contiguous);   // (the weights' dtype: fp32 for a mixed call)
+    shiftnd_problem p;
+    int64_t st[5];
+    tsl_cl_problem(p, st, input, n_segment, padding_mode, active_flag, dtype);
+    const size_t ws_bytes = shiftnd_backward_workspace_bytes(&p);
+    Tensor workspace = at::empty({static_cast<int64_t>(ws_bytes)}, input.options().dtype(at::kByte));
+    const int rc = shiftnd_backward(&p, grad.data_ptr(), st, input.data_ptr(), st, w.data_ptr(), grad_input.data_ptr(), st,
+                                    grad_weights.data_ptr(), workspace.data_ptr(), ws_bytes, current_stream(grad));
+    TORCH_CHECK(rc == SHIFTND_OK, "temporal_shift_learnable_cl backward (HIP): ", shiftnd_status_string(rc));
+    return std::make_tuple(grad_input, grad_weights);
+}
+
 int64_t cuda_version() { return -1; }  // no CUDA toolkit: extension.py only compares when torch.version.cuda is set
 int64_t hip_version() { return HIP_VERSION; }
 
@@ -1422,11 +1544,17 @@ TORCH_LIBRARY(torchshifts, m) {
     m.def("torchshifts::temporal_shift_learnable(Tensor input, Tensor weights, int n_segment, int padding_mode, bool active_flag) -> Tensor", &tsl_public);
     m.def("torchshifts::_temporal_shift_learnable_forward(Tensor input, Tensor weights, int n_segment, int padding_mode, bool active_flag) -> Tensor");
     m.def("torchshifts::_temporal_shift_learnable_backward(Tensor grad, Tensor weights, Tensor input, int n_segment, int padding_mode, bool active_flag) -> (Tensor, Tensor)");
+    // ... with the argument's layout kept: a dense channels-last tensor is served as it lies, forward and backward
+    m.def("torchshifts::temporal_shift_learnable_cl(Tensor input, Tensor weights, int n_segment, int padding_mode, bool active_flag) -> Tensor", &tsl_cl_public);
+    m.def("torchshifts::_temporal_shift_learnable_cl_forward(Tensor input, Tensor weights, int n_segment, int padding_mode, bool active_flag) -> Tensor");
+    m.def("torchshifts::_temporal_shift_learnable_cl_backward(Tensor grad, Tensor weights, Tensor input, int n_segment, int padding_mode, bool active_flag) -> (Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(torchshifts, Autograd, m) {
     m.impl("_temporal_shift_learnable_forward", TORCH_FN(tsl_autograd));
     m.impl("_temporal_shift_learnable_backward", TORCH_FN(tsl_autograd_backward));
+    m.impl("_temporal_shift_learnable_cl_forward", TORCH_FN(tsl_cl_autograd));
+    m.impl("_temporal_shift_learnable_cl_backward", TORCH_FN(tsl_cl_autograd_backward));
     m.impl("temporal_shift", TORCH_FN(temporal_autograd));
     m.impl("_temporal_shift_backward", TORCH_FN(temporal_autograd_backward));
     m.impl("temporal_shift_cl", TORCH_FN(temporal_cl_autograd));
@@ -1457,6 +1585,8 @@ TORCH_LIBRARY_IMPL(torchshifts, CPU, m) {
     m.impl("_temporal_shift_cl_backward", TORCH_FN(temporal_cl_backward_cpu));
     m.impl("_temporal_shift_learnable_forward", TORCH_FN(tsl_forward_cpu));
     m.impl("_temporal_shift_learnable_backward", TORCH_FN(tsl_backward_cpu));
+    m.impl("_temporal_shift_learnable_cl_forward", TORCH_FN(tsl_cl_forward_cpu));
+    m.impl("_temporal_shift_learnable_cl_backward", TORCH_FN(tsl_cl_backward_cpu));
     m.impl("_shift1d_pool_forward", TORCH_FN(pool_forward_composed<1>));
     m.impl("_shift1d_pool_backward", TORCH_FN(pool_backward_composed<1>));
     m.impl("_shift2d_pool_forward", TORCH_FN(pool_forward_composed<2>));
@@ -1468,6 +1598,8 @@ TORCH_LIBRARY_IMPL(torchshifts, CPU, m) {
 TORCH_LIBRARY_IMPL(torchshifts, CUDA, m) {
     m.impl("_temporal_shift_learnable_forward", TORCH_FN(tsl_forward_hip));
     m.impl("_temporal_shift_learnable_backward", TORCH_FN(tsl_backward_hip));
+    m.impl("_temporal_shift_learnable_cl_forward", TORCH_FN(tsl_cl_forward_hip));
+    m.impl("_temporal_shift_learnable_cl_backward", TORCH_FN(tsl_cl_backward_hip));
     m.impl("temporal_shift", TORCH_FN(temporal_forward_hip));
     m.impl("_temporal_shift_backward", TORCH_FN(temporal_backward_hip));
     m.impl("temporal_shift_cl", TORCH_FN(temporal_cl_forward_hip));

@@ -202,11 +202,20 @@ def temporal_shift_func(input: Tensor, shifts: Tensor, n_segment: int, padding_m
 # (The [N, C, T, M] view through shift2d_func with weights (w, 0) is NOT the same thing: the 2-D rule wires a difference along the
 # second dim into the first dim's weight gradient.)  `weights`: [n_channels] or [n_channels, 1] floats of the input's dtype, or
 # float32 with a float16 / bfloat16 input (torch.autocast); weights.grad has the weights' dtype.
+#
+# memory_format: torch.contiguous_format (the default) is the call above, a contiguous result whatever the input's layout.  With
+# torch.preserve_format a dense channels-last input (as for temporal_shift_func) comes back in its own strides with the same
+# values, and x.grad takes the layout of the incoming gradient when that is dense channels-last too; every other input gives what
+# the default gives.  On HIP tensors the channels-last tensors are served as they lie, one kernel per pass, no layout change in
+# either direction, and the autograd node keeps the input without a copy.
 def temporal_shift_learnable_func(input: Tensor, weights: Tensor, n_segment: int, padding_mode: int = 0,
-                                  active_flag: bool = False) -> Tensor:
+                                  active_flag: bool = False,
+                                  memory_format: torch.memory_format = torch.contiguous_format) -> Tensor:
     """Shift the channels of a [N * n_segment, C, ...] tensor (2 to 5 dims) across the n_segment frames of each clip by weights[c]."""
     name = "temporal_shift_learnable_func()"
     _assert_has_ops()
+    assert memory_format in (torch.contiguous_format, torch.preserve_format), \
+        f"{name} expected memory_format to be torch.contiguous_format or torch.preserve_format, but it is {memory_format}"
     assert padding_mode in [0, 1, 2, 3, 4], f"{name} expected padding_mode can be {_PADDING_DOC}"
     assert 2 <= len(input.shape) <= 5, f"{name}: expected a 2D to 5D tensor as input, but it is shape is {input.shape}"
     assert isinstance(n_segment, int) and n_segment >= 1 and input.shape[0] % n_segment == 0, \
@@ -220,4 +229,6 @@ def temporal_shift_learnable_func(input: Tensor, weights: Tensor, n_segment: int
     assert input.device == weights.device, \
         (f"{name}: expected input and weights to be on same device, but input is  on {input.device} "
          f"and weights is on {weights.device}")
+    if memory_format == torch.preserve_format:
+        return torch.ops.torchshifts.temporal_shift_learnable_cl(input, weights, n_segment, padding_mode, bool(active_flag))
     return torch.ops.torchshifts.temporal_shift_learnable(input, weights, n_segment, padding_mode, bool(active_flag))

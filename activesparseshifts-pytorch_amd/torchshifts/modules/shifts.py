@@ -367,14 +367,20 @@ class LearnableTemporalShift(nn.Module):
         sparsity_term (float): strength of the L1 sparsity loss returned by forward. Default 5e-4.
         active_flag (bool): interpolate on the forward pass (active shift). Default False.
         init_thumb_rule (int): as Shift1d's (both values initialise with uniform(-init_shift, init_shift)).
+        memory_format: torch.contiguous_format (default: a contiguous output) or torch.preserve_format (a dense channels-last
+            input comes back channels-last, served as it lies on HIP tensors, forward and backward).  A plain attribute, not
+            part of the state_dict.
     forward(x) -> (output, loss): the pair convention of Shift{N}d; loss is None when sparsity_term == 0.
     """
 
     def __init__(self, n_segment, in_channels, padding='zeros', init_shift=1, sparsity_term=5e-4, active_flag=False,
-                 init_thumb_rule=1):
+                 init_thumb_rule=1, memory_format=torch.contiguous_format):
         super().__init__()
         assert padding.lower() in paddings_dict.keys(), f'incorrect padding option: {padding}'
         assert int(n_segment) >= 1, 'n_segment must be >= 1'
+        assert memory_format in (torch.contiguous_format, torch.preserve_format), \
+            f'memory_format must be torch.contiguous_format or torch.preserve_format, not {memory_format}'
+        self.memory_format = memory_format
         self.padding = paddings_dict[padding.lower()]
         self.n_segment = int(n_segment)
         self.in_channels = in_channels
@@ -393,11 +399,13 @@ class LearnableTemporalShift(nn.Module):
     def forward(self, input):
         """Returns (output, loss); loss is None when sparsity_term == 0."""
         loss = self._compute_weight_loss() if bool(self.sparsity_term) else None
-        return temporal_shift_learnable_func(input, self.weight, self.n_segment, self.padding, self._active_flag), loss
+        return temporal_shift_learnable_func(input, self.weight, self.n_segment, self.padding, self._active_flag,
+                                             self.memory_format), loss
 
     def extra_repr(self):
         pad = {v: k for k, v in paddings_dict.items()}[self.padding]
         active = f'Active shift on forward pass: {"Yes" if self._active_flag else "No"}'
         sparse = ('Sparse shift: Yes - sparsity strength: {}'.format(self.sparsity_term)
                   if bool(self.sparsity_term) else 'Sparse shift: No')
-        return f'n_segment={self.n_segment}, in_channels={self.in_channels}, padding_method={pad}, {active}, {sparse}'
+        return (f'n_segment={self.n_segment}, in_channels={self.in_channels}, padding_method={pad}, {active}, {sparse}, '
+                f'memory_format={self.memory_format}')

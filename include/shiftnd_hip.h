@@ -128,6 +128,32 @@ typedef enum shiftnd_dtype {
  */
 #define SHIFTND_SHIFT_DIM0 0x200
 
+/*
+ * The learnable temporal shift on channels-last tensors.  OR-ed onto a float dtype TOGETHER WITH SHIFTND_SHIFT_DIM0 (and, for F16 /
+ * BF16, optionally SHIFTND_WEIGHTS_F32): "the tensors are dense in memory order N, S0, S1, S2, C; serve the call with the
+ * channels-last frame kernels or refuse it".  The problem, `weights` and `grad_w` are those of SHIFTND_SHIFT_DIM0; only the layout
+ * differs: the video tensor [N*T, C, H, W] in channels-last memory, seen as {ndim 2, sizes N, C, T, M = H*W} with strides
+ * {T*M*C, 1, M*C, C}.  The flag is explicit, so a tensor that both layouts describe (S1 * S2 == 1 or C == 1) goes to the frame
+ * kernels under it.
+ *   shiftnd_forward, p->active == 0: frames_forward, the kernel and the bits of the call without this flag.
+ *   shiftnd_forward, p->active == 1: the interpolating forward (shiftnd_last_kernel(): frames_active_forward, *_ragged for pixel rows
+ *   -- C elements -- that are not whole 16-byte pieces or bases off the 16-byte grid).
+ *   shiftnd_backward: grad_out, x and grad_x all dense channels-last, grad_w [C] in the weights' type, deterministic
+ *   (frames_backward / frames_backward_ragged).  The x == NULL form is refused.
+ *   shiftnd_backward_workspace_bytes: that kernel's plan, a function of the geometry alone; sizeof(double) for an empty problem.
+ *   Served calls report SHIFTND_PATH_CL; an empty problem SHIFTND_PATH_EMPTY with grad_w zeroed.
+ *   Accepted: ndim 2 or 3; F32, F64, F16, BF16; every padding mode; the whole window; element-aligned bases.  Bounds: those of the
+ *   channels-last layout above (N, C and S1 * S2 below 2^31, S0 below 2^30, N * S0 below 2^31, N * S0 * ceil(S1 * S2 / 8) below
+ *   2^31, the tensor below 2^46 bytes) and, for the backward's partial records, N * ceil(S1 * S2 / rows) below 2^31 and those
+ *   records (24 bytes per group and channel) below 2^46 bytes, where rows >= 1 is the rows of a workgroup (at most 8 steps of
+ *   max(1, 256 / ceil(C * elsize / 16)) rows).  The kernels stage nothing, so S0 has no further limit.
+ *   Errors, before anything is launched: a quantized dtype SHIFTND_ERR_UNSUPPORTED_DTYPE (the workspace query answers 0); ndim 1,
+ *   a cut window, any tensor that is not dense channels-last (segment-major and NCHW-dense included), a size beyond the bounds,
+ *   the x == NULL form: SHIFTND_ERR_INVALID_ARGUMENT; a workspace below the plan: SHIFTND_ERR_WORKSPACE_TOO_SMALL.
+ * Without SHIFTND_SHIFT_DIM0 the bit is an unknown dtype bit: SHIFTND_ERR_UNSUPPORTED_DTYPE.  Without the bit nothing changes.
+ */
+#define SHIFTND_FRAMES 0x400
+
 typedef enum shiftnd_status {
     SHIFTND_OK = 0,
     SHIFTND_ERR_INVALID_ARGUMENT = -1,
@@ -151,7 +177,7 @@ typedef enum shiftnd_path {
 /* Problem geometry shared by the entry points. */
 typedef struct shiftnd_problem {
     int32_t ndim;          /* spatial dims: 1, 2 or 3 */
-    int32_t dtype;         /* shiftnd_dtype of input/output (and of float weights), optionally | SHIFTND_WEIGHTS_F32 | SHIFTND_SHIFT_DIM0 */
+    int32_t dtype;         /* shiftnd_dtype of input/output (and of float weights), optionally | SHIFTND_WEIGHTS_F32 | SHIFTND_SHIFT_DIM0 | SHIFTND_FRAMES */
     int32_t padding_mode;  /* 0..4 */
     int32_t active;        /* 0: sparse shift (rounded integer shift); 1: active (interpolated) */
     int64_t sizes[5];      /* input N, C, H, W, D */
