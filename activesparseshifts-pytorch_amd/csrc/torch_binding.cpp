@@ -1203,6 +1203,15 @@ std::tuple<Tensor, Tensor> tsl_backward_cpu(const Tensor &grad, const Tensor &we
     return std::make_tuple(tsl_frames(std::get<0>(result), input.sizes(), n_segment), std::get<1>(result).reshape(weights.sizes()));
 }
 
+// The segment-major kernels count the tensor in 32-bit two-byte units (tshift_geometry_ok, csrc/shiftnd_tshift.hip: planes * units
+// per plane + 16 < 2^31) and SHIFTND_SHIFT_DIM0 has no fallback: refuse a larger tensor here, before anything is allocated
+void tsl_check_size(const Tensor &input, const char *who) {
+    const int64_t units = input.numel() * static_cast<int64_t>(input.element_size()) / 2;
+    TORCH_CHECK(units + 16 < (1LL << 31), who, ": a contiguous tensor of ", units, " two-byte units is beyond the segment-major kernels' ",
+                "limit of 2^31 - 16 two-byte units (4 GiB); pass a channels-last tensor with memory_format=torch.preserve_format, ",
+                "or split the batch");
+}
+
 // HIP tensors: one flagged C-ABI call on the segment-major strides
 Tensor tsl_forward_hip(const Tensor &input_, const Tensor &weights, int64_t n_segment, int64_t padding_mode, bool active_flag) {
     TORCH_CHECK(input_.is_cuda(), "temporal_shift_learnable: expected a CUDA tensor");
@@ -1210,6 +1219,7 @@ Tensor tsl_forward_hip(const Tensor &input_, const Tensor &weights, int64_t n_se
     const int mixed = weights_flag("temporal_shift_learnable_cuda", input_, "input", weights);
     c10::DeviceGuard device_guard(input_.device());
     const int dtype = to_shiftnd_dtype(input_.scalar_type(), "temporal_shift_learnable_cuda") | mixed;
+    tsl_check_size(input_, "temporal_shift_learnable");
     const Tensor input = input_.contiguous();
     Tensor output = at::empty(input.sizes(), input.options(), at::MemoryFormat::Contiguous);
     if (input.numel() == 0) return output;
@@ -1231,6 +1241,7 @@ std::tuple<Tensor, Tensor> tsl_backward_hip(const Tensor &grad_, const Tensor &w
     TORCH_CHECK(grad_.sizes() == input_.sizes(), "temporal_shift_learnable backward: grad does not match the input");
     c10::DeviceGuard device_guard(grad_.device());
     const int dtype = to_shiftnd_dtype(grad_.scalar_type(), "temporal_shift_learnable_backward_cuda") | mixed;
+    tsl_check_size(input_, "temporal_shift_learnable backward");
     const Tensor input = input_.contiguous(), grad = grad_.contiguous();
     const Tensor w = weights.contiguous();
     Tensor grad_input = at::empty(input.sizes(), input.options(), at::MemoryFormat::Contiguous);
