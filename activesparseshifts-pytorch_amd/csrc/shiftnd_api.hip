@@ -339,8 +339,37 @@ int frames_learn_backward_call(const shiftnd_problem *p, const void *go, const i
     return finish(frames_backward(g, q.dtype, go, x, w, wkind, gx, gw, workspace, st));
 }
 
+// ---- SHIFTND_SHIFT_DIM0 with out == x: the fixed temporal shift IN PLACE (shiftnd_inplace.hip).  `q`: the problem with its plain
+// dtype, p->active as the caller gave it.  Served -- both dense layouts, at most 16 frames per clip, the sparse shift, the whole
+// window, x and out under the same strides -- or refused before anything is launched: the out-of-place kernels would race.
+int inplace_call(const shiftnd_problem &q, void *x, const int64_t *xs, const int64_t *os, const void *w, int wkind, int64_t wzp,
+                 uint64_t fill, void *stream) {
+    Geometry g;
+    const int rc = build_geometry(&q, xs, os, nullptr, g);
+    if (rc != SHIFTND_OK) return rc;
+    for (int i = 0; i < 5; ++i)
+        if (g.xs[i] != g.os[i]) return SHIFTND_ERR_INVALID_ARGUMENT;
+    if (!inplace_geometry_ok(g, q.dtype)) return SHIFTND_ERR_INVALID_ARGUMENT;   // (active, a cut window, S0 > 16, the sizes)
+    if (empty_problem(g)) {
+        g_last_path = SHIFTND_PATH_EMPTY;
+        return SHIFTND_OK;
+    }
+    if (!w) return SHIFTND_ERR_INVALID_ARGUMENT;
+    const int layout = inplace_layout(g, q.dtype, x, g.xs);
+    if (layout == 0) return SHIFTND_ERR_INVALID_ARGUMENT;
+    g_last_path = layout == 1 ? SHIFTND_PATH_PLANE : SHIFTND_PATH_CL;
+    return finish(inplace_forward(g, q.dtype, layout, x, w, wkind, wzp, fill, static_cast<hipStream_t>(stream)));
+}
+
 int tshift_forward_call(const shiftnd_problem *p, const void *x, const int64_t *xs, const void *w, void *out, const int64_t *os,
                         void *stream) {
+    if (out && out == x) {   // in place: its own kernel, or refused (SHIFTND_FRAMES asks for kernels that have no such form)
+        shiftnd_problem q;
+        int wkind;
+        if (p->dtype & SHIFTND_FRAMES) return SHIFTND_ERR_INVALID_ARGUMENT;
+        const int rc = tshift_problem(p, q, wkind);
+        return rc != SHIFTND_OK ? rc : inplace_call(q, out, xs, os, w, wkind, 0, 0ull, stream);
+    }
     if (p->dtype & SHIFTND_FRAMES) return frames_learn_forward_call(p, x, xs, w, out, os, stream);
     shiftnd_problem q;
     int wkind;
@@ -555,6 +584,11 @@ int shiftnd_forward_quantized(const shiftnd_problem *p, const void *x, const int
     if (dtype == SHIFTND_I8) fill = static_cast<uint8_t>(static_cast<int8_t>(x_zero_point));
     else if (dtype == SHIFTND_U8) fill = static_cast<uint8_t>(x_zero_point);
     else fill = static_cast<uint32_t>(static_cast<int32_t>(x_zero_point));
+    if ((p->dtype & SHIFTND_SHIFT_DIM0) && out && out == x) {   // in place: both dense layouts
+        q.dtype = dtype;
+        q.active = p->active;
+        return inplace_call(q, out, x_strides, out_strides, wq, wq_dtype, w_zero_point, fill, stream);
+    }
     if (p->dtype & SHIFTND_SHIFT_DIM0)
         return frames_quantized_call(p, x, x_strides, wq, wq_dtype, w_zero_point, fill, out, out_strides, stream);
     return forward_common(&q, x, x_strides, wq, wq_dtype, w_zero_point, fill, out, out_strides, stream);

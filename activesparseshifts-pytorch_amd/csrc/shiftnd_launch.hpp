@@ -249,6 +249,15 @@ size_t frames_backward_workspace(const Geometry &g, int dtype);
 int frames_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw,
                     void *workspace, hipStream_t st);
 
+// ---- the temporal shift IN PLACE (shiftnd_inplace.hip; SHIFTND_SHIFT_DIM0 with out == x): the sparse shift along S0 of float and
+// quantized (I8, U8, I32) tensors in either dense layout, `w` a [C] table, whole window, at most 16 frames per clip; only the bytes
+// of shifted channels are read or written.  inplace_geometry_ok: the sizes (frames_geometry_ok's, S0 <= 16, the grid);
+// inplace_layout: 1 for a dense segment-major tensor, 2 for a dense channels-last one, 0 for neither (normalised strides).
+bool inplace_geometry_ok(const Geometry &g, int dtype);
+int inplace_layout(const Geometry &g, int dtype, const void *p, const int64_t *strides);
+int inplace_forward(const Geometry &g, int dtype, int layout, void *x, const void *w, int wkind, int64_t wzp, uint64_t fill_bits,
+                    hipStream_t st);
+
 // ---- layout change (shiftnd_transpose.hip): dst[n][c][r] = src[n][r][c], dense tensors ---------------------------
 int transpose_planes(const void *src, void *dst, int64_t N, int64_t rows, int64_t cols, int esize, hipStream_t st);
 

@@ -14,6 +14,8 @@
 //   temporal cl   temporal_shift_cl / _temporal_shift_cl_backward / temporal_shift_quantized_cl: ... keeping a channels-last layout
 //   learnable     temporal_shift_learnable / _temporal_shift_learnable_forward / _backward: a trained shift across the frames
 //   learnable cl  temporal_shift_learnable_cl / _temporal_shift_learnable_cl_forward / _backward: ... keeping a channels-last layout
+// ... and, in a namespace of its own (torchshifts_inplace::, registered last), the one family that writes its argument:
+//   in place      temporal_shift_ / temporal_shift_quantized_: the temporal shift written into the input (composes on CPU tensors)
 //
 // Keys: the Autograd, CUDA and QuantizedCUDA kernels of every family are registered here.  The CPU / QuantizedCPU kernels that
 // compute (shift, fixed, fixed pool, temporal, temporal_shift_quantized) live in torch_cpu_backend.cpp; the ones that compose other
@@ -1319,6 +1321,144 @@ std::tuple<Tensor, Tensor> tsl_cl_backward_hip(const Tensor &grad, const Tensor 
     return std::make_tuple(grad_input, grad_weights);
 }
 
+// ---- in-place temporal shift: torchshifts_inplace::temporal_shift_ / temporal_shift_quantized_ -------------------------------------
+// The values of temporal_shift / temporal_shift_quantized written into the argument, which is returned.  A second library namespace,
+// because the op set of torchshifts:: is the reference's surface plus the families above and stays as it is.  On HIP tensors a dense
+// input (contiguous or channels-last, is_channels_last_dense) of at most kInplaceFrames frames per clip is ONE flagged C-ABI call
+// with out == x on the tensor as it lies (shiftnd_inplace.hip): only the shifted channels' bytes are read or written, nothing of the
+// input's size is allocated.  The [C] table is built like the channels-last routes': fp32 for 16-bit tensors (every shift exact),
+// the tensor's dtype for fp32 / fp64, int32 for quantized tensors.  Every other input -- not dense, a slice, more frames -- and every
+// CPU tensor is input.copy_(<the out-of-place op>(input)): the same values.  The autograd node marks the input dirty and keeps the
+// table, n_segment, the padding and whether the input was dense channels-last; its backward is OUT of place (a gradient buffer may
+// be shared with other consumers): _temporal_shift_cl_backward for a dense channels-last input, _temporal_shift_backward otherwise.
+constexpr int64_t kInplaceFrames = 16;   // (the frame slots of frames_inplace: include/shiftnd_hip.h)
+
+using temporal_inplace_sig = Tensor &(Tensor &, const Tensor &, int64_t, int64_t);
+
+struct InplaceOps {
+    static const char *name() { return "temporal_shift_"; }
+    static auto &forward() {
+        static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("torchshifts_inplace::temporal_shift_", "").typed<temporal_inplace_sig>();
+        return op;
+    }
+    static auto &backward() { return TemporalOps::backward(); }
+};
+struct InplaceClOps : InplaceOps {
+    static auto &backward() { return TemporalClOps::backward(); }
+};
+
+void temporal_inplace_check(const Tensor &input, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    TORCH_CHECK(!input.is_quantized(), "temporal_shift_: quantized inputs are not supported");
+    segment_check("temporal_shift_", input, shifts, n_segment, padding_mode, "shifts", is_integer_or_float(shifts), "integers or floats");
+}
+
+void temporal_quantized_inplace_check(const Tensor &input, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    TORCH_CHECK(input.is_quantized(), "temporal_shift_quantized_: expected a quantized input");
+    TORCH_CHECK(input.qscheme() == at::kPerTensorAffine, "temporal_shift_quantized_: expected a per-tensor quantized input");
+    segment_check("temporal_shift_quantized_", input, shifts, n_segment, padding_mode, "shifts",
+                  !shifts.is_quantized() && is_integer_or_float(shifts), "integers or floats");
+}
+
+struct TemporalShiftInplaceFunction : public torch::autograd::Function<TemporalShiftInplaceFunction> {
+    static variable_list forward(AutogradContext *ctx, const Tensor &input, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+        ctx->mark_dirty({input});
+        ctx->saved_data["n_segment"] = n_segment;
+        ctx->saved_data["padding_mode"] = padding_mode;
+        ctx->saved_data["channels_last"] = is_channels_last_dense(input);
+        ctx->save_for_backward({shifts.detach()});
+        at::AutoDispatchBelowADInplaceOrView guard;
+        InplaceOps::forward().call(const_cast<Tensor &>(input), shifts, n_segment, padding_mode);
+        return {input};
+    }
+    static variable_list backward(AutogradContext *ctx, const variable_list &grad_output) {
+        auto saved = ctx->get_saved_variables();
+        const int64_t n_segment = ctx->saved_data["n_segment"].toInt(), padding_mode = ctx->saved_data["padding_mode"].toInt();
+        Tensor grad = ctx->saved_data["channels_last"].toBool()
+                          ? GuardedBackward<InplaceClOps>::kernel(grad_output[0], saved[0], n_segment, padding_mode)
+                          : GuardedBackward<InplaceOps>::kernel(grad_output[0], saved[0], n_segment, padding_mode);
+        return {grad, Tensor(), Tensor(), Tensor()};
+    }
+};
+
+Tensor &temporal_inplace_autograd(Tensor &input, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    temporal_inplace_check(input, shifts, n_segment, padding_mode);
+    TemporalShiftInplaceFunction::apply(input, shifts, n_segment, padding_mode);
+    return input;
+}
+
+// the fallback of every backend: the out-of-place op of the input's layout, copied into the input
+Tensor &temporal_inplace_by_copy(Tensor &input, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    auto &op = is_channels_last_dense(input) ? TemporalClOps::forward() : TemporalOps::forward();
+    input.copy_(op.call(input, shifts, n_segment, padding_mode));
+    return input;
+}
+
+// a quantized tensor's storage as plain integers, the same sizes and strides (copy_ between them moves the int_repr and nothing else)
+Tensor int_repr_alias(const Tensor &t) {
+    const auto type = t.scalar_type() == at::kQUInt8 ? at::kByte : (t.scalar_type() == at::kQInt8 ? at::kChar : at::kInt);
+    return at::empty({0}, t.options().dtype(type)).set_(t.storage(), t.storage_offset(), t.sizes(), t.strides());
+}
+
+Tensor &temporal_quantized_inplace_by_copy(Tensor &input, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    static auto plain = typed_op<temporal_sig>("temporal_shift_quantized"), cl = typed_op<temporal_sig>("temporal_shift_quantized_cl");
+    const Tensor result = (is_channels_last_dense(input) ? cl : plain).call(input, shifts, n_segment, padding_mode);
+    int_repr_alias(input).copy_(int_repr_alias(result));   // (scale and zero point are the input's own: untouched)
+    return input;
+}
+
+Tensor &temporal_inplace_cpu(Tensor &input, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    temporal_inplace_check(input, shifts, n_segment, padding_mode);
+    return temporal_inplace_by_copy(input, shifts, n_segment, padding_mode);
+}
+
+// (no autograd node above the quantized op: the version counter is bumped here)
+Tensor &temporal_quantized_inplace_cpu(Tensor &input, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    temporal_quantized_inplace_check(input, shifts, n_segment, padding_mode);
+    at::AutoDispatchBelowADInplaceOrView guard;
+    input.unsafeGetTensorImpl()->bump_version();
+    return temporal_quantized_inplace_by_copy(input, shifts, n_segment, padding_mode);
+}
+
+// served as it lies: dense in one of the two layouts, few enough frames
+bool inplace_served(const Tensor &t, int64_t n_segment) {
+    return n_segment <= kInplaceFrames && t.numel() > 0 && (t.is_contiguous() || is_channels_last_dense(t));
+}
+
+Tensor &temporal_inplace_hip(Tensor &input, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    TORCH_CHECK(input.is_cuda(), "temporal_shift_: expected a CUDA tensor");
+    temporal_inplace_check(input, shifts, n_segment, padding_mode);
+    if (input.numel() == 0) return input;
+    if (!inplace_served(input, n_segment)) return temporal_inplace_by_copy(input, shifts, n_segment, padding_mode);
+    c10::DeviceGuard device_guard(input.device());
+    const bool half = input.scalar_type() == at::kHalf || input.scalar_type() == at::kBFloat16;
+    const int dtype = to_shiftnd_dtype(input.scalar_type(), "temporal_shift__cuda") | (half ? SHIFTND_WEIGHTS_F32 : 0);
+    const Tensor w = shifts.detach().reshape({input.size(1)}).to(half ? at::kFloat : input.scalar_type()).contiguous();
+    shiftnd_problem p;
+    int64_t st[5];
+    segment_problem(p, st, input, n_segment, padding_mode, false, dtype | SHIFTND_SHIFT_DIM0, !input.is_contiguous(), "temporal_shift_");
+    check_status(shiftnd_forward(&p, input.data_ptr(), st, w.data_ptr(), input.data_ptr(), st, current_stream(input)), "temporal_shift_ (HIP)");
+    return input;
+}
+
+Tensor &temporal_quantized_inplace_hip(Tensor &input, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    TORCH_CHECK(input.is_cuda(), "temporal_shift_quantized_: expected a CUDA tensor");
+    temporal_quantized_inplace_check(input, shifts, n_segment, padding_mode);
+    if (input.numel() == 0) return input;
+    at::AutoDispatchBelowADInplaceOrView guard;
+    input.unsafeGetTensorImpl()->bump_version();
+    if (!inplace_served(input, n_segment)) return temporal_quantized_inplace_by_copy(input, shifts, n_segment, padding_mode);
+    c10::DeviceGuard device_guard(input.device());
+    const int dtype = quant_dtype(input.scalar_type(), "temporal_shift_quantized__cuda");
+    const Tensor w = quantized_shift_table(shifts, input.size(1)).to(at::kInt).contiguous();
+    shiftnd_problem p;
+    int64_t st[5];
+    segment_problem(p, st, input, n_segment, padding_mode, false, dtype | SHIFTND_SHIFT_DIM0, !input.is_contiguous(), "temporal_shift_quantized_");
+    check_status(shiftnd_forward_quantized(&p, input.data_ptr(), st, w.data_ptr(), SHIFTND_I32, 0, input.q_zero_point(), input.data_ptr(), st,
+                                           current_stream(input)),
+                 "temporal_shift_quantized_ (HIP)");
+    return input;
+}
+
 int64_t cuda_version() { return -1; }  // no CUDA toolkit: extension.py only compares when torch.version.cuda is set
 int64_t hip_version() { return HIP_VERSION; }
 
@@ -1476,3 +1616,15 @@ TORCH_LIBRARY_IMPL(torchshifts, QuantizedCUDA, m) {
     m.impl("temporal_shift_quantized", TORCH_FN(temporal_quantized_hip));
     m.impl("temporal_shift_quantized_cl", TORCH_FN(temporal_quantized_cl_hip));
 }
+
+// the in-place temporal shift: its own namespace (the op set of torchshifts:: is pinned)
+TORCH_LIBRARY(torchshifts_inplace, m) {
+    m.def("torchshifts_inplace::temporal_shift_(Tensor(a!) input, Tensor shifts, int n_segment, int padding_mode) -> Tensor(a!)");
+    m.def("torchshifts_inplace::temporal_shift_quantized_(Tensor(a!) input, Tensor shifts, int n_segment, int padding_mode) -> Tensor(a!)");
+}
+
+TORCH_LIBRARY_IMPL(torchshifts_inplace, Autograd, m) { m.impl("temporal_shift_", TORCH_FN(temporal_inplace_autograd)); }
+TORCH_LIBRARY_IMPL(torchshifts_inplace, CPU, m) { m.impl("temporal_shift_", TORCH_FN(temporal_inplace_cpu)); }
+TORCH_LIBRARY_IMPL(torchshifts_inplace, CUDA, m) { m.impl("temporal_shift_", TORCH_FN(temporal_inplace_hip)); }
+TORCH_LIBRARY_IMPL(torchshifts_inplace, QuantizedCPU, m) { m.impl("temporal_shift_quantized_", TORCH_FN(temporal_quantized_inplace_cpu)); }
+TORCH_LIBRARY_IMPL(torchshifts_inplace, QuantizedCUDA, m) { m.impl("temporal_shift_quantized_", TORCH_FN(temporal_quantized_inplace_hip)); }

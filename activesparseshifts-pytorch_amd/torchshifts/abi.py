@@ -168,7 +168,7 @@ def forward(x, w, pad, active, borders=None, out=None, shift_dim0=False, frames=
     """x, w: device tensors (float dtypes; w of x's dtype, or fp32 with an fp16 / bf16 x).  Returns a new contiguous output (or
     fills `out`).  shift_dim0: the flagged call (w [C]; x and out segment-major views, or -- active False -- both dense
     channels-last views, memory order N, S0, S1, S2, C: pass `out`, a new output is contiguous).  frames: with shift_dim0, the
-    channels-last call in both modes (pass `out`)."""
+    channels-last call in both modes (pass `out`).  out=x with shift_dim0 (active False): the in-place call, either dense layout."""
     p = problem(x, pad, active, borders, w=w, shift_dim0=shift_dim0, frames=frames)
     if out is None:
         out = _new(out_shape(x, borders), x)
@@ -219,7 +219,8 @@ def backward_input(grad_out, w, input_shape, pad, borders=None, grad_x=None, wor
 
 def forward_quantized(xq, wq, w_zero_point, x_zero_point, pad, borders=None, out=None, shift_dim0=False):
     """xq: int8/uint8/int32 device tensor (int_repr); wq: int8/uint8/int32 device tensor [C, nd].  shift_dim0: the flagged call
-    (wq [C]; xq and `out` dense channels-last views, memory order N, S0, S1, S2, C)."""
+    (wq [C]; xq and `out` dense channels-last views, memory order N, S0, S1, S2, C; out=xq: the in-place call, which also takes
+    the segment-major layout)."""
     p = problem(xq, pad, False, borders, shift_dim0=shift_dim0)
     if out is None:
         out = _new(out_shape(xq, borders), xq)

@@ -193,6 +193,33 @@ def temporal_shift_func(input: Tensor, shifts: Tensor, n_segment: int, padding_m
     return torch.ops.torchshifts.temporal_shift(input, shifts, n_segment, padding_mode)
 
 
+# ---- in-place temporal shift ----------------------------------------------------------------------------------------------------
+# temporal_shift_func written into `input`, which is returned (the layout is the input's own, so there is no memory_format).  On
+# HIP tensors a dense input -- contiguous, or dense channels-last as above -- with n_segment <= 16 is one pass over the SHIFTED
+# channels alone: the kernel neither reads nor writes a channel whose shift is 0, and nothing of the input's size is allocated.  Its
+# table is float32 for 16-bit tensors (exact for every shift) and the input's dtype otherwise.  Every other input (a slice, a
+# non-dense view, more than 16 frames per clip) and every CPU tensor is input.copy_(temporal_shift_func(input, ...)).  Autograd: the
+# input is marked dirty (a leaf that requires grad raises PyTorch's own error), the node keeps the table alone, and the backward is
+# the out-of-place one of temporal_shift_func, in the layout of the input.
+def temporal_shift_func_(input: Tensor, shifts: Tensor, n_segment: int, padding_mode: int = 0) -> Tensor:
+    """Shift the channels of a [N * n_segment, C, ...] tensor (2 to 5 dims) across the n_segment frames of each clip, in place."""
+    name = "temporal_shift_func_()"
+    _assert_has_ops()
+    assert padding_mode in [0, 1, 2, 3, 4], f"{name} expected padding_mode can be {_PADDING_DOC}"
+    assert 2 <= len(input.shape) <= 5, f"{name}: expected a 2D to 5D tensor as input, but it is shape is {input.shape}"
+    assert isinstance(n_segment, int) and n_segment >= 1 and input.shape[0] % n_segment == 0, \
+        f"{name}: expected dim 0 of the input ({input.shape[0]}) to be a multiple of n_segment ({n_segment})"
+    assert len(shifts.shape) == 1 or (len(shifts.shape) == 2 and shifts.shape[1] == 1), \
+        f"{name}: expected [n_channels] tensor as shifts, but it is shape is {shifts.shape}"
+    assert input.shape[1] == shifts.shape[0], \
+        (f"{name}: expected that input and shifts have equal number of channels, but input have "
+         f"{input.shape[1]} and shifts have {shifts.shape[0]} channels.")
+    assert input.device == shifts.device, \
+        (f"{name}: expected input and shifts to be on same device, but input is  on {input.device} "
+         f"and shifts is on {shifts.device}")
+    return torch.ops.torchshifts_inplace.temporal_shift_(input, shifts, n_segment, padding_mode)
+
+
 # ---- learnable temporal shift: a TRAINED per-channel shift across the frames of a [N * n_segment, C, ...] tensor -----------------
 # The sparse (rounded) or active (interpolated) 1-D shift of shift1d_func, applied along the frames of each clip.  The result, and
 # the gradients of input and weights, equal those of

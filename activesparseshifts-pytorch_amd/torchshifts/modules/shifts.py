@@ -13,7 +13,7 @@ from torch import nn
 
 from torchshifts.functional import (shift1d_fixed_func, shift1d_fixed_pool_func, shift1d_func, shift1d_pool_func, shift2d_fixed_func,
                                     shift2d_fixed_pool_func, shift2d_func, shift2d_pool_func, shift3d_fixed_func,
-                                    shift3d_fixed_pool_func, shift3d_func, shift3d_pool_func, temporal_shift_func,
+                                    shift3d_fixed_pool_func, shift3d_func, shift3d_pool_func, temporal_shift_func, temporal_shift_func_,
                                     temporal_shift_learnable_func)
 
 paddings_dict = {'zeros': 0, 'border': 1, 'periodic': 2, 'reflect': 3, 'symmetric': 4}
@@ -301,16 +301,21 @@ class TemporalShift(nn.Module):
         memory_format: torch.contiguous_format (default: a contiguous output) or torch.preserve_format (a dense channels-last
             input comes back channels-last, shifted as it lies on HIP tensors: for channels-last models).  A plain attribute,
             not part of state_dict.
+        inplace (bool): shift the input itself and return it (the published InplaceShift): on HIP tensors a dense input of at
+            most 16 frames per clip is one pass over the shifted channels alone, without an output allocation.  memory_format is
+            then moot, the layout being the input's own.  A plain attribute, not part of state_dict. Default False.
     forward(x) -> output, the tensor alone: the module sits inside nn.Sequential in front of a convolution.
     """
 
-    def __init__(self, n_segment, in_channels, fold_div=8, shifts=None, padding='zeros', memory_format=torch.contiguous_format):
+    def __init__(self, n_segment, in_channels, fold_div=8, shifts=None, padding='zeros', memory_format=torch.contiguous_format,
+                 inplace=False):
         super().__init__()
         assert padding.lower() in paddings_dict.keys(), f'incorrect padding option: {padding}'
         assert int(n_segment) >= 1, 'n_segment must be >= 1'
         assert memory_format in (torch.contiguous_format, torch.preserve_format), \
             f'memory_format must be torch.contiguous_format or torch.preserve_format, not {memory_format}'
         self.memory_format = memory_format
+        self.inplace = bool(inplace)
         self.padding = paddings_dict[padding.lower()]
         self.n_segment = int(n_segment)
         self.in_channels = in_channels
@@ -345,12 +350,14 @@ class TemporalShift(nn.Module):
         return cls(module.n_segment, module.in_channels, shifts=table.cpu(), padding=pad).to(module.weight.device)
 
     def forward(self, input):
+        if self.inplace:
+            return temporal_shift_func_(input, self.shifts, self.n_segment, self.padding)
         return temporal_shift_func(input, self.shifts, self.n_segment, self.padding, self.memory_format)
 
     def extra_repr(self):
         pad = {v: k for k, v in paddings_dict.items()}[self.padding]
         return (f'n_segment={self.n_segment}, in_channels={self.in_channels}, fold_div={self.fold_div}, padding_method={pad}, '
-                f'memory_format={self.memory_format}, fixed integer shifts')
+                f'memory_format={self.memory_format}, fixed integer shifts' + (', inplace=True' if self.inplace else ''))
 
 
 class LearnableTemporalShift(nn.Module):

@@ -39,3 +39,14 @@ def temporal_shift_quantized(input, shifts, n_segment, padding_mode=0, memory_fo
     if memory_format == torch.preserve_format:
         return torch.ops.torchshifts.temporal_shift_quantized_cl(input, shifts, int(n_segment), int(padding_mode))
     return torch.ops.torchshifts.temporal_shift_quantized(input, shifts, int(n_segment), int(padding_mode))
+
+
+def temporal_shift_quantized_(input, shifts, n_segment, padding_mode=0):
+    """temporal_shift_quantized written into `input`, which is returned with its scale, zero point and layout (the in-place
+    torchshifts.functional.temporal_shift_func_ of a per-tensor quantized tensor).  On HIP tensors a dense input -- contiguous or
+    dense channels-last -- with n_segment <= 16 is one pass over the shifted channels alone, with an int32 table and nothing of
+    the input's size allocated; every other input, and every CPU tensor, is the out-of-place result copied into the input."""
+    if not input.is_quantized:
+        raise ValueError("Input to 'temporal_shift_quantized_' must be quantized!")
+    _assert_has_ops()
+    return torch.ops.torchshifts_inplace.temporal_shift_quantized_(input, shifts, int(n_segment), int(padding_mode))

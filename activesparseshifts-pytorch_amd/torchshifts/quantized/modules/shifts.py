@@ -20,7 +20,7 @@ import torch
 
 import torchshifts.modules.shifts as shifts
 from torchshifts.functional import shift1d_pool_func, shift2d_pool_func, shift3d_pool_func
-from torchshifts.quantized.functional import shift1d_quantized, shift2d_quantized, shift3d_quantized, temporal_shift_quantized
+from torchshifts.quantized.functional import shift1d_quantized, shift2d_quantized, shift3d_quantized, temporal_shift_quantized, temporal_shift_quantized_
 
 _POOL_FUNCS = {1: shift1d_pool_func, 2: shift2d_pool_func, 3: shift3d_pool_func}
 
@@ -152,10 +152,12 @@ class TemporalShift(shifts.TemporalShift):
     forward(x) -> output, the tensor alone.  from_float converts a TemporalShift, or a non-active LearnableTemporalShift
     (frozen through TemporalShift.from_shift: round(weight), half to even); an active one interpolates and raises ValueError.
     memory_format is the float module's option (torch.preserve_format: a channels-last input comes back channels-last);
-    from_float carries the float module's value over.
+    from_float carries the float module's value over, and that of `inplace` (the input itself is shifted and returned).
     """
 
     def forward(self, input):
+        if self.inplace:
+            return temporal_shift_quantized_(input, self.shifts, self.n_segment, self.padding)
         return temporal_shift_quantized(input, self.shifts, self.n_segment, self.padding, self.memory_format)
 
     def _get_name(self):
@@ -167,5 +169,5 @@ class TemporalShift(shifts.TemporalShift):
             mod = shifts.TemporalShift.from_shift(mod)
         assert isinstance(mod, shifts.TemporalShift), 'expected a TemporalShift or LearnableTemporalShift module'
         qshift = cls(mod.n_segment, mod.in_channels, fold_div=mod.fold_div, shifts=mod.shifts.detach().cpu(), padding=rp_dict[mod.padding],
-                     memory_format=mod.memory_format)
+                     memory_format=mod.memory_format, inplace=mod.inplace)
         return qshift.to(mod.shifts.device)

@@ -124,6 +124,26 @@ typedef enum shiftnd_dtype {
  *   tensors, a cut window, ndim 1, a size beyond the bounds: SHIFTND_ERR_INVALID_ARGUMENT.
  *   Errors, before anything is launched: p->active == 1 on the channels-last layout, x and out in different layouts (channels-last
  *   with segment-major or NCHW-dense), a size beyond the bounds: SHIFTND_ERR_INVALID_ARGUMENT.
+ *
+ * In place (the FIXED temporal shift written into its input): under the flag, out == x -- the same pointer, with identical strides --
+ * and p->active == 0 is a call of its own, served by csrc/shiftnd_inplace.hip.  A thread owns one naturally aligned power-of-two
+ * piece (at most 16 bytes: the widest that divides the plane's bytes, or the channel row's bytes, and the base) at the same offset in
+ * every frame of one clip, gathers the pieces of the frames whose content changes into registers and stores them; it reads and
+ * writes no byte outside its piece, so there is no hazard between threads, and a channel whose shift maps every frame to itself
+ * (shift 0, S0 == 1, a whole period) is neither read nor written.  No workspace.
+ *   shiftnd_forward: F32, F64, F16, BF16; `weights` a [C] array of the tensor dtype, or fp32 under SHIFTND_WEIGHTS_F32.
+ *   shiftnd_forward_quantized: I8, U8, I32; wq a [C] integer table of wq_dtype, zeros padding fills with x_zero_point.  For the
+ *   in-place form ALONE this entry point also takes the segment-major layout (with out != x it stays refused).
+ *   Accepted: both dense layouts -- segment-major (memory order N, S0, C, S1, S2) and channels-last (N, S0, S1, S2, C); a tensor both
+ *   describe (S1 * S2 == 1 or C == 1) is served as segment-major, with the same result -- ndim 2 or 3, the whole window, every padding
+ *   mode, element-aligned bases, S0 <= 16 (the kernel keeps a clip's frames in 16 register slots).  Bounds: those of the channels-last
+ *   layout above and N * ceil(C * S1 * S2 / 256) below 2^31 (the grid).  shiftnd_last_kernel(): frames_inplace for 16-byte pieces,
+ *   frames_inplace_ragged for narrower ones; shiftnd_last_path(): SHIFTND_PATH_PLANE for segment-major, SHIFTND_PATH_CL for
+ *   channels-last.
+ *   Errors, before anything is launched (the out-of-place kernels would race on such a call): S0 > 16, p->active == 1, a cut window,
+ *   SHIFTND_FRAMES, x and out strides that differ, a layout that is neither dense form, a size beyond the bounds:
+ *   SHIFTND_ERR_INVALID_ARGUMENT.
+ *   out == x WITHOUT the flag, and tensors that overlap in part, stay undefined: the kernels declare x and out __restrict__.
  * Without the flag nothing changes.
  */
 #define SHIFTND_SHIFT_DIM0 0x200
