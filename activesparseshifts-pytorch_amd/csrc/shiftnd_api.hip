@@ -271,13 +271,20 @@ int forward_common(const shiftnd_problem *p, const void *x, const int64_t *xs, c
 // on spatial dim 0 of dense segment-major tensors; the forward's sparse shift also takes dense channels-last tensors (the fixed
 // temporal shift of an NHWC tensor, shiftnd_frames.hip), and so does shiftnd_forward_quantized.  No routing and no fallback: the call
 // is served by the kernels of its layout or refused before anything is launched.
-// -> the problem without the flag bits in `q`, the weights' type in `wkind`
-int tshift_problem(const shiftnd_problem *p, shiftnd_problem &q, int &wkind) {
+// SHIFTND_PER_CLIP beside the flag: `weights` / `grad_w` are [N, C] arrays, one row per clip -- the tshift kernels on segment-major
+// tensors alone, out of place (tshift_forward_call / tshift_backward_call); every other form under the flag refuses the bit.
+// -> the problem without the flag bits in `q`, the weights' type in `wkind`, SHIFTND_PER_CLIP's presence in `per_clip`
+int tshift_problem(const shiftnd_problem *p, shiftnd_problem &q, int &wkind, bool &per_clip) {
     shiftnd_problem r = *p;
-    r.dtype = p->dtype & ~SHIFTND_SHIFT_DIM0;
+    r.dtype = p->dtype & ~(SHIFTND_SHIFT_DIM0 | SHIFTND_PER_CLIP);
+    per_clip = (p->dtype & SHIFTND_PER_CLIP) != 0;
     if (split_dtype(&r, q, wkind) != SHIFTND_OK || !is_float_dtype(q.dtype)) return SHIFTND_ERR_UNSUPPORTED_DTYPE;
     return SHIFTND_OK;
 }
+
+// the bound SHIFTND_PER_CLIP adds to tshift_geometry_ok's: the [N, C] table is indexed in 32 bits.  (Today N * S0 * C < 2^31 implies
+// it; it is stated on its own because the kernels' table index and the reduction's entry count rest on it.)
+bool per_clip_table_ok(const Geometry &g) { return g.N * g.C < (1LL << 31); }   // (both factors are below 2^31 here: no overflow)
 
 // ---- SHIFTND_SHIFT_DIM0 | SHIFTND_FRAMES: the same problem on dense channels-last tensors, all of them (shiftnd_frames_learn.hip; the
 // sparse forward is frames_forward).  The explicit bit takes every such call to the frame kernels -- also tensors that the
@@ -286,7 +293,10 @@ int tshift_problem(const shiftnd_problem *p, shiftnd_problem &q, int &wkind) {
 int frames_learn_problem(const shiftnd_problem *p, shiftnd_problem &q, int &wkind) {
     shiftnd_problem r = *p;
     r.dtype = p->dtype & ~SHIFTND_FRAMES;
-    return tshift_problem(&r, q, wkind);
+    bool per_clip;
+    const int rc = tshift_problem(&r, q, wkind, per_clip);
+    if (rc != SHIFTND_OK) return rc;
+    return per_clip ? SHIFTND_ERR_INVALID_ARGUMENT : SHIFTND_OK;   // (the frame kernels take a [C] table alone)
 }
 
 bool empty_geometry(const Geometry &g) { return g.N == 0 || g.C == 0 || g.S[0] * g.S[1] * g.S[2] == 0; }
@@ -366,21 +376,26 @@ int tshift_forward_call(const shiftnd_problem *p, const void *x, const int64_t *
     if (out && out == x) {   // in place: its own kernel, or refused (SHIFTND_FRAMES asks for kernels that have no such form)
         shiftnd_problem q;
         int wkind;
+        bool per_clip;
         if (p->dtype & SHIFTND_FRAMES) return SHIFTND_ERR_INVALID_ARGUMENT;
-        const int rc = tshift_problem(p, q, wkind);
+        const int rc = tshift_problem(p, q, wkind, per_clip);
+        if (rc == SHIFTND_OK && per_clip) return SHIFTND_ERR_INVALID_ARGUMENT;   // (the in-place kernel takes a [C] table alone)
         return rc != SHIFTND_OK ? rc : inplace_call(q, out, xs, os, w, wkind, 0, 0ull, stream);
     }
     if (p->dtype & SHIFTND_FRAMES) return frames_learn_forward_call(p, x, xs, w, out, os, stream);
     shiftnd_problem q;
     int wkind;
-    int rc = tshift_problem(p, q, wkind);
+    bool per_clip;
+    int rc = tshift_problem(p, q, wkind, per_clip);
     if (rc != SHIFTND_OK) return rc;
     Geometry g;
     rc = build_geometry(&q, xs, os, nullptr, g);
     if (rc != SHIFTND_OK) return rc;
     // two layouts are served: segment-major (the tshift kernels, sparse and interpolating) and, for the sparse shift, channels-last
-    // (shiftnd_frames.hip).  A tensor both describe (planes or channels of size 1) stays with the tshift kernels
-    const bool segment_sizes = tshift_geometry_ok(g, q.dtype), frames_sizes = frames_geometry_ok(g, q.dtype);
+    // (shiftnd_frames.hip).  A tensor both describe (planes or channels of size 1) stays with the tshift kernels.  A per-clip table:
+    // the tshift kernels alone
+    const bool segment_sizes = tshift_geometry_ok(g, q.dtype) && (!per_clip || per_clip_table_ok(g));
+    const bool frames_sizes = !per_clip && frames_geometry_ok(g, q.dtype);
     if (!segment_sizes && !frames_sizes) return SHIFTND_ERR_INVALID_ARGUMENT;
     if (empty_problem(g)) {
         g_last_path = SHIFTND_PATH_EMPTY;
@@ -389,7 +404,7 @@ int tshift_forward_call(const shiftnd_problem *p, const void *x, const int64_t *
     if (!x || !w || !out) return SHIFTND_ERR_INVALID_ARGUMENT;
     if (segment_sizes && tshift_tensor_ok(g, q.dtype, x, g.xs) && tshift_tensor_ok(g, q.dtype, out, g.os)) {
         g_last_path = SHIFTND_PATH_PLANE;
-        return finish(tshift_forward(g, q.dtype, x, w, wkind, out, static_cast<hipStream_t>(stream)));
+        return finish(tshift_forward(g, q.dtype, x, w, wkind, per_clip, out, static_cast<hipStream_t>(stream)));
     }
     if (frames_sizes && frames_tensor_ok(g, q.dtype, x, g.xs) && frames_tensor_ok(g, q.dtype, out, g.os)) {
         g_last_path = SHIFTND_PATH_CL;
@@ -423,17 +438,19 @@ int tshift_backward_call(const shiftnd_problem *p, const void *go, const int64_t
     if (p->dtype & SHIFTND_FRAMES) return frames_learn_backward_call(p, go, gos, x, xs, w, gx, gxs, gw, workspace, workspace_bytes, stream);
     shiftnd_problem q;
     int wkind;
-    int rc = tshift_problem(p, q, wkind);
+    bool per_clip;
+    int rc = tshift_problem(p, q, wkind, per_clip);
     if (rc != SHIFTND_OK) return rc;
     if (!x || !xs || !gw) return SHIFTND_ERR_INVALID_ARGUMENT;   // (the x == NULL form does not exist under the flag)
     Geometry g;
     rc = build_geometry(&q, xs, gos, gxs, g);
     if (rc != SHIFTND_OK) return rc;
-    if (!tshift_geometry_ok(g, q.dtype)) return SHIFTND_ERR_INVALID_ARGUMENT;
+    if (!tshift_geometry_ok(g, q.dtype) || (per_clip && !per_clip_table_ok(g))) return SHIFTND_ERR_INVALID_ARGUMENT;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (g.N == 0 || g.C == 0 || g.S[0] * g.S[1] * g.S[2] == 0) {
         g_last_path = SHIFTND_PATH_EMPTY;
-        if (g.C > 0 && hipMemsetAsync(gw, 0, static_cast<size_t>(g.C) * dtype_size(wkind), st) != hipSuccess) return SHIFTND_ERR_LAUNCH_FAILED;
+        const size_t entries = static_cast<size_t>(per_clip ? g.N * g.C : g.C);
+        if (entries > 0 && hipMemsetAsync(gw, 0, entries * dtype_size(wkind), st) != hipSuccess) return SHIFTND_ERR_LAUNCH_FAILED;
         return SHIFTND_OK;
     }
     if (!go || !w || !gx || !workspace) return SHIFTND_ERR_INVALID_ARGUMENT;
@@ -441,7 +458,7 @@ int tshift_backward_call(const shiftnd_problem *p, const void *go, const int64_t
         return SHIFTND_ERR_INVALID_ARGUMENT;
     if (tshift_backward_workspace(g, q.dtype) > workspace_bytes) return SHIFTND_ERR_WORKSPACE_TOO_SMALL;
     g_last_path = SHIFTND_PATH_PLANE;
-    return finish(tshift_backward(g, q.dtype, go, x, w, wkind, gx, gw, workspace, st));
+    return finish(tshift_backward(g, q.dtype, go, x, w, wkind, per_clip, gx, gw, workspace, st));
 }
 
 }  // namespace
@@ -612,6 +629,9 @@ size_t shiftnd_backward_workspace_bytes(const shiftnd_problem *p) {
     if (!p) return 0;
     shiftnd_problem q;
     int wkind;
+    // every entry point refuses the bit alone, so the answer is 0.  (The path below would not give it: it looks at the geometry and sizes
+    // the families' plans whatever unknown bits the dtype carries -- 0x800 on F32 answers 512 bytes there, an answer a test pins)
+    if ((p->dtype & SHIFTND_PER_CLIP) && !(p->dtype & SHIFTND_SHIFT_DIM0)) return 0;
     if (p->dtype & SHIFTND_SHIFT_DIM0) {   // the walk's plan alone: no other family runs under the flag, no knob shapes it
         const int64_t unit[5] = {0, 0, 0, 0, 0};
         Geometry g;
@@ -621,8 +641,9 @@ size_t shiftnd_backward_workspace_bytes(const shiftnd_problem *p) {
             if (g.N == 0 || g.C == 0 || g.S[0] * g.S[1] * g.S[2] == 0) return sizeof(double);
             return frames_backward_workspace(g, q.dtype);
         }
-        if (tshift_problem(p, q, wkind) != SHIFTND_OK || build_geometry(&q, unit, unit, unit, g) != SHIFTND_OK) return 0;
-        if (!tshift_geometry_ok(g, q.dtype)) return 0;
+        bool per_clip;   // (a per-clip table re-indexes the same records: the same bytes with and without SHIFTND_PER_CLIP)
+        if (tshift_problem(p, q, wkind, per_clip) != SHIFTND_OK || build_geometry(&q, unit, unit, unit, g) != SHIFTND_OK) return 0;
+        if (!tshift_geometry_ok(g, q.dtype) || (per_clip && !per_clip_table_ok(g))) return 0;
         if (g.N == 0 || g.C == 0 || g.S[0] * g.S[1] * g.S[2] == 0) return sizeof(double);
         return tshift_backward_workspace(g, q.dtype);
     }

@@ -222,13 +222,14 @@ int segment_forward(const Geometry &g, int dtype, const void *x, const void *w, 
 
 // ---- the learnable temporal shift (shiftnd_tshift.hip; SHIFTND_SHIFT_DIM0): a 1-D sparse / interpolating shift along S0 of
 // segment-major float tensors, `w` and `gw` [C] arrays, whole window.  tshift_geometry_ok: the sizes; tshift_tensor_ok: one tensor's
-// base and strides (normalised order).  No fallback: C, S0 or planes of size 1 are served too.
+// base and strides (normalised order).  No fallback: C, S0 or planes of size 1 are served too.  `per_clip` (SHIFTND_PER_CLIP): `w` and
+// `gw` are [N, C] arrays, one row per clip -- the same kernels, the same workspace; the caller has checked N * C < 2^31.
 bool tshift_geometry_ok(const Geometry &g, int dtype);
 bool tshift_tensor_ok(const Geometry &g, int dtype, const void *p, const int64_t *strides);
-int tshift_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, void *out, hipStream_t st);
+int tshift_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, bool per_clip, void *out, hipStream_t st);
 size_t tshift_backward_workspace(const Geometry &g, int dtype);
-int tshift_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw,
-                    void *workspace, hipStream_t st);
+int tshift_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, bool per_clip, void *gx,
+                    void *gw, void *workspace, hipStream_t st);
 
 // ---- the temporal shift of channels-last tensors (shiftnd_frames.hip; SHIFTND_SHIFT_DIM0 on a channels-last view): the sparse shift
 // along S0 of float and quantized (I8, U8, I32) tensors in memory order N, S0, S1, S2, C, `w` a [C] table, whole window; channel

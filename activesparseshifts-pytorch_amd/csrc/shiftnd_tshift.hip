@@ -28,6 +28,12 @@
 // correct everywhere, never outside the tensors, slower.  U is launch-uniform: one kernel per element type and pass (8 kernels),
 // `active` a run-time argument too.  No LDS beyond block_sum's, no scratch.
 //
+// Per-clip tables (SHIFTND_PER_CLIP).  `weights` / `grad_w` of shape [N, C], one row per clip: the same kernels under a
+// launch-uniform row stride (TShiftParams::wrow: 0 for the [C] table, C for [N, C]) -- the weight of (n, c) is entry n * wrow + c, one
+// integer multiply-add on values both kernels hold already.  The walk's partial record moves from ((n * chunks + chunk) * C + c) to
+// ((chunk * N + n) * C + c): `chunks` groups of N * C entries, so that launch_reduce_weight_grads sums per (n, c) -- the same
+// records, the same workspace bytes, a fixed order.  No new kernel, no template parameter.
+//
 // Not built: the quantized form, a cut window, channels-last tensors.
 #include <initializer_list>
 
@@ -46,6 +52,8 @@ struct TShiftParams {
     uint32_t T, C, upp, chunks;        // segments, channels, units per plane, workgroups per (n, c) line (backward)
     FastDiv d_upp, d_C, d_T, d_per, d_chunks;   // d_per: by map_period(T, pad)
     int64_t plane_bytes, units;        // units: of the whole tensor (forward)
+    uint32_t wrow, clips;              // weight of (n, c): entry n * wrow + c -- 0 for a [C] table, C for a per-clip [N, C] one; N
+                                       // (behind the fields the per-channel call reads, whose offsets stay what they were)
 };
 
 template <typename T, int E> struct Unit { typename T::S e[E]; };
@@ -107,7 +115,7 @@ __device__ __forceinline__ void forward_body(const TShiftParams &q, const char *
         const uint32_t nt = fdiv(plane, q.d_C), c = plane - nt * q.C;
         const uint32_t n = fdiv(nt, q.d_T), t = nt - n * q.T;
         int64_t iw;
-        prep_shift_forward<CT>(load_weight<CT>(w, q.wkind, c), q.active != 0, iw, dw[k]);
+        prep_shift_forward<CT>(load_weight<CT>(w, q.wkind, n * q.wrow + c), q.active != 0, iw, dw[k]);
         const int cs = canon_shift(iw, Tn, q.pad, q.d_per);
         const int s0 = source_segment(static_cast<int>(t), cs, Tn, q.pad), s1 = source_segment(static_cast<int>(t) + 1, cs, Tn, q.pad);
         const int64_t clip = static_cast<int64_t>(n) * q.T;
@@ -138,7 +146,7 @@ __device__ __forceinline__ double backward_body(const TShiftParams &q, const cha
     const int Tn = static_cast<int>(q.T);
     int64_t sh;
     CT dw;
-    prep_shift_backward<CT>(load_weight<CT>(w, q.wkind, c), q.active != 0, sh, dw);
+    prep_shift_backward<CT>(load_weight<CT>(w, q.wkind, n * q.wrow + c), q.active != 0, sh, dw);
     const int cs = canon_shift(sh, Tn, q.pad, q.d_per);     // x (and, interpolating, grad_out) at pad(t - sh), pad(t + 1 - sh)
     const int csn = canon_shift(-sh, Tn, q.pad, q.d_per);   // the sparse shift's grad_x: grad_out at pad(t + sh)
     const int64_t clip = static_cast<int64_t>(n) * q.T;
@@ -222,7 +230,9 @@ __global__ __launch_bounds__(kThreads) void tshift_backward(TShiftParams q, cons
     with_unit<16 / static_cast<int>(sizeof(typename T::S))>(
         elems, [&](auto e) { acc = backward_body<T, decltype(e)::value>(q, go, x, w, gx, n, c, chunk); });
     const double total = block_sum(acc, scratch);
-    if (threadIdx.x == 0) partials[((static_cast<size_t>(n) * q.chunks + chunk) * q.C + c) * 3] = total;
+    // group n * chunks + chunk of C channels, or -- a per-clip table -- group chunk of the N * C entries n * C + c
+    const uint32_t group = q.wrow ? chunk * q.clips + n : n * q.chunks + chunk;   // (below 2^31: the reduction counts groups in an int)
+    if (threadIdx.x == 0) partials[(static_cast<size_t>(group) * q.C + c) * 3] = total;
 }
 
 int64_t inner_elements(const Geometry &g) { return (g.nd == 3 ? g.S[1] : 1) * g.S[2]; }
@@ -245,13 +255,15 @@ int unit_bytes(int64_t plane_bytes, std::initializer_list<const void *> bases) {
     return static_cast<int>(bits & (~bits + 1));
 }
 
-TShiftParams make_params(const Geometry &g, int dtype, int wkind, int unit) {
+TShiftParams make_params(const Geometry &g, int dtype, int wkind, int unit, bool per_clip) {
     TShiftParams q;
     q.pad = g.pad;
     q.wkind = wkind;
     q.active = g.active;
     q.T = static_cast<uint32_t>(g.S[3 - g.nd]);
     q.C = static_cast<uint32_t>(g.C);
+    q.wrow = per_clip ? q.C : 0;
+    q.clips = static_cast<uint32_t>(g.N);
     q.plane_bytes = inner_elements(g) * dtype_size(dtype);
     q.upp = static_cast<uint32_t>(q.plane_bytes / unit);
     q.chunks = static_cast<uint32_t>((q.plane_bytes + kChunkBytes - 1) / kChunkBytes);
@@ -295,9 +307,9 @@ bool tshift_tensor_ok(const Geometry &g, int dtype, const void *p, const int64_t
     return aligned_to(p, dtype_size(dtype)) && dense_segment_major(g, strides);
 }
 
-int tshift_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, void *out, hipStream_t st) {
+int tshift_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, bool per_clip, void *out, hipStream_t st) {
     const int unit = unit_bytes(inner_elements(g) * dtype_size(dtype), {x, out});
-    const TShiftParams q = make_params(g, dtype, wkind, unit);
+    const TShiftParams q = make_params(g, dtype, wkind, unit, per_clip);
     note_kernel(unit == 16 ? "tshift_forward" : "tshift_forward_ragged");
     switch (dtype) {
     case SHIFTND_F32: launch_forward<f32_t>(q, x, w, out, unit, st); break;
@@ -313,10 +325,10 @@ size_t tshift_backward_workspace(const Geometry &g, int dtype) {
     return static_cast<size_t>(g.N * ((plane_bytes + kChunkBytes - 1) / kChunkBytes) * g.C) * 3 * sizeof(double);
 }
 
-int tshift_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw,
-                    void *workspace, hipStream_t st) {
+int tshift_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, bool per_clip, void *gx,
+                    void *gw, void *workspace, hipStream_t st) {
     const int unit = unit_bytes(inner_elements(g) * dtype_size(dtype), {go, x, gx});
-    const TShiftParams q = make_params(g, dtype, wkind, unit);
+    const TShiftParams q = make_params(g, dtype, wkind, unit, per_clip);
     double *partials = static_cast<double *>(workspace);
     note_kernel(unit == 16 ? "tshift_backward" : "tshift_backward_ragged");
     const int64_t lines = g.N * g.C;
@@ -326,7 +338,9 @@ int tshift_backward(const Geometry &g, int dtype, const void *go, const void *x,
     case SHIFTND_F16: launch_backward<f16_t>(q, lines, go, x, w, gx, partials, unit, st); break;
     default: launch_backward<bf16_t>(q, lines, go, x, w, gx, partials, unit, st); break;
     }
-    launch_reduce_weight_grads(wkind, partials, static_cast<int>(g.N * q.chunks), static_cast<int>(g.C), 1, gw, st);
+    // [C] table: N * chunks groups of C entries; [N, C] table: chunks groups of N * C entries (the same records, the same bytes)
+    const int64_t groups = per_clip ? q.chunks : g.N * q.chunks, entries = per_clip ? g.N * g.C : g.C;
+    launch_reduce_weight_grads(wkind, partials, static_cast<int>(groups), static_cast<int>(entries), 1, gw, st);
     return SHIFTND_OK;
 }
 

@@ -14,8 +14,11 @@
 //   temporal cl   temporal_shift_cl / _temporal_shift_cl_backward / temporal_shift_quantized_cl: ... keeping a channels-last layout
 //   learnable     temporal_shift_learnable / _temporal_shift_learnable_forward / _backward: a trained shift across the frames
 //   learnable cl  temporal_shift_learnable_cl / _temporal_shift_learnable_cl_forward / _backward: ... keeping a channels-last layout
-// ... and, in a namespace of its own (torchshifts_inplace::, registered last), the one family that writes its argument:
-//   in place      temporal_shift_ / temporal_shift_quantized_: the temporal shift written into the input (composes on CPU tensors)
+// ... and, in namespaces of their own (registered last), the families that came after the op set of torchshifts:: was pinned:
+//   per clip      torchshifts_per_clip::temporal_shift_learnable_per_clip / _forward / _backward, temporal_shift_per_clip /
+//                 _temporal_shift_per_clip_backward: the temporal shifts under a [N, C] table, one row per clip
+//   in place      torchshifts_inplace::temporal_shift_ / temporal_shift_quantized_: the temporal shift written into the input (composes
+//                 on CPU tensors), the one family that writes its argument
 //
 // Keys: the Autograd, CUDA and QuantizedCUDA kernels of every family are registered here.  The CPU / QuantizedCPU kernels that
 // compute (shift, fixed, fixed pool, temporal, temporal_shift_quantized) live in torch_cpu_backend.cpp; the ones that compose other
@@ -1321,6 +1324,200 @@ std::tuple<Tensor, Tensor> tsl_cl_backward_hip(const Tensor &grad, const Tensor 
     return std::make_tuple(grad_input, grad_weights);
 }
 
+// ---- per-clip temporal shift: torchshifts_per_clip::temporal_shift_learnable_per_clip / temporal_shift_per_clip ---------------------
+// The temporal shifts under a table of shape [N, C], N = input.size(0) / n_segment: clip n is shifted by row n (a shift that a small
+// net predicts from the clip -- TIN's OffsetNet, arXiv 2001.06499 -- or per-clip temporal jitter).  By definition, for every clip n,
+//     out[n*T:(n+1)*T] = temporal_shift_learnable(x[n*T:(n+1)*T], weights[n], T, padding_mode, active_flag)
+// with that call's x.grad, and weights.grad[n] that call's weights.grad; the fixed op is the same loop over temporal_shift, without a
+// table gradient.  The CPU key is literally that loop.  On HIP tensors every pass is ONE C-ABI call on the contiguous tensor under
+// SHIFTND_SHIFT_DIM0 | SHIFTND_PER_CLIP (shiftnd_tshift.hip, the kernels of temporal_shift_learnable): the learnable op's backward
+// is shiftnd_backward; the fixed op's forward is shiftnd_forward with active == 0, which copies bit patterns, and its backward the
+// same call on the gradient under the negated table, so that no kernel reads the input or forms a weight gradient.  Its table is
+// built like the channels-last routes': fp32 for 16-bit tensors (every shift exact), the tensor's dtype for fp32 / fp64.
+// A namespace of its own for the reason torchshifts_inplace:: has one.
+template <class Sig> c10::TypedOperatorHandle<Sig> per_clip_op(const char *name) {
+    return c10::Dispatcher::singleton().findSchemaOrThrow((std::string("torchshifts_per_clip::") + name).c_str(), "").typed<Sig>();
+}
+struct PerClipLearnableOps {
+    static const char *name() { return "temporal_shift_learnable_per_clip"; }
+    static auto &forward() { static auto op = per_clip_op<tsl_forward_sig>("_temporal_shift_learnable_per_clip_forward"); return op; }
+    static auto &backward() { static auto op = per_clip_op<tsl_backward_sig>("_temporal_shift_learnable_per_clip_backward"); return op; }
+};
+struct PerClipOps {
+    static const char *name() { return "temporal_shift_per_clip"; }
+    static auto &forward() { static auto op = per_clip_op<temporal_sig>("temporal_shift_per_clip"); return op; }
+    static auto &backward() { static auto op = per_clip_op<temporal_sig>("_temporal_shift_per_clip_backward"); return op; }
+};
+
+// segment_check for a [N, C] table
+void per_clip_check(const char *op_name, const Tensor &input, const Tensor &table, int64_t n_segment, int64_t padding_mode,
+                    const char *kind, bool table_type_ok, const char *table_types) {
+    TORCH_CHECK(!input.is_quantized(), op_name, ": quantized inputs are not supported");
+    TORCH_CHECK(input.dim() >= 2 && input.dim() <= 5, op_name, ": expected a [N*T, C, ...] tensor of 2 to 5 dims");
+    TORCH_CHECK(n_segment >= 1 && input.size(0) % n_segment == 0, op_name, ": dim 0 (", input.size(0),
+                ") must be a multiple of n_segment (", n_segment, ")");
+    TORCH_CHECK(table.dim() == 2 && table.size(0) == input.size(0) / n_segment && table.size(1) == input.size(1), op_name, ": ", kind,
+                " must have shape [N, C] = [", input.size(0) / n_segment, ", ", input.size(1), "]");
+    TORCH_CHECK(table.device() == input.device(), op_name, ": ", kind, " must be on the input's device");
+    TORCH_CHECK(table_type_ok, op_name, ": ", kind, " must be ", table_types);
+    TORCH_CHECK(padding_mode >= 0 && padding_mode <= 4, op_name, ": padding_mode must be 0..4");
+}
+void tslpc_check(const Tensor &input, const Tensor &weights, int64_t n_segment, int64_t padding_mode) {
+    per_clip_check("temporal_shift_learnable_per_clip", input, weights, n_segment, padding_mode, "weights",
+                   at::isFloatingType(weights.scalar_type()), "floats");
+}
+void tpc_check(const Tensor &input, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    per_clip_check("temporal_shift_per_clip", input, shifts, n_segment, padding_mode, "shifts", is_integer_or_float(shifts),
+                   "integers or floats");
+}
+
+// the public entry and the Autograd-key kernels: the nodes are temporal_shift_learnable's (input and weights kept) and
+// temporal_shift's (the table alone kept)
+Tensor tslpc_public(const Tensor &input, const Tensor &weights, int64_t n_segment, int64_t padding_mode, bool active_flag) {
+    tslpc_check(input, weights, n_segment, padding_mode);
+    return PerClipLearnableOps::forward().call(input, weights, n_segment, padding_mode, active_flag);
+}
+Tensor tslpc_autograd(const Tensor &input, const Tensor &weights, int64_t n_segment, int64_t padding_mode, bool active_flag) {
+    tslpc_check(input, weights, n_segment, padding_mode);
+    return LearnableTemporalShiftFunction<PerClipLearnableOps>::apply(input, weights, n_segment, padding_mode, active_flag)[0];
+}
+std::tuple<Tensor, Tensor> tslpc_autograd_backward(const Tensor &grad, const Tensor &weights, const Tensor &input, int64_t n_segment,
+                                                   int64_t padding_mode, bool active_flag) {
+    tslpc_check(input, weights, n_segment, padding_mode);
+    return GuardedBackward<PerClipLearnableOps>::kernel(grad, weights, input, n_segment, padding_mode, active_flag);
+}
+Tensor tpc_autograd(const Tensor &input, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    tpc_check(input, shifts, n_segment, padding_mode);
+    return TemporalShiftFunction<PerClipOps>::apply(input, shifts, n_segment, padding_mode)[0];
+}
+Tensor tpc_autograd_backward(const Tensor &grad, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    tpc_check(grad, shifts, n_segment, padding_mode);
+    return GuardedBackward<PerClipOps>::kernel(grad, shifts, n_segment, padding_mode);
+}
+
+// CPU tensors: the loop of the definition over the per-channel CPU routines
+Tensor tslpc_forward_cpu(const Tensor &input, const Tensor &weights, int64_t n_segment, int64_t padding_mode, bool active_flag) {
+    TORCH_CHECK(input.device().is_cpu() && weights.device().is_cpu(), "temporal_shift_learnable_per_clip_cpu: expected CPU tensors");
+    tslpc_check(input, weights, n_segment, padding_mode);
+    if (input.numel() == 0) return at::empty(input.sizes(), input.options(), at::MemoryFormat::Contiguous);
+    std::vector<Tensor> clips;
+    for (int64_t n = 0; n < weights.size(0); ++n)
+        clips.push_back(tsl_forward_cpu(input.narrow(0, n * n_segment, n_segment), weights.select(0, n), n_segment, padding_mode, active_flag));
+    return at::cat(clips, 0);
+}
+
+std::tuple<Tensor, Tensor> tslpc_backward_cpu(const Tensor &grad, const Tensor &weights, const Tensor &input, int64_t n_segment,
+                                              int64_t padding_mode, bool active_flag) {
+    TORCH_CHECK(grad.device().is_cpu() && input.device().is_cpu() && weights.device().is_cpu(),
+                "temporal_shift_learnable_per_clip_cpu: expected CPU tensors");
+    tslpc_check(input, weights, n_segment, padding_mode);
+    TORCH_CHECK(grad.sizes() == input.sizes(), "temporal_shift_learnable_per_clip backward: grad does not match the input");
+    if (input.numel() == 0)
+        return std::make_tuple(at::empty(input.sizes(), input.options(), at::MemoryFormat::Contiguous), at::zeros_like(weights));
+    std::vector<Tensor> gx, gw;
+    for (int64_t n = 0; n < weights.size(0); ++n) {
+        auto clip = tsl_backward_cpu(grad.narrow(0, n * n_segment, n_segment), weights.select(0, n),
+                                     input.narrow(0, n * n_segment, n_segment), n_segment, padding_mode, active_flag);
+        gx.push_back(std::get<0>(clip));
+        gw.push_back(std::get<1>(clip));
+    }
+    return std::make_tuple(at::cat(gx, 0), at::stack(gw, 0));
+}
+
+Tensor tpc_cpu(const Tensor &t, const Tensor &shifts, int64_t n_segment, int64_t padding_mode, bool backward) {
+    TORCH_CHECK(t.device().is_cpu() && shifts.device().is_cpu(), "temporal_shift_per_clip_cpu: expected CPU tensors");
+    tpc_check(t, shifts, n_segment, padding_mode);
+    if (t.numel() == 0) return at::empty(t.sizes(), t.options(), at::MemoryFormat::Contiguous);
+    auto &op = backward ? TemporalOps::backward() : TemporalOps::forward();
+    std::vector<Tensor> clips;
+    for (int64_t n = 0; n < shifts.size(0); ++n)
+        clips.push_back(op.call(t.narrow(0, n * n_segment, n_segment), shifts.select(0, n), n_segment, padding_mode));
+    return at::cat(clips, 0);
+}
+Tensor tpc_forward_cpu(const Tensor &input, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    return tpc_cpu(input, shifts.detach(), n_segment, padding_mode, false);
+}
+Tensor tpc_backward_cpu(const Tensor &grad, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    return tpc_cpu(grad, shifts.detach(), n_segment, padding_mode, true);
+}
+
+// HIP tensors: one call under SHIFTND_SHIFT_DIM0 | SHIFTND_PER_CLIP on the segment-major strides
+Tensor tslpc_forward_hip(const Tensor &input_, const Tensor &weights, int64_t n_segment, int64_t padding_mode, bool active_flag) {
+    TORCH_CHECK(input_.is_cuda(), "temporal_shift_learnable_per_clip: expected a CUDA tensor");
+    tslpc_check(input_, weights, n_segment, padding_mode);
+    const int mixed = weights_flag("temporal_shift_learnable_per_clip_cuda", input_, "input", weights);
+    c10::DeviceGuard device_guard(input_.device());
+    const int dtype = to_shiftnd_dtype(input_.scalar_type(), "temporal_shift_learnable_per_clip_cuda") | mixed;
+    tsl_check_size(input_, "temporal_shift_learnable");
+    const Tensor input = input_.contiguous();
+    Tensor output = at::empty(input.sizes(), input.options(), at::MemoryFormat::Contiguous);
+    if (input.numel() == 0) return output;
+    const Tensor w = weights.contiguous();
+    shiftnd_problem p;
+    int64_t st[5];
+    segment_problem(p, st, input, n_segment, padding_mode, active_flag, dtype | SHIFTND_SHIFT_DIM0 | SHIFTND_PER_CLIP, false,
+                    "temporal_shift_learnable_per_clip");
+    check_status(shiftnd_forward(&p, input.data_ptr(), st, w.data_ptr(), output.data_ptr(), st, current_stream(input)),
+                 "temporal_shift_learnable_per_clip (HIP)");
+    return output;
+}
+
+std::tuple<Tensor, Tensor> tslpc_backward_hip(const Tensor &grad_, const Tensor &weights, const Tensor &input_, int64_t n_segment,
+                                              int64_t padding_mode, bool active_flag) {
+    TORCH_CHECK(grad_.is_cuda() && input_.is_cuda(), "temporal_shift_learnable_per_clip: expected CUDA tensors");
+    tslpc_check(input_, weights, n_segment, padding_mode);
+    check_same("temporal_shift_learnable_per_clip_backward_cuda", grad_, "grad", input_, "input");
+    const int mixed = weights_flag("temporal_shift_learnable_per_clip_backward_cuda", grad_, "grad", weights);
+    TORCH_CHECK(grad_.sizes() == input_.sizes(), "temporal_shift_learnable_per_clip backward: grad does not match the input");
+    c10::DeviceGuard device_guard(grad_.device());
+    const int dtype = to_shiftnd_dtype(grad_.scalar_type(), "temporal_shift_learnable_per_clip_backward_cuda") | mixed;
+    tsl_check_size(input_, "temporal_shift_learnable backward");
+    const Tensor input = input_.contiguous(), grad = grad_.contiguous();
+    const Tensor w = weights.contiguous();
+    Tensor grad_input = at::empty(input.sizes(), input.options(), at::MemoryFormat::Contiguous);
+    Tensor grad_weights = at::empty_like(w, at::MemoryFormat::Contiguous);   // (the weights' dtype: fp32 for a mixed call)
+    if (input.numel() == 0) return std::make_tuple(grad_input, grad_weights.zero_());   // (no kernel runs: the zero gradient is written here)
+    shiftnd_problem p;
+    int64_t st[5];
+    segment_problem(p, st, input, n_segment, padding_mode, active_flag, dtype | SHIFTND_SHIFT_DIM0 | SHIFTND_PER_CLIP, false,
+                    "temporal_shift_learnable_per_clip");
+    const size_t ws_bytes = shiftnd_backward_workspace_bytes(&p);
+    Tensor workspace = workspace_like(input, ws_bytes);
+    check_status(shiftnd_backward(&p, grad.data_ptr(), st, input.data_ptr(), st, w.data_ptr(), grad_input.data_ptr(), st,
+                                  grad_weights.data_ptr(), workspace.data_ptr(), ws_bytes, current_stream(grad)),
+                 "temporal_shift_learnable_per_clip backward (HIP)");
+    return std::make_tuple(grad_input, grad_weights);
+}
+
+Tensor tpc_hip(const Tensor &t_, const Tensor &shifts, int64_t n_segment, int64_t padding_mode, bool backward) {
+    TORCH_CHECK(t_.is_cuda(), "temporal_shift_per_clip: expected a CUDA tensor");
+    tpc_check(t_, shifts, n_segment, padding_mode);
+    c10::DeviceGuard device_guard(t_.device());
+    const bool half = t_.scalar_type() == at::kHalf || t_.scalar_type() == at::kBFloat16;
+    const int dtype = to_shiftnd_dtype(t_.scalar_type(), "temporal_shift_per_clip_cuda") | (half ? SHIFTND_WEIGHTS_F32 : 0);
+    tsl_check_size(t_, "temporal_shift_per_clip");
+    const Tensor t = t_.contiguous();
+    Tensor out = at::empty(t.sizes(), t.options(), at::MemoryFormat::Contiguous);
+    if (t.numel() == 0) return out;
+    Tensor w = shifts.detach();
+    if (at::isFloatingType(w.scalar_type())) w = w.round();   // (half to even, before the table's type can move an entry onto a half)
+    w = w.to(half ? at::kFloat : t.scalar_type());
+    // (grad_x[t] = grad_out[pad(t + s)]: the forward under -s.)  The library reads a dense [N, C] array, and round / to / neg keep the
+    // strides of a transposed table: contiguous after them, in both directions
+    w = (backward ? w.neg() : w).contiguous();
+    shiftnd_problem p;
+    int64_t st[5];
+    segment_problem(p, st, t, n_segment, padding_mode, false, dtype | SHIFTND_SHIFT_DIM0 | SHIFTND_PER_CLIP, false, "temporal_shift_per_clip");
+    check_status(shiftnd_forward(&p, t.data_ptr(), st, w.data_ptr(), out.data_ptr(), st, current_stream(t)), "temporal_shift_per_clip (HIP)");
+    return out;
+}
+Tensor tpc_forward_hip(const Tensor &input, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    return tpc_hip(input, shifts, n_segment, padding_mode, false);
+}
+Tensor tpc_backward_hip(const Tensor &grad, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    return tpc_hip(grad, shifts, n_segment, padding_mode, true);
+}
+
 // ---- in-place temporal shift: torchshifts_inplace::temporal_shift_ / temporal_shift_quantized_ -------------------------------------
 // The values of temporal_shift / temporal_shift_quantized written into the argument, which is returned.  A second library namespace,
 // because the op set of torchshifts:: is the reference's surface plus the families above and stays as it is.  On HIP tensors a dense
@@ -1615,6 +1812,34 @@ TORCH_LIBRARY_IMPL(torchshifts, QuantizedCUDA, m) {
     m.impl("_shift3d_pool_forward", TORCH_FN(qpool_forward_hip<3>));
     m.impl("temporal_shift_quantized", TORCH_FN(temporal_quantized_hip));
     m.impl("temporal_shift_quantized_cl", TORCH_FN(temporal_quantized_cl_hip));
+}
+
+// the per-clip temporal shifts: their own namespace (the op set of torchshifts:: is pinned)
+TORCH_LIBRARY(torchshifts_per_clip, m) {
+    m.def("torchshifts_per_clip::temporal_shift_learnable_per_clip(Tensor input, Tensor weights, int n_segment, int padding_mode, bool active_flag) -> Tensor", &tslpc_public);
+    m.def("torchshifts_per_clip::_temporal_shift_learnable_per_clip_forward(Tensor input, Tensor weights, int n_segment, int padding_mode, bool active_flag) -> Tensor");
+    m.def("torchshifts_per_clip::_temporal_shift_learnable_per_clip_backward(Tensor grad, Tensor weights, Tensor input, int n_segment, int padding_mode, bool active_flag) -> (Tensor, Tensor)");
+    m.def("torchshifts_per_clip::temporal_shift_per_clip(Tensor input, Tensor shifts, int n_segment, int padding_mode) -> Tensor");
+    m.def("torchshifts_per_clip::_temporal_shift_per_clip_backward(Tensor grad, Tensor shifts, int n_segment, int padding_mode) -> Tensor");
+}
+
+TORCH_LIBRARY_IMPL(torchshifts_per_clip, Autograd, m) {
+    m.impl("_temporal_shift_learnable_per_clip_forward", TORCH_FN(tslpc_autograd));
+    m.impl("_temporal_shift_learnable_per_clip_backward", TORCH_FN(tslpc_autograd_backward));
+    m.impl("temporal_shift_per_clip", TORCH_FN(tpc_autograd));
+    m.impl("_temporal_shift_per_clip_backward", TORCH_FN(tpc_autograd_backward));
+}
+TORCH_LIBRARY_IMPL(torchshifts_per_clip, CPU, m) {
+    m.impl("_temporal_shift_learnable_per_clip_forward", TORCH_FN(tslpc_forward_cpu));
+    m.impl("_temporal_shift_learnable_per_clip_backward", TORCH_FN(tslpc_backward_cpu));
+    m.impl("temporal_shift_per_clip", TORCH_FN(tpc_forward_cpu));
+    m.impl("_temporal_shift_per_clip_backward", TORCH_FN(tpc_backward_cpu));
+}
+TORCH_LIBRARY_IMPL(torchshifts_per_clip, CUDA, m) {
+    m.impl("_temporal_shift_learnable_per_clip_forward", TORCH_FN(tslpc_forward_hip));
+    m.impl("_temporal_shift_learnable_per_clip_backward", TORCH_FN(tslpc_backward_hip));
+    m.impl("temporal_shift_per_clip", TORCH_FN(tpc_forward_hip));
+    m.impl("_temporal_shift_per_clip_backward", TORCH_FN(tpc_backward_hip));
 }
 
 // the in-place temporal shift: its own namespace (the op set of torchshifts:: is pinned)

@@ -259,3 +259,49 @@ def temporal_shift_learnable_func(input: Tensor, weights: Tensor, n_segment: int
     if memory_format == torch.preserve_format:
         return torch.ops.torchshifts.temporal_shift_learnable_cl(input, weights, n_segment, padding_mode, bool(active_flag))
     return torch.ops.torchshifts.temporal_shift_learnable(input, weights, n_segment, padding_mode, bool(active_flag))
+
+
+# ---- per-clip temporal shift: a table of shape [N, n_channels], one row per clip of a [N * n_segment, C, ...] tensor ------------------
+# The temporal shifts above under a table that differs from clip to clip -- a shift that a small net predicts from the clip itself
+# (the Temporal Interlacing Network's OffsetNet, arXiv 2001.06499), or per-clip temporal jitter.  By definition, for every clip n,
+#   out[n*T:(n+1)*T] = temporal_shift_learnable_func(x[n*T:(n+1)*T], weights[n], T, padding_mode, active_flag)
+# (temporal_shift_func for the fixed form), with that call's x.grad, and weights.grad[n] that call's weights.grad, in both modes.
+# On HIP tensors it is ONE kernel per pass, the kernel of temporal_shift_learnable_func, instead of N launches and a cat: out and
+# x.grad carry the loop's bits, weights.grad is deterministic.  The result is contiguous.
+# The table is [N, n_channels], or [N, n_groups] with n_channels % n_groups == 0 (TIN's groups: entry g serves the n_channels //
+# n_groups consecutive channels of group g); a group table is expanded here, so autograd sums a group's gradient.
+def _per_clip_table(name: str, input: Tensor, table: Tensor, n_segment: int, padding_mode: int, kind: str) -> Tensor:
+    _assert_has_ops()
+    assert padding_mode in [0, 1, 2, 3, 4], f"{name} expected padding_mode can be {_PADDING_DOC}"
+    assert 2 <= len(input.shape) <= 5, f"{name}: expected a 2D to 5D tensor as input, but it is shape is {input.shape}"
+    assert isinstance(n_segment, int) and n_segment >= 1 and input.shape[0] % n_segment == 0, \
+        f"{name}: expected dim 0 of the input ({input.shape[0]}) to be a multiple of n_segment ({n_segment})"
+    assert not input.is_quantized, f"{name}: quantized inputs are not supported"
+    clips, channels = input.shape[0] // n_segment, input.shape[1]
+    assert (len(table.shape) == 2 and table.shape[0] == clips and table.shape[1] >= 1 and channels % table.shape[1] == 0), \
+        (f"{name}: expected [{clips}, {channels}] tensor (one row per clip; or [{clips}, n_groups] with {channels} % n_groups == 0) "
+         f"as {kind}, but it is shape is {table.shape}")
+    assert input.device == table.device, \
+        (f"{name}: expected input and {kind} to be on same device, but input is  on {input.device} "
+         f"and {kind} is on {table.device}")
+    if table.shape[1] != channels:
+        table = table.repeat_interleave(channels // table.shape[1], dim=1)
+    return table
+
+
+def temporal_shift_per_clip_func(input: Tensor, shifts: Tensor, n_segment: int, padding_mode: int = 0) -> Tensor:
+    """Shift the channels of a [N * n_segment, C, ...] tensor (2 to 5 dims) across the frames of each clip by the integers
+    shifts[n, c] of its own clip n.  Floats are rounded half to even; the autograd node keeps the table alone."""
+    name = "temporal_shift_per_clip_func()"
+    shifts = _per_clip_table(name, input, shifts, n_segment, padding_mode, "shifts")
+    return torch.ops.torchshifts_per_clip.temporal_shift_per_clip(input, shifts, n_segment, padding_mode)
+
+
+def temporal_shift_learnable_per_clip_func(input: Tensor, weights: Tensor, n_segment: int, padding_mode: int = 0,
+                                           active_flag: bool = False) -> Tensor:
+    """Shift the channels of a [N * n_segment, C, ...] tensor (2 to 5 dims) across the frames of each clip by weights[n, c] of its
+    own clip n, sparse (rounded) or active (interpolated); differentiable in input and weights."""
+    name = "temporal_shift_learnable_per_clip_func()"
+    assert weights.is_floating_point(), f"{name}: expected float weights, but they are {weights.dtype}"
+    weights = _per_clip_table(name, input, weights, n_segment, padding_mode, "weights")
+    return torch.ops.torchshifts_per_clip.temporal_shift_learnable_per_clip(input, weights, n_segment, padding_mode, bool(active_flag))

@@ -14,7 +14,8 @@ from torch import nn
 from torchshifts.functional import (shift1d_fixed_func, shift1d_fixed_pool_func, shift1d_func, shift1d_pool_func, shift2d_fixed_func,
                                     shift2d_fixed_pool_func, shift2d_func, shift2d_pool_func, shift3d_fixed_func,
                                     shift3d_fixed_pool_func, shift3d_func, shift3d_pool_func, temporal_shift_func, temporal_shift_func_,
-                                    temporal_shift_learnable_func)
+                                    temporal_shift_learnable_func, temporal_shift_learnable_per_clip_func,
+                                    temporal_shift_per_clip_func)
 
 paddings_dict = {'zeros': 0, 'border': 1, 'periodic': 2, 'reflect': 3, 'symmetric': 4}
 
@@ -416,3 +417,62 @@ class LearnableTemporalShift(nn.Module):
                   if bool(self.sparsity_term) else 'Sparse shift: No')
         return (f'n_segment={self.n_segment}, in_channels={self.in_channels}, padding_method={pad}, {active}, {sparse}, '
                 f'memory_format={self.memory_format}')
+
+
+class PerClipTemporalShift(nn.Module):
+    """Fixed shifts across the frames of a [N * n_segment, C, ...] tensor under a table that differs from clip to clip: channel c
+    of frame t of clip n becomes channel c of frame t - table[n, c] of the same clip (per-clip temporal jitter; the integer
+    offsets of a net that looks at the clip).  The module has no parameter and no buffer: the table comes from the caller, and
+    the autograd node keeps it alone.
+
+    Arguments:
+        n_segment (int): frames per clip, T.
+        padding (str): 'zeros' | 'border' | 'periodic' | 'reflect' | 'symmetric'. Default 'zeros'.
+    forward(x, table) -> output, the tensor alone.  table: [N, C] integers (floats are rounded half to even), or [N, G] with
+    C % G == 0, entry g serving the C // G consecutive channels of group g.
+    """
+
+    def __init__(self, n_segment, padding='zeros'):
+        super().__init__()
+        assert padding.lower() in paddings_dict.keys(), f'incorrect padding option: {padding}'
+        assert int(n_segment) >= 1, 'n_segment must be >= 1'
+        self.padding = paddings_dict[padding.lower()]
+        self.n_segment = int(n_segment)
+
+    def forward(self, input, table):
+        return temporal_shift_per_clip_func(input, table, self.n_segment, self.padding)
+
+    def extra_repr(self):
+        pad = {v: k for k, v in paddings_dict.items()}[self.padding]
+        return f'n_segment={self.n_segment}, padding_method={pad}, per-clip integer shifts'
+
+
+class LearnablePerClipTemporalShift(nn.Module):
+    """Differentiable shifts across the frames of a [N * n_segment, C, ...] tensor under a table that a net predicts from the clip
+    itself (the Temporal Interlacing Network's OffsetNet, arXiv 2001.06499): clip n is shifted by table[n], sparse (rounded) or,
+    with active_flag, interpolated between two frames; the gradient flows into the input and into the table, hence into the
+    net that produced it.  The module has no parameter and no buffer.
+
+    Arguments:
+        n_segment (int): frames per clip, T.
+        padding (str): 'zeros' | 'border' | 'periodic' | 'reflect' | 'symmetric'. Default 'zeros'.
+        active_flag (bool): interpolate on the forward pass (active shift). Default False.
+    forward(x, table) -> output, the tensor alone.  table: [N, C] floats of the input's dtype (float32 with a float16 / bfloat16
+    input works too), or [N, G] with C % G == 0 (TIN's groups): a group's gradient is the sum over its channels.
+    """
+
+    def __init__(self, n_segment, padding='zeros', active_flag=False):
+        super().__init__()
+        assert padding.lower() in paddings_dict.keys(), f'incorrect padding option: {padding}'
+        assert int(n_segment) >= 1, 'n_segment must be >= 1'
+        self.padding = paddings_dict[padding.lower()]
+        self.n_segment = int(n_segment)
+        self._active_flag = active_flag
+
+    def forward(self, input, table):
+        return temporal_shift_learnable_per_clip_func(input, table, self.n_segment, self.padding, self._active_flag)
+
+    def extra_repr(self):
+        pad = {v: k for k, v in paddings_dict.items()}[self.padding]
+        active = f'Active shift on forward pass: {"Yes" if self._active_flag else "No"}'
+        return f'n_segment={self.n_segment}, padding_method={pad}, {active}, per-clip weights'

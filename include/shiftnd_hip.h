@@ -174,6 +174,27 @@ typedef enum shiftnd_dtype {
  */
 #define SHIFTND_FRAMES 0x400
 
+/*
+ * The temporal shift under a PER-CLIP table (a shift that a small net predicts from the clip itself: TIN's OffsetNet, arXiv
+ * 2001.06499; per-clip temporal jitter).  OR-ed onto a float dtype TOGETHER WITH SHIFTND_SHIFT_DIM0 (and, for F16 / BF16, optionally
+ * SHIFTND_WEIGHTS_F32): `weights` and `grad_w` are contiguous [N, C] arrays, ONE entry per clip and channel, N = sizes[0].  Clip n is
+ * the SHIFTND_SHIFT_DIM0 problem {1, C, S0, S1, S2} on its own frames under row n of the table: out and grad_x carry the bits of
+ * that call, and grad_w[n] is its grad_w -- the fp64 sum of clip n's products in a fixed order, narrowed once to the weights' type,
+ * deterministic.  (0x800 is not assigned: it stays an unknown dtype bit.)
+ *   Honoured by shiftnd_forward (both values of p->active), shiftnd_backward (full form) and shiftnd_backward_workspace_bytes,
+ *   which answers the bytes it answers without the bit: the partial records are re-indexed, not multiplied.
+ *   Accepted: the geometry, layout and limits of SHIFTND_SHIFT_DIM0 on segment-major tensors (memory order N, S0, C, S1, S2), and
+ *   N * C below 2^31.  The same kernels serve the call -- the table's row stride is a run-time field of theirs -- so
+ *   shiftnd_last_kernel() reports tshift_forward[_ragged] / tshift_backward[_ragged] and shiftnd_last_path() SHIFTND_PATH_PLANE.
+ *   An empty problem: SHIFTND_PATH_EMPTY, with the N * C entries of grad_w zeroed.
+ *   Errors, before anything is launched: a quantized dtype, the bit on shiftnd_forward_quantized or on the pooled entry points, and
+ *   the bit without SHIFTND_SHIFT_DIM0 (an unknown dtype bit): SHIFTND_ERR_UNSUPPORTED_DTYPE; together with SHIFTND_FRAMES, out == x
+ *   (the in-place form), channels-last tensors, the x == NULL && grad_w == NULL form of shiftnd_backward, N * C of 2^31 or more,
+ *   and whatever SHIFTND_SHIFT_DIM0 refuses: SHIFTND_ERR_INVALID_ARGUMENT.  The workspace query answers 0 for a refused problem.
+ * Without the bit nothing changes.
+ */
+#define SHIFTND_PER_CLIP 0x1000
+
 typedef enum shiftnd_status {
     SHIFTND_OK = 0,
     SHIFTND_ERR_INVALID_ARGUMENT = -1,
@@ -197,7 +218,7 @@ typedef enum shiftnd_path {
 /* Problem geometry shared by the entry points. */
 typedef struct shiftnd_problem {
     int32_t ndim;          /* spatial dims: 1, 2 or 3 */
-    int32_t dtype;         /* shiftnd_dtype of input/output (and of float weights), optionally | SHIFTND_WEIGHTS_F32 | SHIFTND_SHIFT_DIM0 | SHIFTND_FRAMES */
+    int32_t dtype;         /* shiftnd_dtype of input/output (and of float weights), optionally | SHIFTND_WEIGHTS_F32 | SHIFTND_SHIFT_DIM0 | SHIFTND_FRAMES | SHIFTND_PER_CLIP */
     int32_t padding_mode;  /* 0..4 */
     int32_t active;        /* 0: sparse shift (rounded integer shift); 1: active (interpolated) */
     int64_t sizes[5];      /* input N, C, H, W, D */
