@@ -143,9 +143,8 @@ struct DefaultKnobs {
     DefaultKnobs &operator=(const DefaultKnobs &) = delete;
 };
 
-bool empty_problem(const Geometry &g) {
-    return g.N == 0 || g.C == 0 || g.S[0] * g.S[1] * g.S[2] == 0 || g.O[0] * g.O[1] * g.O[2] == 0;
-}
+bool empty_geometry(const Geometry &g) { return g.N == 0 || g.C == 0 || g.S[0] * g.S[1] * g.S[2] == 0; }
+bool empty_problem(const Geometry &g) { return empty_geometry(g) || g.O[0] * g.O[1] * g.O[2] == 0; }   // ... or its window is
 
 int finish(int rc) {
     if (rc != SHIFTND_OK) return rc;
@@ -273,80 +272,30 @@ int forward_common(const shiftnd_problem *p, const void *x, const int64_t *xs, c
 // is served by the kernels of its layout or refused before anything is launched.
 // SHIFTND_PER_CLIP beside the flag: `weights` / `grad_w` are [N, C] arrays, one row per clip -- the tshift kernels on segment-major
 // tensors alone, out of place (tshift_forward_call / tshift_backward_call); every other form under the flag refuses the bit.
-// -> the problem without the flag bits in `q`, the weights' type in `wkind`, SHIFTND_PER_CLIP's presence in `per_clip`
-int tshift_problem(const shiftnd_problem *p, shiftnd_problem &q, int &wkind, bool &per_clip) {
+// SHIFTND_FRAMES beside the flag: the same problem on dense channels-last tensors, all of them (shiftnd_frames_learn.hip; the sparse
+// forward is frames_forward).  The explicit bit takes every such call to the frame kernels -- also tensors that the segment-major
+// layout describes as well -- or refuses it.
+// -> the problem without the flag bits in `q`, the weights' type in `wkind`, the presence of SHIFTND_PER_CLIP and SHIFTND_FRAMES
+int tshift_problem(const shiftnd_problem *p, shiftnd_problem &q, int &wkind, bool &per_clip, bool &frames) {
     shiftnd_problem r = *p;
-    r.dtype = p->dtype & ~(SHIFTND_SHIFT_DIM0 | SHIFTND_PER_CLIP);
+    r.dtype = p->dtype & ~(SHIFTND_SHIFT_DIM0 | SHIFTND_PER_CLIP | SHIFTND_FRAMES);
     per_clip = (p->dtype & SHIFTND_PER_CLIP) != 0;
+    frames = (p->dtype & SHIFTND_FRAMES) != 0;
     if (split_dtype(&r, q, wkind) != SHIFTND_OK || !is_float_dtype(q.dtype)) return SHIFTND_ERR_UNSUPPORTED_DTYPE;
-    return SHIFTND_OK;
+    return frames && per_clip ? SHIFTND_ERR_INVALID_ARGUMENT : SHIFTND_OK;   // (the frame kernels take a [C] table alone)
 }
 
 // the bound SHIFTND_PER_CLIP adds to tshift_geometry_ok's: the [N, C] table is indexed in 32 bits.  (Today N * S0 * C < 2^31 implies
 // it; it is stated on its own because the kernels' table index and the reduction's entry count rest on it.)
 bool per_clip_table_ok(const Geometry &g) { return g.N * g.C < (1LL << 31); }   // (both factors are below 2^31 here: no overflow)
 
-// ---- SHIFTND_SHIFT_DIM0 | SHIFTND_FRAMES: the same problem on dense channels-last tensors, all of them (shiftnd_frames_learn.hip; the
-// sparse forward is frames_forward).  The explicit bit takes every such call to the frame kernels -- also tensors that the
-// segment-major layout describes as well -- or refuses it.
-// -> the problem without the flag bits in `q`, the weights' type in `wkind`
-int frames_learn_problem(const shiftnd_problem *p, shiftnd_problem &q, int &wkind) {
-    shiftnd_problem r = *p;
-    r.dtype = p->dtype & ~SHIFTND_FRAMES;
-    bool per_clip;
-    const int rc = tshift_problem(&r, q, wkind, per_clip);
-    if (rc != SHIFTND_OK) return rc;
-    return per_clip ? SHIFTND_ERR_INVALID_ARGUMENT : SHIFTND_OK;   // (the frame kernels take a [C] table alone)
+// the sizes a backward under the flag is served at, and its workspace: the two points where the workspace query and the backward
+// call tell the layouts apart together
+bool tshift_backward_sizes_ok(const Geometry &g, int dtype, bool per_clip, bool frames) {
+    return frames ? frames_learn_geometry_ok(g, dtype) : tshift_geometry_ok(g, dtype) && (!per_clip || per_clip_table_ok(g));
 }
-
-bool empty_geometry(const Geometry &g) { return g.N == 0 || g.C == 0 || g.S[0] * g.S[1] * g.S[2] == 0; }
-
-int frames_learn_forward_call(const shiftnd_problem *p, const void *x, const int64_t *xs, const void *w, void *out, const int64_t *os,
-                              void *stream) {
-    shiftnd_problem q;
-    int wkind;
-    int rc = frames_learn_problem(p, q, wkind);
-    if (rc != SHIFTND_OK) return rc;
-    Geometry g;
-    rc = build_geometry(&q, xs, os, nullptr, g);
-    if (rc != SHIFTND_OK) return rc;
-    if (!frames_learn_geometry_ok(g, q.dtype)) return SHIFTND_ERR_INVALID_ARGUMENT;
-    if (empty_geometry(g)) {
-        g_last_path = SHIFTND_PATH_EMPTY;
-        return SHIFTND_OK;
-    }
-    if (!x || !w || !out) return SHIFTND_ERR_INVALID_ARGUMENT;
-    if (!frames_tensor_ok(g, q.dtype, x, g.xs) || !frames_tensor_ok(g, q.dtype, out, g.os)) return SHIFTND_ERR_INVALID_ARGUMENT;
-    g_last_path = SHIFTND_PATH_CL;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (!g.active) return finish(frames_forward(g, q.dtype, x, w, wkind, 0, 0ull, out, st));
-    return finish(frames_active_forward(g, q.dtype, x, w, wkind, out, st));
-}
-
-int frames_learn_backward_call(const shiftnd_problem *p, const void *go, const int64_t *gos, const void *x, const int64_t *xs,
-                               const void *w, void *gx, const int64_t *gxs, void *gw, void *workspace, size_t workspace_bytes,
-                               void *stream) {
-    shiftnd_problem q;
-    int wkind;
-    int rc = frames_learn_problem(p, q, wkind);
-    if (rc != SHIFTND_OK) return rc;
-    if (!x || !xs || !gw) return SHIFTND_ERR_INVALID_ARGUMENT;   // (the x == NULL form does not exist under the flag)
-    Geometry g;
-    rc = build_geometry(&q, xs, gos, gxs, g);
-    if (rc != SHIFTND_OK) return rc;
-    if (!frames_learn_geometry_ok(g, q.dtype)) return SHIFTND_ERR_INVALID_ARGUMENT;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (empty_geometry(g)) {
-        g_last_path = SHIFTND_PATH_EMPTY;
-        if (g.C > 0 && hipMemsetAsync(gw, 0, static_cast<size_t>(g.C) * dtype_size(wkind), st) != hipSuccess) return SHIFTND_ERR_LAUNCH_FAILED;
-        return SHIFTND_OK;
-    }
-    if (!go || !w || !gx || !workspace) return SHIFTND_ERR_INVALID_ARGUMENT;
-    if (!frames_tensor_ok(g, q.dtype, go, g.os) || !frames_tensor_ok(g, q.dtype, x, g.xs) || !frames_tensor_ok(g, q.dtype, gx, g.gs))
-        return SHIFTND_ERR_INVALID_ARGUMENT;
-    if (frames_backward_workspace(g, q.dtype) > workspace_bytes) return SHIFTND_ERR_WORKSPACE_TOO_SMALL;
-    g_last_path = SHIFTND_PATH_CL;
-    return finish(frames_backward(g, q.dtype, go, x, w, wkind, gx, gw, workspace, st));
+size_t tshift_backward_workspace_for(const Geometry &g, int dtype, bool frames) {
+    return frames ? frames_backward_workspace(g, dtype) : tshift_backward_workspace(g, dtype);
 }
 
 // ---- SHIFTND_SHIFT_DIM0 with out == x: the fixed temporal shift IN PLACE (shiftnd_inplace.hip).  `q`: the problem with its plain
@@ -376,28 +325,27 @@ int tshift_forward_call(const shiftnd_problem *p, const void *x, const int64_t *
     if (out && out == x) {   // in place: its own kernel, or refused (SHIFTND_FRAMES asks for kernels that have no such form)
         shiftnd_problem q;
         int wkind;
-        bool per_clip;
+        bool per_clip, frames;
         if (p->dtype & SHIFTND_FRAMES) return SHIFTND_ERR_INVALID_ARGUMENT;
-        const int rc = tshift_problem(p, q, wkind, per_clip);
+        const int rc = tshift_problem(p, q, wkind, per_clip, frames);
         if (rc == SHIFTND_OK && per_clip) return SHIFTND_ERR_INVALID_ARGUMENT;   // (the in-place kernel takes a [C] table alone)
         return rc != SHIFTND_OK ? rc : inplace_call(q, out, xs, os, w, wkind, 0, 0ull, stream);
     }
-    if (p->dtype & SHIFTND_FRAMES) return frames_learn_forward_call(p, x, xs, w, out, os, stream);
     shiftnd_problem q;
     int wkind;
-    bool per_clip;
-    int rc = tshift_problem(p, q, wkind, per_clip);
+    bool per_clip, frames;
+    int rc = tshift_problem(p, q, wkind, per_clip, frames);
     if (rc != SHIFTND_OK) return rc;
     Geometry g;
     rc = build_geometry(&q, xs, os, nullptr, g);
     if (rc != SHIFTND_OK) return rc;
-    // two layouts are served: segment-major (the tshift kernels, sparse and interpolating) and, for the sparse shift, channels-last
-    // (shiftnd_frames.hip).  A tensor both describe (planes or channels of size 1) stays with the tshift kernels.  A per-clip table:
-    // the tshift kernels alone
-    const bool segment_sizes = tshift_geometry_ok(g, q.dtype) && (!per_clip || per_clip_table_ok(g));
-    const bool frames_sizes = !per_clip && frames_geometry_ok(g, q.dtype);
+    // without SHIFTND_FRAMES two layouts are served: segment-major (the tshift kernels, sparse and interpolating) and, for the sparse
+    // shift, channels-last (shiftnd_frames.hip: frames_geometry_ok refuses `active`).  A tensor both describe (planes or channels of
+    // size 1) stays with the tshift kernels.  A per-clip table: the tshift kernels alone.  With the bit: the frame kernels alone
+    const bool segment_sizes = !frames && tshift_geometry_ok(g, q.dtype) && (!per_clip || per_clip_table_ok(g));
+    const bool frames_sizes = frames ? frames_learn_geometry_ok(g, q.dtype) : !per_clip && frames_geometry_ok(g, q.dtype);
     if (!segment_sizes && !frames_sizes) return SHIFTND_ERR_INVALID_ARGUMENT;
-    if (empty_problem(g)) {
+    if (empty_geometry(g)) {   // (empty_problem's answer: every *_geometry_ok above refuses a cut window)
         g_last_path = SHIFTND_PATH_EMPTY;
         return SHIFTND_OK;
     }
@@ -408,6 +356,7 @@ int tshift_forward_call(const shiftnd_problem *p, const void *x, const int64_t *
     }
     if (frames_sizes && frames_tensor_ok(g, q.dtype, x, g.xs) && frames_tensor_ok(g, q.dtype, out, g.os)) {
         g_last_path = SHIFTND_PATH_CL;
+        if (g.active) return finish(frames_active_forward(g, q.dtype, x, w, wkind, out, static_cast<hipStream_t>(stream)));   // (SHIFTND_FRAMES only)
         return finish(frames_forward(g, q.dtype, x, w, wkind, 0, 0ull, out, static_cast<hipStream_t>(stream)));
     }
     return SHIFTND_ERR_INVALID_ARGUMENT;
@@ -433,31 +382,34 @@ int frames_quantized_call(const shiftnd_problem *p, const void *x, const int64_t
     return finish(frames_forward(g, q.dtype, x, wq, wq_dtype, wzp, fill, out, static_cast<hipStream_t>(stream)));
 }
 
+// the backward under the flag, both layouts: `frames` (SHIFTND_FRAMES) picks the sizes, the tensor check, the workspace and the kernels
 int tshift_backward_call(const shiftnd_problem *p, const void *go, const int64_t *gos, const void *x, const int64_t *xs, const void *w,
                          void *gx, const int64_t *gxs, void *gw, void *workspace, size_t workspace_bytes, void *stream) {
-    if (p->dtype & SHIFTND_FRAMES) return frames_learn_backward_call(p, go, gos, x, xs, w, gx, gxs, gw, workspace, workspace_bytes, stream);
     shiftnd_problem q;
     int wkind;
-    bool per_clip;
-    int rc = tshift_problem(p, q, wkind, per_clip);
+    bool per_clip, frames;
+    int rc = tshift_problem(p, q, wkind, per_clip, frames);
     if (rc != SHIFTND_OK) return rc;
     if (!x || !xs || !gw) return SHIFTND_ERR_INVALID_ARGUMENT;   // (the x == NULL form does not exist under the flag)
     Geometry g;
     rc = build_geometry(&q, xs, gos, gxs, g);
     if (rc != SHIFTND_OK) return rc;
-    if (!tshift_geometry_ok(g, q.dtype) || (per_clip && !per_clip_table_ok(g))) return SHIFTND_ERR_INVALID_ARGUMENT;
+    if (!tshift_backward_sizes_ok(g, q.dtype, per_clip, frames)) return SHIFTND_ERR_INVALID_ARGUMENT;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (g.N == 0 || g.C == 0 || g.S[0] * g.S[1] * g.S[2] == 0) {
+    if (empty_geometry(g)) {
         g_last_path = SHIFTND_PATH_EMPTY;
         const size_t entries = static_cast<size_t>(per_clip ? g.N * g.C : g.C);
         if (entries > 0 && hipMemsetAsync(gw, 0, entries * dtype_size(wkind), st) != hipSuccess) return SHIFTND_ERR_LAUNCH_FAILED;
         return SHIFTND_OK;
     }
     if (!go || !w || !gx || !workspace) return SHIFTND_ERR_INVALID_ARGUMENT;
-    if (!tshift_tensor_ok(g, q.dtype, go, g.os) || !tshift_tensor_ok(g, q.dtype, x, g.xs) || !tshift_tensor_ok(g, q.dtype, gx, g.gs))
-        return SHIFTND_ERR_INVALID_ARGUMENT;
-    if (tshift_backward_workspace(g, q.dtype) > workspace_bytes) return SHIFTND_ERR_WORKSPACE_TOO_SMALL;
-    g_last_path = SHIFTND_PATH_PLANE;
+    const auto tensor_ok = [&](const void *t, const int64_t *strides) {
+        return frames ? frames_tensor_ok(g, q.dtype, t, strides) : tshift_tensor_ok(g, q.dtype, t, strides);
+    };
+    if (!tensor_ok(go, g.os) || !tensor_ok(x, g.xs) || !tensor_ok(gx, g.gs)) return SHIFTND_ERR_INVALID_ARGUMENT;
+    if (tshift_backward_workspace_for(g, q.dtype, frames) > workspace_bytes) return SHIFTND_ERR_WORKSPACE_TOO_SMALL;
+    g_last_path = frames ? SHIFTND_PATH_CL : SHIFTND_PATH_PLANE;
+    if (frames) return finish(frames_backward(g, q.dtype, go, x, w, wkind, gx, gw, workspace, st));
     return finish(tshift_backward(g, q.dtype, go, x, w, wkind, per_clip, gx, gw, workspace, st));
 }
 
@@ -565,7 +517,7 @@ int shiftnd_backward_serves_channels_last(const shiftnd_problem *p, const void *
     p = &q;
     Geometry g;
     if (build_geometry(p, x_strides, grad_out_strides, grad_x_strides, g) != SHIFTND_OK) return 0;
-    if (g.N == 0 || g.C == 0 || g.S[0] * g.S[1] * g.S[2] == 0) return 0;
+    if (empty_geometry(g)) return 0;
     if (g.nd == 3) {
         // NDHWC (round 5): shiftnd_cl_tiled3.hip serves such tensors as they lie (what a C-ABI caller gets: 1.2 - 1.5 ms on N8 C128
         // 16x112x112 fp32 where the channel-fastest kernels took 21 - 36 ms), but the op's route -- shiftnd_transpose of the saved
@@ -632,20 +584,13 @@ size_t shiftnd_backward_workspace_bytes(const shiftnd_problem *p) {
     // every entry point refuses the bit alone, so the answer is 0.  (The path below would not give it: it looks at the geometry and sizes
     // the families' plans whatever unknown bits the dtype carries -- 0x800 on F32 answers 512 bytes there, an answer a test pins)
     if ((p->dtype & SHIFTND_PER_CLIP) && !(p->dtype & SHIFTND_SHIFT_DIM0)) return 0;
-    if (p->dtype & SHIFTND_SHIFT_DIM0) {   // the walk's plan alone: no other family runs under the flag, no knob shapes it
+    if (p->dtype & SHIFTND_SHIFT_DIM0) {   // the walk's plan alone (SHIFTND_FRAMES: the channels-last walk's): no other family runs under the flag, no knob shapes it
         const int64_t unit[5] = {0, 0, 0, 0, 0};
         Geometry g;
-        if (p->dtype & SHIFTND_FRAMES) {   // ... or, with SHIFTND_FRAMES, the channels-last walk's
-            if (frames_learn_problem(p, q, wkind) != SHIFTND_OK || build_geometry(&q, unit, unit, unit, g) != SHIFTND_OK) return 0;
-            if (!frames_learn_geometry_ok(g, q.dtype)) return 0;
-            if (g.N == 0 || g.C == 0 || g.S[0] * g.S[1] * g.S[2] == 0) return sizeof(double);
-            return frames_backward_workspace(g, q.dtype);
-        }
-        bool per_clip;   // (a per-clip table re-indexes the same records: the same bytes with and without SHIFTND_PER_CLIP)
-        if (tshift_problem(p, q, wkind, per_clip) != SHIFTND_OK || build_geometry(&q, unit, unit, unit, g) != SHIFTND_OK) return 0;
-        if (!tshift_geometry_ok(g, q.dtype) || (per_clip && !per_clip_table_ok(g))) return 0;
-        if (g.N == 0 || g.C == 0 || g.S[0] * g.S[1] * g.S[2] == 0) return sizeof(double);
-        return tshift_backward_workspace(g, q.dtype);
+        bool per_clip, frames;   // (a per-clip table re-indexes the same records: the same bytes with and without SHIFTND_PER_CLIP)
+        if (tshift_problem(p, q, wkind, per_clip, frames) != SHIFTND_OK || build_geometry(&q, unit, unit, unit, g) != SHIFTND_OK) return 0;
+        if (!tshift_backward_sizes_ok(g, q.dtype, per_clip, frames)) return 0;
+        return empty_geometry(g) ? sizeof(double) : tshift_backward_workspace_for(g, q.dtype, frames);
     }
     if (split_dtype(p, q, wkind) != SHIFTND_OK) return 0;
     p = &q;   // (the records are fp64 whatever the weights are: the same bytes with and without SHIFTND_WEIGHTS_F32)
@@ -653,7 +598,7 @@ size_t shiftnd_backward_workspace_bytes(const shiftnd_problem *p) {
     const int64_t unit[5] = {0, 0, 0, 0, 0};
     Geometry g;
     if (build_geometry(p, unit, unit, unit, g) != SHIFTND_OK) return 0;
-    if (g.N == 0 || g.C == 0 || g.S[0] * g.S[1] * g.S[2] == 0) return sizeof(double);
+    if (empty_geometry(g)) return sizeof(double);
     size_t m = backward_workspace_now(g, p->dtype);
     if (knobs_touched()) {   // ... and under the default knobs: what a run on any thread can fall back to
         DefaultKnobs scope;
@@ -702,7 +647,7 @@ static int backward_planned(const shiftnd_problem *p, const void *grad_out, cons
     const int rc = build_geometry(p, x_strides ? x_strides : grad_x_strides, grad_out_strides, grad_x_strides, g);
     if (rc != SHIFTND_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (g.N == 0 || g.C == 0 || g.S[0] * g.S[1] * g.S[2] == 0) {
+    if (empty_geometry(g)) {
         // nothing to differentiate; grad_w (if any channels) is all zeros (zeros_like, shifts_cpu.cpp:247)
         g_last_path = SHIFTND_PATH_EMPTY;
         if (g.C > 0 && grad_w)
@@ -842,7 +787,7 @@ size_t shiftnd_backward_pooled_workspace_bytes(const shiftnd_problem *p, const i
     p = &q;   // (as shiftnd_backward_workspace_bytes: the same bytes with and without SHIFTND_WEIGHTS_F32)
     Geometry g;
     if (pooled_geometry(p, pool, g) != SHIFTND_OK) return 0;
-    if (g.N == 0 || g.C == 0 || g.S[0] * g.S[1] * g.S[2] == 0) return sizeof(double);
+    if (empty_geometry(g)) return sizeof(double);
     size_t m = plane_backward_workspace(g, p->dtype);
     if (knobs_touched()) {   // (as shiftnd_backward_workspace_bytes)
         DefaultKnobs scope;
@@ -955,7 +900,7 @@ static int backward_pooled_planned(const shiftnd_problem *p, const int32_t *pool
     hipStream_t st = static_cast<hipStream_t>(stream);
     const bool input_only = !x && !grad_w;
     if (input_only && (p->active || wkind != p->dtype)) return SHIFTND_ERR_INVALID_ARGUMENT;   // (also for an empty problem: the form does not exist)
-    if (g.N == 0 || g.C == 0 || g.S[0] * g.S[1] * g.S[2] == 0) {
+    if (empty_geometry(g)) {
         g_last_path = SHIFTND_PATH_EMPTY;
         if (g.C > 0 && grad_w)
             if (hipMemsetAsync(grad_w, 0, static_cast<size_t>(g.C) * g.nd * dtype_size(wkind), st) != hipSuccess)

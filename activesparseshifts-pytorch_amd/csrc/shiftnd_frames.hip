@@ -28,8 +28,7 @@
 // The input gradient of the op is this kernel on the gradient under the negated table.
 #include <algorithm>
 
-#include "shiftnd_common.hpp"
-#include "shiftnd_launch.hpp"
+#include "shiftnd_temporal.hpp"
 
 namespace shiftnd {
 namespace {
@@ -53,13 +52,6 @@ struct FramesParams {
     uint32_t fill;                        // what a filled element holds, as a dword pattern (0 for floats)
 };
 
-template <int UL> struct piece_of;
-template <> struct piece_of<4> { typedef shiftnd_u4 type; };
-template <> struct piece_of<3> { typedef uint32_t type __attribute__((ext_vector_type(2))); };
-template <> struct piece_of<2> { typedef uint32_t type; };
-template <> struct piece_of<1> { typedef uint16_t type; };
-template <> struct piece_of<0> { typedef uint8_t type; };
-
 // a piece of 1 << UL bytes in the low bytes of four dwords
 template <int UL> __device__ __forceinline__ shiftnd_u4 load_piece(const char *p) {
     typedef typename piece_of<UL>::type piece_t;
@@ -80,6 +72,7 @@ template <int UL> __device__ __forceinline__ void store_piece(char *p, shiftnd_u
 }
 
 // do table entries [e0, e0 + n) (1 <= n <= 16) hold the same bits?  Unconditional loads inside the table, issued together
+// (shiftnd_inplace.hip has its own raw_equal on purpose: a compile-time count and exactly that many loads, against 15 clamped ones here)
 template <typename R> __device__ __forceinline__ bool raw_equal(const void *w, int64_t e0, int n) {
     const R *p = static_cast<const R *>(w) + e0;
     const R first = p[0];
@@ -102,9 +95,6 @@ __device__ __forceinline__ int source_frame(const FramesParams &q, const void *w
     const int T = static_cast<int>(q.T);
     return fold_index(t - canon_shift(gather_shift(w, q.wkind, q.wzp, c), T, q.pad, q.d_per), T, q.pad);
 }
-
-// bytes [0, n) of a dword (n clamped to 0..4)
-__device__ __forceinline__ uint32_t low_bytes(int n) { return n <= 0 ? 0u : (n >= 4 ? ~0u : (1u << (8 * n)) - 1u); }
 
 template <int UL>
 __device__ __forceinline__ void frames_body(const FramesParams &q, const char *__restrict__ x, const void *__restrict__ w,
@@ -198,14 +188,6 @@ __global__ __launch_bounds__(kThreads) void frames_forward(FramesParams q, const
     }
 }
 
-int64_t frame_pixels(const Geometry &g) { return (g.nd == 3 ? g.S[1] : 1) * g.S[2]; }
-
-// the widest power-of-two piece, at most 16 bytes, that divides the row's bytes and both bases
-int piece_log2(int64_t row_bytes, const void *x, const void *out) {
-    const uintptr_t all = static_cast<uintptr_t>(row_bytes) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out) | 16u;
-    return __builtin_ctzll(all);
-}
-
 }  // namespace
 
 // The sizes the kernel's index arithmetic needs (include/shiftnd_hip.h states them): 32-bit frame and workgroup indices through
@@ -240,14 +222,13 @@ int frames_forward(const Geometry &g, int dtype, const void *x, const void *w, i
     q.pad = g.pad;
     q.wkind = wkind;
     q.wzp = wzp;
-    q.es_log2 = es == 8 ? 3 : (es == 4 ? 2 : (es == 2 ? 1 : 0));
-    // the fill as a dword pattern: a byte four times, the dword itself (floats: fill_bits == 0)
-    q.fill = es == 1 ? static_cast<uint32_t>(fill_bits & 0xff) * 0x01010101u : static_cast<uint32_t>(fill_bits);
+    q.es_log2 = es_log2(es);
+    q.fill = fill_dword(es, fill_bits);
     q.T = static_cast<uint32_t>(g.S[3 - g.nd]);
     q.M = frame_pixels(g);
     q.R = g.C * es;
     q.frame_bytes = q.M * q.R;
-    q.unit_log2 = piece_log2(q.R, x, out);
+    q.unit_log2 = __builtin_ctz(piece_bytes(q.R, {x, out}));
     q.P = static_cast<uint32_t>(q.R >> q.unit_log2);
     q.span = q.P < static_cast<uint32_t>(kThreads) ? q.P : static_cast<uint32_t>(kThreads);
     q.rps = static_cast<uint32_t>(kThreads) / q.span;

@@ -27,10 +27,7 @@
 // ONE kernel per pass: the element type and the piece (`elems` elements, 16 bytes down to one element) are launch-uniform
 // run-time switches over instantiations of one body; shiftnd_last_kernel() names the form, *_ragged for pieces under 16 bytes.
 // Every access is naturally aligned and inside the tensors' bytes; the weights are read at entries [0, C) only.  No scratch.
-#include <initializer_list>
-
-#include "shiftnd_common.hpp"
-#include "shiftnd_launch.hpp"
+#include "shiftnd_temporal.hpp"
 
 namespace shiftnd {
 namespace {
@@ -48,29 +45,6 @@ struct FramesLearnParams {
     FastDiv d_chunks, d_T, d_span, d_per;   // d_per: by map_period(T, pad)
     int64_t M, R, frame_bytes;              // pixels per frame, bytes per row, bytes per frame
 };
-
-template <typename T, int E> struct Unit { typename T::S e[E]; };
-
-template <typename T, int E, bool NT> __device__ __forceinline__ Unit<T, E> load_unit(const char *p) {
-    constexpr int V = sizeof(typename T::S) * E;
-    typedef typename vec_of<V>::type vec_t;
-    const vec_t v = NT ? __builtin_nontemporal_load(reinterpret_cast<const vec_t *>(p)) : *reinterpret_cast<const vec_t *>(p);
-    Unit<T, E> u;
-    __builtin_memcpy(u.e, &v, V);
-    return u;
-}
-template <typename T, int E> __device__ __forceinline__ Unit<T, E> zero_unit() {
-    Unit<T, E> u;
-    __builtin_memset(u.e, 0, sizeof(u.e));
-    return u;
-}
-template <typename T, int E> __device__ __forceinline__ void store_unit(char *p, const Unit<T, E> &u) {
-    constexpr int V = sizeof(typename T::S) * E;
-    typedef typename vec_of<V>::type vec_t;
-    vec_t v;
-    __builtin_memcpy(&v, u.e, V);
-    __builtin_nontemporal_store(v, reinterpret_cast<vec_t *>(p));
-}
 
 // the piece at `at` (its byte offset in frame 0 of the clip) whose element e comes from frame f[e], or is the fill (f[e] < 0):
 // one piece load where the elements agree, element-sized loads otherwise
@@ -103,9 +77,6 @@ __device__ __forceinline__ Unit<T, E> blend_units(const Unit<T, E> &a, const Uni
     }
     return r;
 }
-
-// source frame of coordinate p in [0, T] under the canonical shift cs (a size-1 dim ignores its shift), or -1 (fill)
-__device__ __forceinline__ int source_frame(int p, int cs, int T, int pad) { return T == 1 ? 0 : fold_index(p - cs, T, pad); }
 
 template <typename T, int E>
 __device__ __forceinline__ void forward_body(const FramesLearnParams &q, const char *__restrict__ x, const void *__restrict__ w,
@@ -254,15 +225,6 @@ __device__ __forceinline__ void backward_body(const FramesLearnParams &q, const 
     }
 }
 
-template <int E> struct UnitElems { static constexpr int value = E; };
-template <int E, typename F> __device__ __forceinline__ void with_unit(int elems, F &&f) {
-    if constexpr (E == 1) {
-        f(UnitElems<1>());
-    } else {
-        if (elems == E) f(UnitElems<E>());
-        else with_unit<E / 2>(elems, f);
-    }
-}
 // the element type and the piece: launch-uniform, scalar branches
 template <typename F> __device__ __forceinline__ void with_type_and_unit(int dtype, int elems, F &&f) {
     switch (dtype) {
@@ -284,16 +246,6 @@ __global__ __launch_bounds__(kThreads) void frames_backward(FramesLearnParams q,
     __shared__ double red[kThreads * kMaxElems];
     with_type_and_unit(q.dtype, q.elems,
                        [&](auto ty, auto e) { backward_body<decltype(ty), decltype(e)::value>(q, go, x, w, gx, partials, red); });
-}
-
-int64_t frame_pixels(const Geometry &g) { return (g.nd == 3 ? g.S[1] : 1) * g.S[2]; }
-
-// bytes of the piece: the largest power of two up to 16 that divides the row's bytes and every base (at least one element: rows
-// are whole elements and bases are element-aligned)
-int piece_bytes(int64_t row_bytes, std::initializer_list<const void *> bases) {
-    uintptr_t bits = static_cast<uintptr_t>(row_bytes) | 16;
-    for (const void *p : bases) bits |= reinterpret_cast<uintptr_t>(p);
-    return static_cast<int>(bits & (~bits + 1));
 }
 
 FramesLearnParams make_params(const Geometry &g, int dtype, int wkind, int unit) {

@@ -28,8 +28,7 @@
 // slots >= T predicated off; the host route refuses T > 16.
 // shiftnd_last_kernel() names the form: frames_inplace (16-byte pieces), frames_inplace_ragged (8-, 4-, 2- or 1-byte pieces).
 // Every access is naturally aligned and lies inside the bytes the tensor occupies; the table is read at entries [0, C) only.
-#include "shiftnd_common.hpp"
-#include "shiftnd_launch.hpp"
+#include "shiftnd_temporal.hpp"
 
 namespace shiftnd {
 namespace {
@@ -46,13 +45,6 @@ struct InplaceParams {
     int64_t wzp;                          // zero point of an integer table
     uint32_t fill;                        // what a filled element holds, as a dword pattern (0 for floats)
 };
-
-template <int UL> struct piece_of;
-template <> struct piece_of<4> { typedef shiftnd_u4 type; };
-template <> struct piece_of<3> { typedef uint32_t type __attribute__((ext_vector_type(2))); };
-template <> struct piece_of<2> { typedef uint32_t type; };
-template <> struct piece_of<1> { typedef uint16_t type; };
-template <> struct piece_of<0> { typedef uint8_t type; };
 
 // the bytes [p, p + (1 << UL)) of every frame of the clip under the canonical shift `cs`: gather, then store
 template <int UL> __device__ __forceinline__ void shift_line(const InplaceParams &q, char *p, int cs) {
@@ -78,6 +70,7 @@ template <int UL> __device__ __forceinline__ void shift_line(const InplaceParams
 }
 
 // do table entries [e0, e0 + N) hold the same bits?  N is a compile-time count: exactly N loads inside the table, issued together
+// (shiftnd_frames.hip has its own raw_equal on purpose: a run-time count under 15 clamped loads, against exactly N loads here)
 template <typename R, int N> __device__ __forceinline__ bool raw_equal(const void *w, int64_t e0) {
     const R *p = static_cast<const R *>(w) + e0;
     const R first = p[0];
@@ -167,20 +160,6 @@ __global__ __launch_bounds__(kThreads) void frames_inplace(InplaceParams q, char
     }
 }
 
-int64_t frame_pixels(const Geometry &g) { return (g.nd == 3 ? g.S[1] : 1) * g.S[2]; }
-
-// dense strides of memory order N, S0, C, S1, S2 (a dim of size 1 has no stride to check) at an element-aligned base
-bool segment_major_dense(const Geometry &g, int dtype, const void *p, const int64_t *st) {
-    const int lead = 3 - g.nd;
-    const int64_t A = g.nd == 3 ? g.S[1] : 1, B = g.S[2], T = g.S[lead];
-    if (!aligned_to(p, dtype_size(dtype))) return false;
-    if (B > 1 && st[4] != 1) return false;
-    if (A > 1 && st[3] != B) return false;
-    if (g.C > 1 && st[1] != A * B) return false;
-    if (T > 1 && st[2 + lead] != g.C * A * B) return false;
-    return g.N == 1 || st[0] == T * g.C * A * B;
-}
-
 }  // namespace
 
 // The sizes the kernel serves (include/shiftnd_hip.h states them): those of frames_geometry_ok, at most kMaxFrames frames per clip,
@@ -195,7 +174,7 @@ bool inplace_geometry_ok(const Geometry &g, int dtype) {
 
 // 1: dense segment-major, 2: dense channels-last, 0: neither.  A tensor both describe (planes or channels of size 1) is segment-major
 int inplace_layout(const Geometry &g, int dtype, const void *p, const int64_t *strides) {
-    if (segment_major_dense(g, dtype, p, strides)) return 1;
+    if (tshift_tensor_ok(g, dtype, p, strides)) return 1;
     return frames_tensor_ok(g, dtype, p, strides) ? 2 : 0;
 }
 
@@ -208,13 +187,11 @@ int inplace_forward(const Geometry &g, int dtype, int layout, void *x, const voi
     q.wkind = wkind;
     q.wzp = wzp;
     q.cl = layout == 2 ? 1 : 0;
-    q.es_log2 = es == 8 ? 3 : (es == 4 ? 2 : (es == 2 ? 1 : 0));
-    // the fill as a dword pattern: a byte four times, the dword itself (floats: fill_bits == 0)
-    q.fill = es == 1 ? static_cast<uint32_t>(fill_bits & 0xff) * 0x01010101u : static_cast<uint32_t>(fill_bits);
+    q.es_log2 = es_log2(es);
+    q.fill = fill_dword(es, fill_bits);
     q.T = static_cast<uint32_t>(g.S[3 - g.nd]);
     q.frame_bytes = g.C * M * es;
-    // the widest power-of-two piece, at most 16 bytes, that divides the run's bytes and the base (the rule of shiftnd_frames.hip)
-    q.unit_log2 = __builtin_ctzll(static_cast<uintptr_t>(run_bytes) | reinterpret_cast<uintptr_t>(x) | 16u);
+    q.unit_log2 = __builtin_ctz(piece_bytes(run_bytes, {x}));
     q.ppf = q.frame_bytes >> q.unit_log2;
     q.ppr = static_cast<uint32_t>(run_bytes >> q.unit_log2);   // (at most max(C, M): below 2^31)
     q.small = q.ppf < (1LL << 31) ? 1 : 0;

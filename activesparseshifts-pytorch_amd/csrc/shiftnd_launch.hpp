@@ -1,4 +1,5 @@
-// shiftnd_launch.hpp -- host-side entry points of the two kernel families (internal).
+// shiftnd_launch.hpp -- what the host code of every kernel file shares and the host-side entry points of every kernel family, one
+// section per .hip file (internal).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -190,7 +191,6 @@ bool rows_forward_eligible(const Geometry &g, int dtype, const void *x, const vo
 int rows_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, int64_t wzp, uint64_t fill_bits, void *out,
                  hipStream_t st);
 void rows_set_tuning(int knob, int value);
-bool bytes_forward_eligible(const Geometry &g, int dtype, const void *x, const void *out);
 
 // ---- quantized shift + average pool in one pass (shiftnd_qpool.hip): one-byte element types, contiguous tensors
 bool qpool_forward_eligible(const Geometry &g, int dtype);

@@ -28,8 +28,7 @@
 //                            tensor, so the dwords of an aligned output piece are whole elements.
 // The backward of a fixed shift (shiftnd_backward's x == NULL form, whole window) is the forward under the negated table and
 // arrives here through forward_common with the gradient's strides.
-#include "shiftnd_common.hpp"
-#include "shiftnd_launch.hpp"
+#include "shiftnd_temporal.hpp"
 
 namespace shiftnd {
 namespace {
@@ -171,9 +170,6 @@ __device__ __forceinline__ shiftnd_u4 funnel(shiftnd_u4 lo, shiftnd_u4 hi, uint3
     return v;
 }
 
-// bytes [0, n) of a dword (n clamped to 0..4)
-__device__ __forceinline__ uint32_t low_bytes(int n) { return n <= 0 ? 0u : (n >= 4 ? ~0u : (1u << (8 * n)) - 1u); }
-
 // any plane size, element-aligned bases
 __device__ __forceinline__ void ragged_pieces_body(const SegmentParams &q, const char *__restrict__ x, const void *__restrict__ w,
                                                    char *__restrict__ out) {
@@ -252,18 +248,8 @@ __global__ __launch_bounds__(kThreads) void segment_forward(SegmentParams q, con
     else whole_pieces_body(q, x, w, out);
 }
 
-// dense strides of memory order N, S0, C, S1, S2 (a dim of size 1 has no stride to check)
-bool segment_major(const Geometry &g, const int64_t *st) {
-    const int lead = 3 - g.nd;
-    const int64_t A = g.nd == 3 ? g.S[1] : 1, B = g.S[2], inner = A * B;
-    if (B > 1 && st[4] != 1) return false;
-    if (A > 1 && st[3] != B) return false;
-    if (st[1] != inner || st[2 + lead] != g.C * inner) return false;
-    return g.N == 1 || st[0] == g.S[lead] * g.C * inner;
-}
-
 bool whole_pieces(const Geometry &g, int dtype, const void *x, const void *out) {
-    const int64_t plane_bytes = (g.nd == 3 ? g.S[1] : 1) * g.S[2] * dtype_size(dtype);
+    const int64_t plane_bytes = frame_pixels(g) * dtype_size(dtype);
     return plane_bytes % 16 == 0 && aligned_to(x, 16) && aligned_to(out, 16);
 }
 
@@ -272,15 +258,11 @@ bool whole_pieces(const Geometry &g, int dtype, const void *x, const void *out) 
 // float tensors, and the int_repr of quantized ones (I8, U8, I32: the caller passes their fill pattern and an integer table)
 bool segment_forward_eligible(const Geometry &g, int dtype, const void *x, const void *out) {
     if (g.active || dtype < SHIFTND_F32 || dtype > SHIFTND_I32 || cropped(g) || g.nd < 2) return false;
-    const int64_t T = g.S[3 - g.nd], inner = (g.nd == 3 ? g.S[1] : 1) * g.S[2], es = dtype_size(dtype);
-    if (g.C <= 1 || T <= 1 || !segment_major(g, g.xs) || !segment_major(g, g.os)) return false;
+    const int64_t T = g.S[3 - g.nd], es = dtype_size(dtype);
+    // (C > 1 and T > 1 from here on, so dense_segment_major checks the channel and the segment stride whatever they are)
+    if (g.C <= 1 || T <= 1 || !dense_segment_major(g, g.xs) || !dense_segment_major(g, g.os)) return false;
     if (!aligned_to(x, es) || !aligned_to(out, es)) return false;
-    // 32-bit plane and unit counts (FastDiv: below 2^31; the unit is the element where it is one byte, two bytes elsewhere, so a
-    // 1-byte tensor of 2^31 - 16 bytes or more keeps the strided kernel); T also enters the 32-bit padding map (periods of 2 T)
-    const int64_t limit = 1LL << 31;
-    if (T >= (1LL << 30) || inner >= limit || g.N >= limit || g.C >= limit || g.N * T >= limit) return false;
-    const int64_t planes = g.N * T * g.C;   // (every factor is below 2^31 here: no overflow)
-    return planes < limit && planes * (es == 1 ? inner : inner * es / 2) + 16 < limit;
+    return segment_counts_fit(g, es);   // (a tensor beyond them keeps the strided kernel)
 }
 
 int segment_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, int64_t wzp, uint64_t fill_bits, void *out,
@@ -292,10 +274,9 @@ int segment_forward(const Geometry &g, int dtype, const void *x, const void *w, 
     q.pad = g.pad;
     q.wkind = wkind;
     q.wzp = wzp;
-    q.es_log2 = es == 8 ? 3 : (es == 4 ? 2 : (es == 2 ? 1 : 0));
+    q.es_log2 = es_log2(es);
     q.unit_log2 = es == 1 ? 0 : 1;
-    // the fill as a dword pattern: a byte four times, the dword itself (floats: fill_bits == 0)
-    q.fill = es == 1 ? static_cast<uint32_t>(fill_bits & 0xff) * 0x01010101u : static_cast<uint32_t>(fill_bits);
+    q.fill = fill_dword(es, fill_bits);
     q.T = static_cast<uint32_t>(g.S[3 - g.nd]);
     q.C = static_cast<uint32_t>(g.C);
     q.A = g.nd == 3 ? g.S[1] : 1;

@@ -35,10 +35,7 @@
 // records, the same workspace bytes, a fixed order.  No new kernel, no template parameter.
 //
 // Not built: the quantized form, a cut window, channels-last tensors.
-#include <initializer_list>
-
-#include "shiftnd_common.hpp"
-#include "shiftnd_launch.hpp"
+#include "shiftnd_temporal.hpp"
 
 namespace shiftnd {
 namespace {
@@ -56,28 +53,6 @@ struct TShiftParams {
                                        // (behind the fields the per-channel call reads, whose offsets stay what they were)
 };
 
-template <typename T, int E> struct Unit { typename T::S e[E]; };
-
-template <typename T, int E, bool NT> __device__ __forceinline__ Unit<T, E> load_unit(const char *p) {
-    constexpr int V = sizeof(typename T::S) * E;
-    typedef typename vec_of<V>::type vec_t;
-    const vec_t v = NT ? __builtin_nontemporal_load(reinterpret_cast<const vec_t *>(p)) : *reinterpret_cast<const vec_t *>(p);
-    Unit<T, E> u;
-    __builtin_memcpy(u.e, &v, V);
-    return u;
-}
-template <typename T, int E> __device__ __forceinline__ Unit<T, E> zero_unit() {
-    Unit<T, E> u;
-    __builtin_memset(u.e, 0, sizeof(u.e));
-    return u;
-}
-template <typename T, int E> __device__ __forceinline__ void store_unit(char *p, const Unit<T, E> &u) {
-    constexpr int V = sizeof(typename T::S) * E;
-    typedef typename vec_of<V>::type vec_t;
-    vec_t v;
-    __builtin_memcpy(&v, u.e, V);
-    __builtin_nontemporal_store(v, reinterpret_cast<vec_t *>(p));
-}
 template <typename T, int E>
 __device__ __forceinline__ Unit<T, E> blend_units(const Unit<T, E> &a, const Unit<T, E> &b, typename T::C d) {
     Unit<T, E> r;
@@ -88,9 +63,6 @@ __device__ __forceinline__ Unit<T, E> blend_units(const Unit<T, E> &a, const Uni
     }
     return r;
 }
-
-// source segment of coordinate p in [0, T] under the canonical shift cs (a size-1 dim ignores its shift), or -1 (fill)
-__device__ __forceinline__ int source_segment(int p, int cs, int T, int pad) { return T == 1 ? 0 : fold_index(p - cs, T, pad); }
 
 constexpr int64_t kFill = -1, kPast = -2;
 
@@ -117,7 +89,7 @@ __device__ __forceinline__ void forward_body(const TShiftParams &q, const char *
         int64_t iw;
         prep_shift_forward<CT>(load_weight<CT>(w, q.wkind, n * q.wrow + c), q.active != 0, iw, dw[k]);
         const int cs = canon_shift(iw, Tn, q.pad, q.d_per);
-        const int s0 = source_segment(static_cast<int>(t), cs, Tn, q.pad), s1 = source_segment(static_cast<int>(t) + 1, cs, Tn, q.pad);
+        const int s0 = source_frame(static_cast<int>(t), cs, Tn, q.pad), s1 = source_frame(static_cast<int>(t) + 1, cs, Tn, q.pad);
         const int64_t clip = static_cast<int64_t>(n) * q.T;
         sa[k] = s0 < 0 ? kFill : ((clip + s0) * q.C + c) * q.plane_bytes + at;
         sb[k] = (s1 < 0 || !q.active) ? kFill : ((clip + s1) * q.C + c) * q.plane_bytes + at;
@@ -164,7 +136,7 @@ __device__ __forceinline__ double backward_body(const TShiftParams &q, const cha
             at[k] = u * V;
         }
         Unit<T, E> xa[kBwdInFlight], ga[kBwdInFlight];
-        const int s0 = source_segment(0, cs, Tn, q.pad);
+        const int s0 = source_frame(0, cs, Tn, q.pad);
 #pragma unroll
         for (int k = 0; k < kBwdInFlight; ++k) {
             xa[k] = ga[k] = zero_unit<T, E>();
@@ -173,8 +145,8 @@ __device__ __forceinline__ double backward_body(const TShiftParams &q, const cha
         }
 #pragma unroll 1
         for (int t = 0; t < Tn; ++t) {
-            const int s1 = source_segment(t + 1, cs, Tn, q.pad);
-            const int sg = q.active ? s1 : source_segment(t, csn, Tn, q.pad);
+            const int s1 = source_frame(t + 1, cs, Tn, q.pad);
+            const int sg = q.active ? s1 : source_frame(t, csn, Tn, q.pad);
             Unit<T, E> xb[kBwdInFlight], gb[kBwdInFlight], gv[kBwdInFlight];
 #pragma unroll
             for (int k = 0; k < kBwdInFlight; ++k) {
@@ -202,17 +174,7 @@ __device__ __forceinline__ double backward_body(const TShiftParams &q, const cha
     return acc;
 }
 
-// ONE kernel per element type and pass: the unit (`elems` elements) and `active` are launch-uniform, scalar branches
-template <int E> struct UnitElems { static constexpr int value = E; };
-template <int E, typename F> __device__ __forceinline__ void with_unit(int elems, F &&f) {
-    if constexpr (E == 1) {
-        f(UnitElems<1>());
-    } else {
-        if (elems == E) f(UnitElems<E>());
-        else with_unit<E / 2>(elems, f);
-    }
-}
-
+// ONE kernel per element type and pass: the unit (`elems` elements, with_unit) and `active` are launch-uniform, scalar branches
 template <typename T>
 __global__ __launch_bounds__(kThreads) void tshift_forward(TShiftParams q, const char *__restrict__ x, const void *__restrict__ w,
                                                           char *__restrict__ out, int elems) {
@@ -235,26 +197,6 @@ __global__ __launch_bounds__(kThreads) void tshift_backward(TShiftParams q, cons
     if (threadIdx.x == 0) partials[(static_cast<size_t>(group) * q.C + c) * 3] = total;
 }
 
-int64_t inner_elements(const Geometry &g) { return (g.nd == 3 ? g.S[1] : 1) * g.S[2]; }
-
-// dense strides of memory order N, S0, C, S1, S2 (a dim of size 1 has no stride to check)
-bool dense_segment_major(const Geometry &g, const int64_t *st) {
-    const int lead = 3 - g.nd;
-    const int64_t A = g.nd == 3 ? g.S[1] : 1, B = g.S[2], inner = A * B, T = g.S[lead];
-    if (B > 1 && st[4] != 1) return false;
-    if (A > 1 && st[3] != B) return false;
-    if (g.C > 1 && st[1] != inner) return false;
-    if (T > 1 && st[2 + lead] != g.C * inner) return false;
-    return g.N == 1 || st[0] == T * g.C * inner;
-}
-
-// bytes of the unit: the largest power of two up to 16 that divides the plane's bytes and every base
-int unit_bytes(int64_t plane_bytes, std::initializer_list<const void *> bases) {
-    uintptr_t bits = static_cast<uintptr_t>(plane_bytes) | 16;
-    for (const void *p : bases) bits |= reinterpret_cast<uintptr_t>(p);
-    return static_cast<int>(bits & (~bits + 1));
-}
-
 TShiftParams make_params(const Geometry &g, int dtype, int wkind, int unit, bool per_clip) {
     TShiftParams q;
     q.pad = g.pad;
@@ -264,7 +206,7 @@ TShiftParams make_params(const Geometry &g, int dtype, int wkind, int unit, bool
     q.C = static_cast<uint32_t>(g.C);
     q.wrow = per_clip ? q.C : 0;
     q.clips = static_cast<uint32_t>(g.N);
-    q.plane_bytes = inner_elements(g) * dtype_size(dtype);
+    q.plane_bytes = frame_pixels(g) * dtype_size(dtype);
     q.upp = static_cast<uint32_t>(q.plane_bytes / unit);
     q.chunks = static_cast<uint32_t>((q.plane_bytes + kChunkBytes - 1) / kChunkBytes);
     q.units = g.N * q.T * q.C * static_cast<int64_t>(q.upp);
@@ -295,12 +237,7 @@ void launch_backward(const TShiftParams &q, int64_t lines, const void *go, const
 
 // the geometry SHIFTND_SHIFT_DIM0 accepts: 2 or 3 spatial dims, the whole window, segment_forward_eligible's 32-bit limits
 bool tshift_geometry_ok(const Geometry &g, int dtype) {
-    if (dtype > SHIFTND_BF16 || g.nd < 2 || cropped(g)) return false;
-    const int64_t T = g.S[3 - g.nd], inner = inner_elements(g), es = dtype_size(dtype);
-    const int64_t limit = 1LL << 31;
-    if (T >= (1LL << 30) || inner >= limit || g.N >= limit || g.C >= limit || g.N * T >= limit) return false;
-    const int64_t planes = g.N * T * g.C;   // (every factor is below 2^31 here: no overflow)
-    return planes < limit && planes * (inner * es / 2) + 16 < limit;
+    return dtype <= SHIFTND_BF16 && g.nd >= 2 && !cropped(g) && segment_counts_fit(g, dtype_size(dtype));
 }
 
 bool tshift_tensor_ok(const Geometry &g, int dtype, const void *p, const int64_t *strides) {
@@ -308,7 +245,7 @@ bool tshift_tensor_ok(const Geometry &g, int dtype, const void *p, const int64_t
 }
 
 int tshift_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, bool per_clip, void *out, hipStream_t st) {
-    const int unit = unit_bytes(inner_elements(g) * dtype_size(dtype), {x, out});
+    const int unit = piece_bytes(frame_pixels(g) * dtype_size(dtype), {x, out});
     const TShiftParams q = make_params(g, dtype, wkind, unit, per_clip);
     note_kernel(unit == 16 ? "tshift_forward" : "tshift_forward_ragged");
     switch (dtype) {
@@ -321,13 +258,13 @@ int tshift_forward(const Geometry &g, int dtype, const void *x, const void *w, i
 }
 
 size_t tshift_backward_workspace(const Geometry &g, int dtype) {
-    const int64_t plane_bytes = inner_elements(g) * dtype_size(dtype);
+    const int64_t plane_bytes = frame_pixels(g) * dtype_size(dtype);
     return static_cast<size_t>(g.N * ((plane_bytes + kChunkBytes - 1) / kChunkBytes) * g.C) * 3 * sizeof(double);
 }
 
 int tshift_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, bool per_clip, void *gx,
                     void *gw, void *workspace, hipStream_t st) {
-    const int unit = unit_bytes(inner_elements(g) * dtype_size(dtype), {go, x, gx});
+    const int unit = piece_bytes(frame_pixels(g) * dtype_size(dtype), {go, x, gx});
     const TShiftParams q = make_params(g, dtype, wkind, unit, per_clip);
     double *partials = static_cast<double *>(workspace);
     note_kernel(unit == 16 ? "tshift_backward" : "tshift_backward_ragged");

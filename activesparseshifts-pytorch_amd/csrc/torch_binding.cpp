@@ -63,8 +63,8 @@ using temporal_sig = Tensor(const Tensor &, const Tensor &, int64_t, int64_t);
 using tsl_forward_sig = Tensor(const Tensor &, const Tensor &, int64_t, int64_t, bool);
 using tsl_backward_sig = std::tuple<Tensor, Tensor>(const Tensor &, const Tensor &, const Tensor &, int64_t, int64_t, bool);
 
-template <class Sig> c10::TypedOperatorHandle<Sig> typed_op(const std::string &name) {
-    return c10::Dispatcher::singleton().findSchemaOrThrow(("torchshifts::" + name).c_str(), "").typed<Sig>();
+template <class Sig> c10::TypedOperatorHandle<Sig> typed_op(const std::string &name, const char *library = "torchshifts") {
+    return c10::Dispatcher::singleton().findSchemaOrThrow((library + ("::" + name)).c_str(), "").typed<Sig>();
 }
 
 inline std::string nd_name(int nd, const char *suffix = "") { return "shift" + std::to_string(nd) + "d" + suffix; }
@@ -97,15 +97,40 @@ struct TemporalClOps {
     static auto &forward() { static auto op = typed_op<temporal_sig>("temporal_shift_cl"); return op; }
     static auto &backward() { static auto op = typed_op<temporal_sig>("_temporal_shift_cl_backward"); return op; }
 };
+// The three learnable families also carry what their HIP adapters (tsl_forward_hip / tsl_backward_hip) differ in: the names
+// check_same's messages speak under, the argument check, the flag bits of the C-ABI call, the name segment_problem's refusal speaks
+// under, and whether the route takes a dense channels-last tensor as it lies (every other tensor then goes the plain family's way).
+void tsl_check(const Tensor &input, const Tensor &weights, int64_t n_segment, int64_t padding_mode);
+void tslpc_check(const Tensor &input, const Tensor &weights, int64_t n_segment, int64_t padding_mode);
 struct LearnableOps {
     static const char *name() { return "temporal_shift_learnable"; }
     static auto &forward() { static auto op = typed_op<tsl_forward_sig>("_temporal_shift_learnable_forward"); return op; }
     static auto &backward() { static auto op = typed_op<tsl_backward_sig>("_temporal_shift_learnable_backward"); return op; }
+    static constexpr const char *kCuda = "temporal_shift_learnable_cuda", *kBackwardCuda = "temporal_shift_learnable_backward_cuda";
+    static constexpr auto check = tsl_check;
+    static constexpr int kFlags = SHIFTND_SHIFT_DIM0;
+    static constexpr const char *kProblemName = "temporal_shift_learnable";
+    static constexpr bool kAsItLies = false;
 };
 struct LearnableClOps {
     static const char *name() { return "temporal_shift_learnable_cl"; }
     static auto &forward() { static auto op = typed_op<tsl_forward_sig>("_temporal_shift_learnable_cl_forward"); return op; }
     static auto &backward() { static auto op = typed_op<tsl_backward_sig>("_temporal_shift_learnable_cl_backward"); return op; }
+    static constexpr const char *kCuda = "temporal_shift_learnable_cl_cuda", *kBackwardCuda = "temporal_shift_learnable_cl_backward_cuda";
+    static constexpr auto check = tsl_check;
+    static constexpr int kFlags = SHIFTND_SHIFT_DIM0 | SHIFTND_FRAMES;
+    static constexpr const char *kProblemName = "temporal_shift";   // (a known slip)
+    static constexpr bool kAsItLies = true;
+};
+struct PerClipLearnableOps {
+    static const char *name() { return "temporal_shift_learnable_per_clip"; }
+    static auto &forward() { static auto op = typed_op<tsl_forward_sig>("_temporal_shift_learnable_per_clip_forward", "torchshifts_per_clip"); return op; }
+    static auto &backward() { static auto op = typed_op<tsl_backward_sig>("_temporal_shift_learnable_per_clip_backward", "torchshifts_per_clip"); return op; }
+    static constexpr const char *kCuda = "temporal_shift_learnable_per_clip_cuda", *kBackwardCuda = "temporal_shift_learnable_per_clip_backward_cuda";
+    static constexpr auto check = tslpc_check;
+    static constexpr int kFlags = SHIFTND_SHIFT_DIM0 | SHIFTND_PER_CLIP;
+    static constexpr const char *kProblemName = "temporal_shift_learnable_per_clip";
+    static constexpr bool kAsItLies = false;
 };
 
 // ---- the double-backward guard ------------------------------------------------------------------------
@@ -290,14 +315,20 @@ void segment_problem(shiftnd_problem &p, int64_t st[5], const Tensor &t, int64_t
 }
 
 // what the temporal families' argument checks share; `kind`: what the family calls its per-channel table ("shifts" / "weights"),
-// `table_type_ok` / `table_types`: the family's own test of the table's element type and how the message names the types it takes
+// `table_type_ok` / `table_types`: the family's own test of the table's element type and how the message names the types it takes,
+// `per_clip`: the table is [N, C], one row per clip, not [C]
 void segment_check(const char *op_name, const Tensor &input, const Tensor &table, int64_t n_segment, int64_t padding_mode,
-                   const char *kind, bool table_type_ok, const char *table_types) {
+                   const char *kind, bool table_type_ok, const char *table_types, bool per_clip = false) {
     TORCH_CHECK(input.dim() >= 2 && input.dim() <= 5, op_name, ": expected a [N*T, C, ...] tensor of 2 to 5 dims");
     TORCH_CHECK(n_segment >= 1 && input.size(0) % n_segment == 0, op_name, ": dim 0 (", input.size(0),
                 ") must be a multiple of n_segment (", n_segment, ")");
-    TORCH_CHECK((table.dim() == 1 || (table.dim() == 2 && table.size(1) == 1)) && table.size(0) == input.size(1), op_name, ": ", kind,
-                " must have shape [C] or [C, 1]");
+    if (per_clip) {
+        TORCH_CHECK(table.dim() == 2 && table.size(0) == input.size(0) / n_segment && table.size(1) == input.size(1), op_name, ": ", kind,
+                    " must have shape [N, C] = [", input.size(0) / n_segment, ", ", input.size(1), "]");
+    } else {
+        TORCH_CHECK((table.dim() == 1 || (table.dim() == 2 && table.size(1) == 1)) && table.size(0) == input.size(1), op_name, ": ", kind,
+                    " must have shape [C] or [C, 1]");
+    }
     TORCH_CHECK(table.device() == input.device(), op_name, ": ", kind, " must be on the input's device");
     TORCH_CHECK(table_type_ok, op_name, ": ", kind, " must be ", table_types);
     TORCH_CHECK(padding_mode >= 0 && padding_mode <= 4, op_name, ": padding_mode must be 0..4");
@@ -1217,49 +1248,62 @@ void tsl_check_size(const Tensor &input, const char *who) {
                 "or split the batch");
 }
 
-// HIP tensors: one flagged C-ABI call on the segment-major strides
+// HIP tensors, the three learnable families (Ops: LearnableOps, LearnableClOps, PerClipLearnableOps): one flagged C-ABI call per
+// pass.  The plain and the per-clip route make their tensors contiguous, refuse what the segment-major kernels cannot count, and
+// answer an empty tensor themselves; the _cl route (Ops::kAsItLies) hands every tensor that is not dense channels-last to the plain
+// route first and then takes its tensors as they lie -- no contiguous(), no size check (the frame kernels have no such limit), no
+// empty tensor (none is dense channels-last), results in the argument's strides (grad_x: the gradient's).
+template <class Ops>
 Tensor tsl_forward_hip(const Tensor &input_, const Tensor &weights, int64_t n_segment, int64_t padding_mode, bool active_flag) {
-    TORCH_CHECK(input_.is_cuda(), "temporal_shift_learnable: expected a CUDA tensor");
-    tsl_check(input_, weights, n_segment, padding_mode);
-    const int mixed = weights_flag("temporal_shift_learnable_cuda", input_, "input", weights);
+    if constexpr (Ops::kAsItLies)
+        if (!is_channels_last_dense(input_)) return tsl_forward_hip<LearnableOps>(input_, weights, n_segment, padding_mode, active_flag);
+    TORCH_CHECK(input_.is_cuda(), Ops::name(), ": expected a CUDA tensor");
+    Ops::check(input_, weights, n_segment, padding_mode);
+    const int mixed = weights_flag(Ops::kCuda, input_, "input", weights);
     c10::DeviceGuard device_guard(input_.device());
-    const int dtype = to_shiftnd_dtype(input_.scalar_type(), "temporal_shift_learnable_cuda") | mixed;
-    tsl_check_size(input_, "temporal_shift_learnable");
-    const Tensor input = input_.contiguous();
-    Tensor output = at::empty(input.sizes(), input.options(), at::MemoryFormat::Contiguous);
+    const int dtype = to_shiftnd_dtype(input_.scalar_type(), Ops::kCuda) | mixed;
+    if (!Ops::kAsItLies) tsl_check_size(input_, "temporal_shift_learnable");
+    const Tensor input = Ops::kAsItLies ? input_ : input_.contiguous();
+    Tensor output = Ops::kAsItLies ? at::empty_strided(input.sizes(), input.strides(), input.options())
+                                   : at::empty(input.sizes(), input.options(), at::MemoryFormat::Contiguous);
     if (input.numel() == 0) return output;
     const Tensor w = weights.contiguous();
     shiftnd_problem p;
     int64_t st[5];
-    segment_problem(p, st, input, n_segment, padding_mode, active_flag, dtype | SHIFTND_SHIFT_DIM0, false, "temporal_shift_learnable");
-    check_status(shiftnd_forward(&p, input.data_ptr(), st, w.data_ptr(), output.data_ptr(), st, current_stream(input)),
-                 "temporal_shift_learnable (HIP)");
+    segment_problem(p, st, input, n_segment, padding_mode, active_flag, dtype | Ops::kFlags, Ops::kAsItLies, Ops::kProblemName);
+    const int rc = shiftnd_forward(&p, input.data_ptr(), st, w.data_ptr(), output.data_ptr(), st, current_stream(input));
+    TORCH_CHECK(rc == SHIFTND_OK, Ops::name(), " (HIP): ", shiftnd_status_string(rc));
     return output;
 }
 
+template <class Ops>
 std::tuple<Tensor, Tensor> tsl_backward_hip(const Tensor &grad_, const Tensor &weights, const Tensor &input_, int64_t n_segment,
                                             int64_t padding_mode, bool active_flag) {
-    TORCH_CHECK(grad_.is_cuda() && input_.is_cuda(), "temporal_shift_learnable: expected CUDA tensors");
-    tsl_check(input_, weights, n_segment, padding_mode);
-    check_same("temporal_shift_learnable_backward_cuda", grad_, "grad", input_, "input");
-    const int mixed = weights_flag("temporal_shift_learnable_backward_cuda", grad_, "grad", weights);
-    TORCH_CHECK(grad_.sizes() == input_.sizes(), "temporal_shift_learnable backward: grad does not match the input");
+    if constexpr (Ops::kAsItLies)
+        if (!is_channels_last_dense(input_) || !is_channels_last_dense(grad_) || grad_.sizes() != input_.sizes())
+            return tsl_backward_hip<LearnableOps>(grad_, weights, input_, n_segment, padding_mode, active_flag);   // (contiguous grad_x)
+    TORCH_CHECK(grad_.is_cuda() && input_.is_cuda(), Ops::name(), ": expected CUDA tensors");
+    Ops::check(input_, weights, n_segment, padding_mode);
+    check_same(Ops::kBackwardCuda, grad_, "grad", input_, "input");
+    const int mixed = weights_flag(Ops::kBackwardCuda, grad_, "grad", weights);
+    TORCH_CHECK(grad_.sizes() == input_.sizes(), Ops::name(), " backward: grad does not match the input");
     c10::DeviceGuard device_guard(grad_.device());
-    const int dtype = to_shiftnd_dtype(grad_.scalar_type(), "temporal_shift_learnable_backward_cuda") | mixed;
-    tsl_check_size(input_, "temporal_shift_learnable backward");
-    const Tensor input = input_.contiguous(), grad = grad_.contiguous();
+    const int dtype = to_shiftnd_dtype(grad_.scalar_type(), Ops::kBackwardCuda) | mixed;
+    if (!Ops::kAsItLies) tsl_check_size(input_, "temporal_shift_learnable backward");
+    const Tensor input = Ops::kAsItLies ? input_ : input_.contiguous(), grad = Ops::kAsItLies ? grad_ : grad_.contiguous();
     const Tensor w = weights.contiguous();
-    Tensor grad_input = at::empty(input.sizes(), input.options(), at::MemoryFormat::Contiguous);
+    Tensor grad_input = Ops::kAsItLies ? at::empty_strided(grad.sizes(), grad.strides(), grad.options())
+                                       : at::empty(input.sizes(), input.options(), at::MemoryFormat::Contiguous);
     Tensor grad_weights = at::empty_like(w, at::MemoryFormat::Contiguous);   // (the weights' dtype: fp32 for a mixed call)
     if (input.numel() == 0) return std::make_tuple(grad_input, grad_weights.zero_());   // (no kernel runs: the zero gradient is written here)
     shiftnd_problem p;
     int64_t st[5];
-    segment_problem(p, st, input, n_segment, padding_mode, active_flag, dtype | SHIFTND_SHIFT_DIM0, false, "temporal_shift_learnable");
+    segment_problem(p, st, input, n_segment, padding_mode, active_flag, dtype | Ops::kFlags, Ops::kAsItLies, Ops::kProblemName);
     const size_t ws_bytes = shiftnd_backward_workspace_bytes(&p);
     Tensor workspace = workspace_like(input, ws_bytes);
-    check_status(shiftnd_backward(&p, grad.data_ptr(), st, input.data_ptr(), st, w.data_ptr(), grad_input.data_ptr(), st,
-                                  grad_weights.data_ptr(), workspace.data_ptr(), ws_bytes, current_stream(grad)),
-                 "temporal_shift_learnable backward (HIP)");
+    const int rc = shiftnd_backward(&p, grad.data_ptr(), st, input.data_ptr(), st, w.data_ptr(), grad_input.data_ptr(), st,
+                                    grad_weights.data_ptr(), workspace.data_ptr(), ws_bytes, current_stream(grad));
+    TORCH_CHECK(rc == SHIFTND_OK, Ops::name(), " backward (HIP): ", shiftnd_status_string(rc));
     return std::make_tuple(grad_input, grad_weights);
 }
 
@@ -1282,48 +1326,6 @@ std::tuple<Tensor, Tensor> tsl_cl_backward_cpu(const Tensor &grad, const Tensor 
     return std::make_tuple(in_layout_of(std::get<0>(result), grad), std::get<1>(result));
 }
 
-// HIP tensors: the problem [N, C, T, M] on the strides {T*M*C, 1, M*C, C} under both flags
-Tensor tsl_cl_forward_hip(const Tensor &input, const Tensor &weights, int64_t n_segment, int64_t padding_mode, bool active_flag) {
-    if (!is_channels_last_dense(input)) return tsl_forward_hip(input, weights, n_segment, padding_mode, active_flag);
-    TORCH_CHECK(input.is_cuda(), "temporal_shift_learnable_cl: expected a CUDA tensor");
-    tsl_check(input, weights, n_segment, padding_mode);
-    const int mixed = weights_flag("temporal_shift_learnable_cl_cuda", input, "input", weights);
-    c10::DeviceGuard device_guard(input.device());
-    const int dtype = to_shiftnd_dtype(input.scalar_type(), "temporal_shift_learnable_cl_cuda") | mixed;
-    Tensor output = at::empty_strided(input.sizes(), input.strides(), input.options());
-    const Tensor w = weights.contiguous();
-    shiftnd_problem p;
-    int64_t st[5];
-    segment_problem(p, st, input, n_segment, padding_mode, active_flag, dtype | SHIFTND_FRAMES | SHIFTND_SHIFT_DIM0, true, "temporal_shift");
-    check_status(shiftnd_forward(&p, input.data_ptr(), st, w.data_ptr(), output.data_ptr(), st, current_stream(input)),
-                 "temporal_shift_learnable_cl (HIP)");
-    return output;
-}
-
-std::tuple<Tensor, Tensor> tsl_cl_backward_hip(const Tensor &grad, const Tensor &weights, const Tensor &input, int64_t n_segment,
-                                               int64_t padding_mode, bool active_flag) {
-    if (!is_channels_last_dense(input) || !is_channels_last_dense(grad) || grad.sizes() != input.sizes())
-        return tsl_backward_hip(grad, weights, input, n_segment, padding_mode, active_flag);   // (contiguous grad_x)
-    TORCH_CHECK(grad.is_cuda() && input.is_cuda(), "temporal_shift_learnable_cl: expected CUDA tensors");
-    tsl_check(input, weights, n_segment, padding_mode);
-    check_same("temporal_shift_learnable_cl_backward_cuda", grad, "grad", input, "input");
-    const int mixed = weights_flag("temporal_shift_learnable_cl_backward_cuda", grad, "grad", weights);
-    c10::DeviceGuard device_guard(grad.device());
-    const int dtype = to_shiftnd_dtype(grad.scalar_type(), "temporal_shift_learnable_cl_backward_cuda") | mixed;
-    const Tensor w = weights.contiguous();
-    Tensor grad_input = at::empty_strided(grad.sizes(), grad.strides(), grad.options());
-    Tensor grad_weights = at::empty_like(w, at::MemoryFormat::Contiguous);   // (the weights' dtype: fp32 for a mixed call)
-    shiftnd_problem p;
-    int64_t st[5];
-    segment_problem(p, st, input, n_segment, padding_mode, active_flag, dtype | SHIFTND_FRAMES | SHIFTND_SHIFT_DIM0, true, "temporal_shift");
-    const size_t ws_bytes = shiftnd_backward_workspace_bytes(&p);
-    Tensor workspace = workspace_like(input, ws_bytes);
-    check_status(shiftnd_backward(&p, grad.data_ptr(), st, input.data_ptr(), st, w.data_ptr(), grad_input.data_ptr(), st,
-                                  grad_weights.data_ptr(), workspace.data_ptr(), ws_bytes, current_stream(grad)),
-                 "temporal_shift_learnable_cl backward (HIP)");
-    return std::make_tuple(grad_input, grad_weights);
-}
-
 // ---- per-clip temporal shift: torchshifts_per_clip::temporal_shift_learnable_per_clip / temporal_shift_per_clip ---------------------
 // The temporal shifts under a table of shape [N, C], N = input.size(0) / n_segment: clip n is shifted by row n (a shift that a small
 // net predicts from the clip -- TIN's OffsetNet, arXiv 2001.06499 -- or per-clip temporal jitter).  By definition, for every clip n,
@@ -1335,40 +1337,21 @@ std::tuple<Tensor, Tensor> tsl_cl_backward_hip(const Tensor &grad, const Tensor 
 // same call on the gradient under the negated table, so that no kernel reads the input or forms a weight gradient.  Its table is
 // built like the channels-last routes': fp32 for 16-bit tensors (every shift exact), the tensor's dtype for fp32 / fp64.
 // A namespace of its own for the reason torchshifts_inplace:: has one.
-template <class Sig> c10::TypedOperatorHandle<Sig> per_clip_op(const char *name) {
-    return c10::Dispatcher::singleton().findSchemaOrThrow((std::string("torchshifts_per_clip::") + name).c_str(), "").typed<Sig>();
-}
-struct PerClipLearnableOps {
-    static const char *name() { return "temporal_shift_learnable_per_clip"; }
-    static auto &forward() { static auto op = per_clip_op<tsl_forward_sig>("_temporal_shift_learnable_per_clip_forward"); return op; }
-    static auto &backward() { static auto op = per_clip_op<tsl_backward_sig>("_temporal_shift_learnable_per_clip_backward"); return op; }
-};
-struct PerClipOps {
+struct PerClipOps {   // (the learnable pair: PerClipLearnableOps, beside LearnableOps)
     static const char *name() { return "temporal_shift_per_clip"; }
-    static auto &forward() { static auto op = per_clip_op<temporal_sig>("temporal_shift_per_clip"); return op; }
-    static auto &backward() { static auto op = per_clip_op<temporal_sig>("_temporal_shift_per_clip_backward"); return op; }
+    static auto &forward() { static auto op = typed_op<temporal_sig>("temporal_shift_per_clip", "torchshifts_per_clip"); return op; }
+    static auto &backward() { static auto op = typed_op<temporal_sig>("_temporal_shift_per_clip_backward", "torchshifts_per_clip"); return op; }
 };
 
-// segment_check for a [N, C] table
-void per_clip_check(const char *op_name, const Tensor &input, const Tensor &table, int64_t n_segment, int64_t padding_mode,
-                    const char *kind, bool table_type_ok, const char *table_types) {
-    TORCH_CHECK(!input.is_quantized(), op_name, ": quantized inputs are not supported");
-    TORCH_CHECK(input.dim() >= 2 && input.dim() <= 5, op_name, ": expected a [N*T, C, ...] tensor of 2 to 5 dims");
-    TORCH_CHECK(n_segment >= 1 && input.size(0) % n_segment == 0, op_name, ": dim 0 (", input.size(0),
-                ") must be a multiple of n_segment (", n_segment, ")");
-    TORCH_CHECK(table.dim() == 2 && table.size(0) == input.size(0) / n_segment && table.size(1) == input.size(1), op_name, ": ", kind,
-                " must have shape [N, C] = [", input.size(0) / n_segment, ", ", input.size(1), "]");
-    TORCH_CHECK(table.device() == input.device(), op_name, ": ", kind, " must be on the input's device");
-    TORCH_CHECK(table_type_ok, op_name, ": ", kind, " must be ", table_types);
-    TORCH_CHECK(padding_mode >= 0 && padding_mode <= 4, op_name, ": padding_mode must be 0..4");
-}
 void tslpc_check(const Tensor &input, const Tensor &weights, int64_t n_segment, int64_t padding_mode) {
-    per_clip_check("temporal_shift_learnable_per_clip", input, weights, n_segment, padding_mode, "weights",
-                   at::isFloatingType(weights.scalar_type()), "floats");
+    TORCH_CHECK(!input.is_quantized(), "temporal_shift_learnable_per_clip: quantized inputs are not supported");
+    segment_check("temporal_shift_learnable_per_clip", input, weights, n_segment, padding_mode, "weights",
+                  at::isFloatingType(weights.scalar_type()), "floats", true);
 }
 void tpc_check(const Tensor &input, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
-    per_clip_check("temporal_shift_per_clip", input, shifts, n_segment, padding_mode, "shifts", is_integer_or_float(shifts),
-                   "integers or floats");
+    TORCH_CHECK(!input.is_quantized(), "temporal_shift_per_clip: quantized inputs are not supported");
+    segment_check("temporal_shift_per_clip", input, shifts, n_segment, padding_mode, "shifts", is_integer_or_float(shifts),
+                  "integers or floats", true);
 }
 
 // the public entry and the Autograd-key kernels: the nodes are temporal_shift_learnable's (input and weights kept) and
@@ -1441,54 +1424,8 @@ Tensor tpc_backward_cpu(const Tensor &grad, const Tensor &shifts, int64_t n_segm
     return tpc_cpu(grad, shifts.detach(), n_segment, padding_mode, true);
 }
 
-// HIP tensors: one call under SHIFTND_SHIFT_DIM0 | SHIFTND_PER_CLIP on the segment-major strides
-Tensor tslpc_forward_hip(const Tensor &input_, const Tensor &weights, int64_t n_segment, int64_t padding_mode, bool active_flag) {
-    TORCH_CHECK(input_.is_cuda(), "temporal_shift_learnable_per_clip: expected a CUDA tensor");
-    tslpc_check(input_, weights, n_segment, padding_mode);
-    const int mixed = weights_flag("temporal_shift_learnable_per_clip_cuda", input_, "input", weights);
-    c10::DeviceGuard device_guard(input_.device());
-    const int dtype = to_shiftnd_dtype(input_.scalar_type(), "temporal_shift_learnable_per_clip_cuda") | mixed;
-    tsl_check_size(input_, "temporal_shift_learnable");
-    const Tensor input = input_.contiguous();
-    Tensor output = at::empty(input.sizes(), input.options(), at::MemoryFormat::Contiguous);
-    if (input.numel() == 0) return output;
-    const Tensor w = weights.contiguous();
-    shiftnd_problem p;
-    int64_t st[5];
-    segment_problem(p, st, input, n_segment, padding_mode, active_flag, dtype | SHIFTND_SHIFT_DIM0 | SHIFTND_PER_CLIP, false,
-                    "temporal_shift_learnable_per_clip");
-    check_status(shiftnd_forward(&p, input.data_ptr(), st, w.data_ptr(), output.data_ptr(), st, current_stream(input)),
-                 "temporal_shift_learnable_per_clip (HIP)");
-    return output;
-}
-
-std::tuple<Tensor, Tensor> tslpc_backward_hip(const Tensor &grad_, const Tensor &weights, const Tensor &input_, int64_t n_segment,
-                                              int64_t padding_mode, bool active_flag) {
-    TORCH_CHECK(grad_.is_cuda() && input_.is_cuda(), "temporal_shift_learnable_per_clip: expected CUDA tensors");
-    tslpc_check(input_, weights, n_segment, padding_mode);
-    check_same("temporal_shift_learnable_per_clip_backward_cuda", grad_, "grad", input_, "input");
-    const int mixed = weights_flag("temporal_shift_learnable_per_clip_backward_cuda", grad_, "grad", weights);
-    TORCH_CHECK(grad_.sizes() == input_.sizes(), "temporal_shift_learnable_per_clip backward: grad does not match the input");
-    c10::DeviceGuard device_guard(grad_.device());
-    const int dtype = to_shiftnd_dtype(grad_.scalar_type(), "temporal_shift_learnable_per_clip_backward_cuda") | mixed;
-    tsl_check_size(input_, "temporal_shift_learnable backward");
-    const Tensor input = input_.contiguous(), grad = grad_.contiguous();
-    const Tensor w = weights.contiguous();
-    Tensor grad_input = at::empty(input.sizes(), input.options(), at::MemoryFormat::Contiguous);
-    Tensor grad_weights = at::empty_like(w, at::MemoryFormat::Contiguous);   // (the weights' dtype: fp32 for a mixed call)
-    if (input.numel() == 0) return std::make_tuple(grad_input, grad_weights.zero_());   // (no kernel runs: the zero gradient is written here)
-    shiftnd_problem p;
-    int64_t st[5];
-    segment_problem(p, st, input, n_segment, padding_mode, active_flag, dtype | SHIFTND_SHIFT_DIM0 | SHIFTND_PER_CLIP, false,
-                    "temporal_shift_learnable_per_clip");
-    const size_t ws_bytes = shiftnd_backward_workspace_bytes(&p);
-    Tensor workspace = workspace_like(input, ws_bytes);
-    check_status(shiftnd_backward(&p, grad.data_ptr(), st, input.data_ptr(), st, w.data_ptr(), grad_input.data_ptr(), st,
-                                  grad_weights.data_ptr(), workspace.data_ptr(), ws_bytes, current_stream(grad)),
-                 "temporal_shift_learnable_per_clip backward (HIP)");
-    return std::make_tuple(grad_input, grad_weights);
-}
-
+// HIP tensors: one call under SHIFTND_SHIFT_DIM0 | SHIFTND_PER_CLIP on the segment-major strides (the learnable pair: tsl_forward_hip /
+// tsl_backward_hip under PerClipLearnableOps)
 Tensor tpc_hip(const Tensor &t_, const Tensor &shifts, int64_t n_segment, int64_t padding_mode, bool backward) {
     TORCH_CHECK(t_.is_cuda(), "temporal_shift_per_clip: expected a CUDA tensor");
     tpc_check(t_, shifts, n_segment, padding_mode);
@@ -1534,10 +1471,7 @@ using temporal_inplace_sig = Tensor &(Tensor &, const Tensor &, int64_t, int64_t
 
 struct InplaceOps {
     static const char *name() { return "temporal_shift_"; }
-    static auto &forward() {
-        static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("torchshifts_inplace::temporal_shift_", "").typed<temporal_inplace_sig>();
-        return op;
-    }
+    static auto &forward() { static auto op = typed_op<temporal_inplace_sig>("temporal_shift_", "torchshifts_inplace"); return op; }
     static auto &backward() { return TemporalOps::backward(); }
 };
 struct InplaceClOps : InplaceOps {
@@ -1790,10 +1724,10 @@ TORCH_LIBRARY_IMPL(torchshifts, CUDA, m) {
     m.impl("_temporal_shift_backward", TORCH_FN(temporal_backward_hip));
     m.impl("temporal_shift_cl", TORCH_FN(temporal_cl_forward_hip));
     m.impl("_temporal_shift_cl_backward", TORCH_FN(temporal_cl_backward_hip));
-    m.impl("_temporal_shift_learnable_forward", TORCH_FN(tsl_forward_hip));
-    m.impl("_temporal_shift_learnable_backward", TORCH_FN(tsl_backward_hip));
-    m.impl("_temporal_shift_learnable_cl_forward", TORCH_FN(tsl_cl_forward_hip));
-    m.impl("_temporal_shift_learnable_cl_backward", TORCH_FN(tsl_cl_backward_hip));
+    m.impl("_temporal_shift_learnable_forward", TORCH_FN(tsl_forward_hip<LearnableOps>));
+    m.impl("_temporal_shift_learnable_backward", TORCH_FN(tsl_backward_hip<LearnableOps>));
+    m.impl("_temporal_shift_learnable_cl_forward", TORCH_FN(tsl_forward_hip<LearnableClOps>));
+    m.impl("_temporal_shift_learnable_cl_backward", TORCH_FN(tsl_backward_hip<LearnableClOps>));
 }
 
 TORCH_LIBRARY_IMPL(torchshifts, QuantizedCPU, m) {
@@ -1836,8 +1770,8 @@ TORCH_LIBRARY_IMPL(torchshifts_per_clip, CPU, m) {
     m.impl("_temporal_shift_per_clip_backward", TORCH_FN(tpc_backward_cpu));
 }
 TORCH_LIBRARY_IMPL(torchshifts_per_clip, CUDA, m) {
-    m.impl("_temporal_shift_learnable_per_clip_forward", TORCH_FN(tslpc_forward_hip));
-    m.impl("_temporal_shift_learnable_per_clip_backward", TORCH_FN(tslpc_backward_hip));
+    m.impl("_temporal_shift_learnable_per_clip_forward", TORCH_FN(tsl_forward_hip<PerClipLearnableOps>));
+    m.impl("_temporal_shift_learnable_per_clip_backward", TORCH_FN(tsl_backward_hip<PerClipLearnableOps>));
     m.impl("temporal_shift_per_clip", TORCH_FN(tpc_forward_hip));
     m.impl("_temporal_shift_per_clip_backward", TORCH_FN(tpc_backward_hip));
 }

@@ -1,4 +1,5 @@
-"""The surface of the torch operator library, pinned on CPU tensors: every schema string, which dispatch keys hold a kernel for every
+"""The surface of the torch operator library (torchshifts:: and the two later namespaces, torchshifts_per_clip:: and
+torchshifts_inplace::), pinned on CPU tensors: every schema string, which dispatch keys hold a kernel for every
 op, the whole message of every double-backward guard and of every argument refusal a CPU tensor can reach, and what each forward
 node saves.  Nothing here computes anything of size: the point is that a change to csrc/torch_binding.cpp that moves a name, a key,
 a message or a saved tensor fails a test that says which.
@@ -12,6 +13,8 @@ import torch
 import torchshifts  # noqa: F401
 
 OPS = torch.ops.torchshifts
+PER_CLIP = torch.ops.torchshifts_per_clip
+INPLACE = torch.ops.torchshifts_inplace
 N, T, C = 2, 3, 5
 
 SHIFT_FWD = "(Tensor input, Tensor weights, Tensor borders, int[] new_size, int padding_mode, bool active_flag) -> Tensor"
@@ -134,13 +137,38 @@ KERNELS = {
 }
 
 
-def registered_ops():
-    return sorted(n.split("::", 1)[1] for n in torch._C._dispatch_get_all_op_names() if n.startswith("torchshifts::"))
+# the two later namespaces: "<namespace>::<op>" -> the same two tables
+TEMPORAL_INPLACE = "(Tensor(a!) input, Tensor shifts, int n_segment, int padding_mode) -> Tensor(a!)"
+LATER_SCHEMAS = {
+    "torchshifts_per_clip::temporal_shift_learnable_per_clip": TSL_FWD,
+    "torchshifts_per_clip::_temporal_shift_learnable_per_clip_forward": TSL_FWD,
+    "torchshifts_per_clip::_temporal_shift_learnable_per_clip_backward": TSL_BWD,
+    "torchshifts_per_clip::temporal_shift_per_clip": TEMPORAL,
+    "torchshifts_per_clip::_temporal_shift_per_clip_backward": TEMPORAL_BWD,
+    "torchshifts_inplace::temporal_shift_": TEMPORAL_INPLACE,
+    "torchshifts_inplace::temporal_shift_quantized_": TEMPORAL_INPLACE,
+}
+LATER_KERNELS = {
+    "torchshifts_per_clip::temporal_shift_learnable_per_clip": COMPOSITE,
+    "torchshifts_per_clip::_temporal_shift_learnable_per_clip_forward": FLOAT,
+    "torchshifts_per_clip::_temporal_shift_learnable_per_clip_backward": FLOAT,
+    "torchshifts_per_clip::temporal_shift_per_clip": FLOAT,
+    "torchshifts_per_clip::_temporal_shift_per_clip_backward": FLOAT,
+    "torchshifts_inplace::temporal_shift_": FLOAT,
+    "torchshifts_inplace::temporal_shift_quantized_": QUANT,
+}
+
+
+def registered_ops(namespace="torchshifts"):
+    return sorted(n.split("::", 1)[1] for n in torch._C._dispatch_get_all_op_names() if n.startswith(namespace + "::"))
 
 
 def test_no_op_beyond_the_pinned_set():
     assert registered_ops() == sorted(SCHEMAS)
     assert sorted(KERNELS) == sorted(SCHEMAS)
+    for namespace in ("torchshifts_per_clip", "torchshifts_inplace"):
+        assert [namespace + "::" + op for op in registered_ops(namespace)] == sorted(n for n in LATER_SCHEMAS if n.startswith(namespace + "::"))
+    assert sorted(LATER_KERNELS) == sorted(LATER_SCHEMAS)
 
 
 @pytest.mark.parametrize("op", sorted(SCHEMAS))
@@ -152,6 +180,17 @@ def test_schema(op):
 def test_dispatch_keys(op):
     have = tuple(k for k in KEYS if torch._C._dispatch_has_kernel_for_dispatch_key("torchshifts::" + op, k))
     assert have == KERNELS[op]
+
+
+@pytest.mark.parametrize("op", sorted(LATER_SCHEMAS))
+def test_schema_of_the_later_namespaces(op):
+    assert str(torch._C._get_schema(op, "")) == op + LATER_SCHEMAS[op]
+
+
+@pytest.mark.parametrize("op", sorted(LATER_KERNELS))
+def test_dispatch_keys_of_the_later_namespaces(op):
+    have = tuple(k for k in KEYS if torch._C._dispatch_has_kernel_for_dispatch_key(op, k))
+    assert have == LATER_KERNELS[op]
 
 
 # ---- arguments ------------------------------------------------------------------------------------------------------------------
@@ -224,6 +263,23 @@ def test_a_second_backward_raises_under_the_ops_name(make, arg):
     assert message(first.sum().backward) == "double backwards on %s not supported" % name
 
 
+def grads_of_per_clip_learnable(_):
+    w = torch.randn(N, C)
+    return PER_CLIP._temporal_shift_learnable_per_clip_backward(frames(True), w, frames(), T, 0, True), "temporal_shift_learnable_per_clip"
+
+
+def grads_of_per_clip(_):
+    return PER_CLIP._temporal_shift_per_clip_backward(frames(True), torch.ones(N, C, dtype=torch.int64), T, 0), "temporal_shift_per_clip"
+
+
+@pytest.mark.parametrize("make", [grads_of_per_clip_learnable, grads_of_per_clip], ids=["learnable", "fixed"])
+def test_a_second_backward_of_the_per_clip_ops_raises_under_the_ops_name(make):
+    out, name = make(None)
+    first = out if torch.is_tensor(out) else out[0]
+    assert first.requires_grad
+    assert message(first.sum().backward) == "double backwards on %s not supported" % name
+
+
 # ---- argument refusals ---------------------------------------------------------------------------------------------------------
 S = torch.tensor([1, 0, -1, 2, 0])                       # a [C] table of shifts
 W = torch.tensor([0.5, -1.25, 2.0, 0.0, 1.0])            # [C] learnable shifts
@@ -235,9 +291,9 @@ def per_channel(t):
     return torch.quantize_per_channel(t, torch.full((C,), 0.1), torch.zeros(C, dtype=torch.int64), 1, torch.quint8)
 
 
-def segment_refusals(op, prefix, table, kind, extra, wrong_type, types):
+def segment_refusals(op, prefix, table, kind, extra, wrong_type, types, ops=OPS):
     """the seven lines of a segment family's check, in the order the check has them"""
-    call = lambda x, t, n, pad: getattr(OPS, op)(x, t, n, pad, *extra)   # noqa: E731
+    call = lambda x, t, n, pad: getattr(ops, op)(x, t, n, pad, *extra)   # noqa: E731
     return [
         (call, (quantized(frames()), table, T, 0), prefix + ": quantized inputs are not supported"),
         (call, (torch.randn(N * T), table, T, 0), prefix + ": expected a [N*T, C, ...] tensor of 2 to 5 dims"),
@@ -307,6 +363,63 @@ REFUSALS = (
 )
 
 
+SN = torch.ones(N, C, dtype=torch.int64)                 # a [N, C] table of shifts
+WN = torch.full((N, C), 0.5)                             # [N, C] learnable shifts
+
+
+def per_clip_refusals(op, table, kind, extra, wrong_type, types):
+    """the seven lines of per_clip_check, in the order the check has them"""
+    call = lambda x, t, n, pad: getattr(PER_CLIP, op)(x, t, n, pad, *extra)   # noqa: E731
+    prefix = op.lstrip("_").replace("_forward", "")
+    return [
+        (call, (quantized(frames()), table, T, 0), prefix + ": quantized inputs are not supported"),
+        (call, (torch.randn(N * T), table, T, 0), prefix + ": expected a [N*T, C, ...] tensor of 2 to 5 dims"),
+        (call, (frames(), table, 4, 0), prefix + ": dim 0 (6) must be a multiple of n_segment (4)"),
+        (call, (frames(), table[0], T, 0), prefix + ": %s must have shape [N, C] = [2, 5]" % kind),
+        (call, (frames(), table[:1], T, 0), prefix + ": %s must have shape [N, C] = [2, 5]" % kind),
+        (call, (frames(), table[:, :4], 2, 0), prefix + ": %s must have shape [N, C] = [3, 5]" % kind),
+        (call, (frames(), table.to("meta"), T, 0), prefix + ": %s must be on the input's device" % kind),
+        (call, (frames(), wrong_type, T, 0), prefix + ": %s must be %s" % (kind, types)),
+        (call, (frames(), table, T, 5), prefix + ": padding_mode must be 0..4"),
+    ]
+
+
+def quantized_inplace(x, s, n, pad):
+    return INPLACE.temporal_shift_quantized_(x, s, n, pad)
+
+
+LATER_REFUSALS = (
+    # per_clip_check under both names, and before the guarded backward nodes and the CPU kernels' own lines
+    per_clip_refusals("temporal_shift_learnable_per_clip", WN, "weights", (True,), SN, "floats") +
+    per_clip_refusals("_temporal_shift_learnable_per_clip_forward", WN, "weights", (True,), SN, "floats")[3:4] +
+    per_clip_refusals("temporal_shift_per_clip", SN, "shifts", (), SN.bool(), "integers or floats") +
+    [(PER_CLIP._temporal_shift_learnable_per_clip_backward, (frames(), SN, frames(), T, 0, True),
+      "temporal_shift_learnable_per_clip: weights must be floats"),
+     (PER_CLIP._temporal_shift_learnable_per_clip_backward, (frames()[:T], WN, frames(), T, 0, True),
+      "temporal_shift_learnable_per_clip backward: grad does not match the input"),
+     (PER_CLIP._temporal_shift_per_clip_backward, (frames(), SN, 4, 0), "temporal_shift_per_clip: dim 0 (6) must be a multiple of n_segment (4)")] +
+    # temporal_inplace_check
+    segment_refusals("temporal_shift_", "temporal_shift_", S, "shifts", (), S.bool(), "integers or floats", INPLACE) +
+    # temporal_quantized_inplace_check
+    [(quantized_inplace, (frames(), quantized(S.float()), T, 0), "temporal_shift_quantized_: expected a quantized input"),
+     (quantized_inplace, (per_channel(frames()), S, T, 0), "temporal_shift_quantized_: expected a per-tensor quantized input"),
+     (quantized_inplace, (quantized(torch.randn(N * T)), S, T, 0), "temporal_shift_quantized_: expected a [N*T, C, ...] tensor of 2 to 5 dims"),
+     (quantized_inplace, (quantized(frames()), S, 4, 0), "temporal_shift_quantized_: dim 0 (6) must be a multiple of n_segment (4)"),
+     (quantized_inplace, (quantized(frames()), S[:4], T, 0), "temporal_shift_quantized_: shifts must have shape [C] or [C, 1]"),
+     # (its device line is out of a CPU tensor's reach, as temporal_shift_quantized's is: a meta table takes the call to another key)
+     (quantized_inplace, (quantized(frames()), quantized(S.float()), T, 0), "temporal_shift_quantized_: shifts must be integers or floats"),
+     (quantized_inplace, (quantized(frames()), S.bool(), T, 0), "temporal_shift_quantized_: shifts must be integers or floats"),
+     (quantized_inplace, (quantized(frames()), S, T, -1), "temporal_shift_quantized_: padding_mode must be 0..4")]
+)
+
+
+@pytest.mark.parametrize("case", range(len(LATER_REFUSALS)),
+                         ids=["%02d-%s" % (i, r[2][:48].replace(" ", "_")) for i, r in enumerate(LATER_REFUSALS)])
+def test_argument_refusal_of_the_later_namespaces(case):
+    fn, args, text = LATER_REFUSALS[case]
+    assert message(fn, *args) == text
+
+
 @pytest.mark.parametrize("case", range(len(REFUSALS)), ids=["%02d-%s" % (i, r[2][:40].replace(" ", "_")) for i, r in enumerate(REFUSALS)])
 def test_argument_refusal(case):
     fn, args, text = REFUSALS[case]
@@ -355,3 +468,15 @@ def test_temporal_nodes_save_the_table_alone(op):
 def test_learnable_nodes_save_input_and_weights(op):
     x, w = frames(True), W.clone().requires_grad_(True)
     assert saved_shapes(lambda: getattr(OPS, op)(x, w, T, 0, True)) == [(N * T, C, 2, 2), (C,)]
+
+
+def test_per_clip_nodes_save_what_the_per_channel_nodes_save():
+    x, w = frames(True), WN.clone().requires_grad_(True)
+    assert saved_shapes(lambda: PER_CLIP.temporal_shift_learnable_per_clip(x, w, T, 0, True)) == [(N * T, C, 2, 2), (N, C)]
+    assert saved_shapes(lambda: PER_CLIP.temporal_shift_per_clip(x, SN, T, 0)) == [(N, C)]
+
+
+def test_the_inplace_node_saves_the_table_alone():
+    assert saved_shapes(lambda: INPLACE.temporal_shift_(frames(True).clone(), S, T, 0)) == [(C,)]
+    xc = frames(True).contiguous(memory_format=torch.channels_last)
+    assert saved_shapes(lambda: INPLACE.temporal_shift_(xc, S.reshape(C, 1), T, 0)) == [(C, 1)]

@@ -399,3 +399,41 @@ def test_the_module_trains_one_step():
     out.square().mean().backward()
     opt.step()
     assert torch.isfinite(net.weight).all() and not torch.equal(net.weight.detach(), before)
+
+
+# ---- the refusals of the three learnable families' HIP adapters that only a HIP tensor reaches ---------------------------------------
+# Every case raises before a kernel is launched.  [4, 3, 2, 2], n_segment 2: N = 2 clips, C = 3; contiguous and channels-last.
+_SAME_TYPE = "Expected tensor for %s to have the same type as tensor for %s; but type %s does not equal %s (while checking arguments for %s)"
+LEARNABLE_FAMILIES = {   # family -> namespace, op stem, the table's shape
+    "plain": (torch.ops.torchshifts, "temporal_shift_learnable", (3,)),
+    "cl": (torch.ops.torchshifts, "temporal_shift_learnable_cl", (3,)),
+    "per_clip": (OPS, "temporal_shift_learnable_per_clip", (2, 3)),
+}
+
+
+def _message(fn, *args):
+    with pytest.raises(RuntimeError) as e:
+        fn(*args)
+    return str(e.value).split("\n")[0]
+
+
+@pytest.mark.parametrize("channels_last", [False, True], ids=["contiguous", "channels_last"])
+@pytest.mark.parametrize("backward", [False, True], ids=["forward", "backward"])
+@pytest.mark.parametrize("family", sorted(LEARNABLE_FAMILIES))
+def test_the_refusals_only_a_hip_tensor_reaches(family, backward, channels_last):
+    ops, stem, table = LEARNABLE_FAMILIES[family]
+    lay = (lambda t: t.contiguous(memory_format=torch.channels_last)) if channels_last else (lambda t: t)
+    x, g = lay(torch.randn(4, 3, 2, 2, device="cuda")), lay(torch.randn(4, 3, 2, 2, device="cuda"))
+    w = torch.zeros(table, device="cuda")
+    # the _cl adapters speak under their own name for dense channels-last tensors and hand every other call to the plain adapters
+    said = stem if (family != "cl" or channels_last) else "temporal_shift_learnable"
+    if not backward:
+        fwd = getattr(ops, "_%s_forward" % stem)
+        assert _message(fwd, x, w.double(), 2, 0, True) == _SAME_TYPE % ("input", "weights", "Float", "Double", said + "_cuda")
+        return
+    bwd = getattr(ops, "_%s_backward" % stem)
+    assert _message(bwd, g, w.double(), x, 2, 0, True) == _SAME_TYPE % ("grad", "weights", "Float", "Double", said + "_backward_cuda")
+    assert _message(bwd, g.double(), w, x, 2, 0, True) == _SAME_TYPE % ("grad", "input", "Double", "Float", said + "_backward_cuda")
+    # a gradient of another size: the _cl adapter falls back to the plain one, which refuses it under the plain name
+    plain = "temporal_shift_learnable_per_clip" if family == "per_clip" else "temporal_shift_learnable"
+    assert _message(bwd, g[:2], w, x, 2, 0, True) == plain + " backward: grad does not match the input"
