@@ -320,8 +320,39 @@ int inplace_call(const shiftnd_problem &q, void *x, const int64_t *xs, const int
     return finish(inplace_forward(g, q.dtype, layout, x, w, wkind, wzp, fill, static_cast<hipStream_t>(stream)));
 }
 
+// ---- SHIFTND_SHIFT_DIM0 | SHIFTND_STREAM: one step of the ONLINE temporal shift (shiftnd_stream.hip).  `q`: the problem with its
+// plain dtype, p->active as the caller gave it; `flags`: the caller's dtype bits.  sizes {B, C, D, spatial...}; `state` (the entry
+// points' x) carries the slot stride in the S0 place, `frame` (their out) is read and written too, its S0 stride is not looked at.
+// Served -- both dense layouts, at most 15 slots, paddings 0 and 1 (the initial state IS the padding: no other mode can be
+// causal), the whole window -- or refused before anything is launched.
+int stream_call(const shiftnd_problem &q, int flags, void *state, const int64_t *xs, void *frame, const int64_t *os, const void *w,
+                int wkind, int64_t wzp, void *stream) {
+    if (flags & (SHIFTND_FRAMES | SHIFTND_PER_CLIP)) return SHIFTND_ERR_INVALID_ARGUMENT;
+    if (q.active || q.padding_mode > 1) return SHIFTND_ERR_INVALID_ARGUMENT;
+    Geometry g;
+    const int rc = build_geometry(&q, xs, os, nullptr, g);
+    if (rc != SHIFTND_OK) return rc;
+    if (!stream_geometry_ok(g, q.dtype)) return SHIFTND_ERR_INVALID_ARGUMENT;   // (a cut window, more than 15 slots, the sizes)
+    if (empty_problem(g)) {   // (no slots: every shift clamps to 0)
+        g_last_path = SHIFTND_PATH_EMPTY;
+        return SHIFTND_OK;
+    }
+    if (!state || !frame || !w) return SHIFTND_ERR_INVALID_ARGUMENT;
+    const int layout = stream_layout(g, q.dtype, state, g.xs, frame, g.os);
+    if (layout == 0) return SHIFTND_ERR_INVALID_ARGUMENT;
+    g_last_path = layout == 1 ? SHIFTND_PATH_PLANE : SHIFTND_PATH_CL;
+    return finish(stream_forward(g, q.dtype, layout, state, frame, w, wkind, wzp, static_cast<hipStream_t>(stream)));
+}
+
 int tshift_forward_call(const shiftnd_problem *p, const void *x, const int64_t *xs, const void *w, void *out, const int64_t *os,
                         void *stream) {
+    if (p->dtype & SHIFTND_STREAM) {   // the online step: x is the state, read AND written (the header says so)
+        shiftnd_problem r = *p, q;
+        int wkind;
+        r.dtype = p->dtype & ~(SHIFTND_SHIFT_DIM0 | SHIFTND_STREAM | SHIFTND_FRAMES | SHIFTND_PER_CLIP);
+        if (split_dtype(&r, q, wkind) != SHIFTND_OK || !is_float_dtype(q.dtype)) return SHIFTND_ERR_UNSUPPORTED_DTYPE;
+        return stream_call(q, p->dtype, const_cast<void *>(x), xs, out, os, w, wkind, 0, stream);
+    }
     if (out && out == x) {   // in place: its own kernel, or refused (SHIFTND_FRAMES asks for kernels that have no such form)
         shiftnd_problem q;
         int wkind;
@@ -544,9 +575,16 @@ int shiftnd_forward_quantized(const shiftnd_problem *p, const void *x, const int
                               int32_t wq_dtype, int64_t w_zero_point, int64_t x_zero_point, void *out,
                               const int64_t out_strides[5], void *stream) {
     if (!p || !x_strides || !out_strides) return SHIFTND_ERR_INVALID_ARGUMENT;
-    const int dtype = p->dtype & ~SHIFTND_SHIFT_DIM0;   // (the flag with a float dtype or with SHIFTND_WEIGHTS_F32: no quantized dtype)
+    // the online step (SHIFTND_STREAM beside the flag; alone it is an unknown dtype bit): SHIFTND_FRAMES / SHIFTND_PER_CLIP beside it
+    // are its own refusal, not an unknown dtype
+    const bool online = (p->dtype & SHIFTND_SHIFT_DIM0) && (p->dtype & SHIFTND_STREAM);
+    const int dtype = p->dtype & ~(online ? SHIFTND_SHIFT_DIM0 | SHIFTND_STREAM | SHIFTND_FRAMES | SHIFTND_PER_CLIP : SHIFTND_SHIFT_DIM0);   // (the flag with a float dtype or with SHIFTND_WEIGHTS_F32: no quantized dtype)
     if (!is_quant_dtype(dtype) || !is_quant_dtype(wq_dtype)) return SHIFTND_ERR_UNSUPPORTED_DTYPE;
     shiftnd_problem q = *p;
+    if (online) {   // x is the state, read AND written; the state's initial bytes are the padding, so x_zero_point is not used
+        q.dtype = dtype;
+        return stream_call(q, p->dtype, const_cast<void *>(x), x_strides, out, out_strides, wq, wq_dtype, w_zero_point, stream);
+    }
     q.active = 0;
     // fill value = input zero point, as the element type's bit pattern
     uint64_t fill = 0;
@@ -584,6 +622,7 @@ size_t shiftnd_backward_workspace_bytes(const shiftnd_problem *p) {
     // every entry point refuses the bit alone, so the answer is 0.  (The path below would not give it: it looks at the geometry and sizes
     // the families' plans whatever unknown bits the dtype carries -- 0x800 on F32 answers 512 bytes there, an answer a test pins)
     if ((p->dtype & SHIFTND_PER_CLIP) && !(p->dtype & SHIFTND_SHIFT_DIM0)) return 0;
+    if (p->dtype & SHIFTND_STREAM) return 0;   // (alone an unknown bit like the one above; beside the flag the online step: no backward, no workspace)
     if (p->dtype & SHIFTND_SHIFT_DIM0) {   // the walk's plan alone (SHIFTND_FRAMES: the channels-last walk's): no other family runs under the flag, no knob shapes it
         const int64_t unit[5] = {0, 0, 0, 0, 0};
         Geometry g;
@@ -615,6 +654,7 @@ int shiftnd_backward(const shiftnd_problem *p, const void *grad_out, const int64
                      const int64_t x_strides[5], const void *weights, void *grad_x, const int64_t grad_x_strides[5],
                      void *grad_w, void *workspace, size_t workspace_bytes, void *stream) {
     if (p && (p->dtype & SHIFTND_SHIFT_DIM0)) {
+        if (p->dtype & SHIFTND_STREAM) return SHIFTND_ERR_INVALID_ARGUMENT;   // (the online step is an inference call: no backward)
         if (!grad_out_strides || !grad_x_strides) return SHIFTND_ERR_INVALID_ARGUMENT;
         return tshift_backward_call(p, grad_out, grad_out_strides, x, x_strides, weights, grad_x, grad_x_strides, grad_w, workspace,
                                     workspace_bytes, stream);

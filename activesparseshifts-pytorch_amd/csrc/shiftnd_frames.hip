@@ -72,7 +72,7 @@ template <int UL> __device__ __forceinline__ void store_piece(char *p, shiftnd_u
 }
 
 // do table entries [e0, e0 + n) (1 <= n <= 16) hold the same bits?  Unconditional loads inside the table, issued together
-// (shiftnd_inplace.hip has its own raw_equal on purpose: a compile-time count and exactly that many loads, against 15 clamped ones here)
+// (shiftnd_temporal.hpp has raw_equal_fixed for the in-place and online kernels on purpose: a compile-time count and exactly that many loads, against 15 clamped ones here)
 template <typename R> __device__ __forceinline__ bool raw_equal(const void *w, int64_t e0, int n) {
     const R *p = static_cast<const R *>(w) + e0;
     const R first = p[0];

@@ -69,33 +69,6 @@ template <int UL> __device__ __forceinline__ void shift_line(const InplaceParams
         if (moved >> t & 1) __builtin_nontemporal_store(v[t], reinterpret_cast<piece_t *>(p + t * q.frame_bytes));
 }
 
-// do table entries [e0, e0 + N) hold the same bits?  N is a compile-time count: exactly N loads inside the table, issued together
-// (shiftnd_frames.hip has its own raw_equal on purpose: a run-time count under 15 clamped loads, against exactly N loads here)
-template <typename R, int N> __device__ __forceinline__ bool raw_equal(const void *w, int64_t e0) {
-    const R *p = static_cast<const R *>(w) + e0;
-    const R first = p[0];
-    bool same = true;
-#pragma unroll
-    for (int e = 1; e < N; ++e) same = same && p[e] == first;
-    return same;
-}
-// ... the 1 << n_log2 entries of a piece of 1 << UL bytes (n_log2 <= UL, launch-uniform: scalar branches)
-template <typename R, int UL> __device__ __forceinline__ bool raw_equal_n(const void *w, int64_t e0, int n_log2) {
-    if constexpr (UL >= 4) if (n_log2 == 4) return raw_equal<R, 16>(w, e0);
-    if constexpr (UL >= 3) if (n_log2 == 3) return raw_equal<R, 8>(w, e0);
-    if constexpr (UL >= 2) if (n_log2 == 2) return raw_equal<R, 4>(w, e0);
-    if constexpr (UL >= 1) if (n_log2 == 1) return raw_equal<R, 2>(w, e0);
-    return true;
-}
-template <int UL> __device__ __forceinline__ bool raw_entries_equal(const void *w, int wkind, int64_t e0, int n_log2) {
-    switch (wkind) {
-    case SHIFTND_F64: return raw_equal_n<uint64_t, UL>(w, e0, n_log2);
-    case SHIFTND_F32: case SHIFTND_I32: return raw_equal_n<uint32_t, UL>(w, e0, n_log2);
-    case SHIFTND_F16: case SHIFTND_BF16: return raw_equal_n<uint16_t, UL>(w, e0, n_log2);
-    default: return raw_equal_n<uint8_t, UL>(w, e0, n_log2);
-    }
-}
-
 __device__ __forceinline__ int canon_of(const InplaceParams &q, int64_t s) {
     return canon_shift(s, static_cast<int>(q.T), q.pad, q.d_per);
 }
@@ -126,7 +99,7 @@ template <int UL> __device__ __forceinline__ void inplace_body(const InplacePara
     const int epp = 1 << (UL - q.es_log2);
     const int64_t e0 = static_cast<int64_t>(kr) * epp;
     const int64_t s0 = gather_shift(w, q.wkind, q.wzp, e0);
-    bool uniform = raw_entries_equal<UL>(w, q.wkind, e0, UL - q.es_log2);
+    bool uniform = piece_entries_equal<UL>(w, q.wkind, e0, UL - q.es_log2);
     if (!uniform) {
         uniform = true;
 #pragma unroll 1

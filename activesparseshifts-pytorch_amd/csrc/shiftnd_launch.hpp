@@ -259,6 +259,18 @@ int inplace_layout(const Geometry &g, int dtype, const void *p, const int64_t *s
 int inplace_forward(const Geometry &g, int dtype, int layout, void *x, const void *w, int wkind, int64_t wzp, uint64_t fill_bits,
                     hipStream_t st);
 
+// ---- the ONLINE temporal shift (shiftnd_stream.hip; SHIFTND_SHIFT_DIM0 | SHIFTND_STREAM): one step of a frame [N, C, S1, S2]
+// against a state of S0 <= 15 slots, float and quantized (I8, U8, I32) tensors in either dense layout, `w` a [C] table of shifts
+// clamped into [0, S0]; only the bytes of shifted channels are read or written, in the frame and in the state.
+// stream_geometry_ok: the sizes (inplace_geometry_ok's, S0 <= 15); stream_layout: 1 for a dense contiguous frame and state, 2 for
+// dense channels-last ones, 0 for anything else and for a frame that overlaps the state (normalised strides; the frame's S0 stride
+// is not looked at).
+bool stream_geometry_ok(const Geometry &g, int dtype);
+int stream_layout(const Geometry &g, int dtype, const void *state, const int64_t *state_strides, const void *frame,
+                  const int64_t *frame_strides);
+int stream_forward(const Geometry &g, int dtype, int layout, void *state, void *frame, const void *w, int wkind, int64_t wzp,
+                   hipStream_t st);
+
 // ---- layout change (shiftnd_transpose.hip): dst[n][c][r] = src[n][r][c], dense tensors ---------------------------
 int transpose_planes(const void *src, void *dst, int64_t N, int64_t rows, int64_t cols, int esize, hipStream_t st);
 

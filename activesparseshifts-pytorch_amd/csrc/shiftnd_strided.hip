@@ -59,16 +59,20 @@ __device__ __forceinline__ int64_t resolve(const int64_t idx[3], const int64_t s
     return off;
 }
 
-// SSL / quantized forward: pure gather of ESIZE-byte elements ------------------------------------
+// SSL / quantized forward: pure gather of elements of 1 << es_log2 bytes ---------------------------
+// ONE kernel for the four element sizes (es_log2 is launch-uniform: a scalar branch around the load and the store; the index
+// arithmetic, which is what this kernel spends its time on, is shared).  A pure copy, so the element type is its size alone.
 template <int ESIZE>
+__device__ __forceinline__ void gather_element(const void *x_, int64_t src, uint64_t fill_bits, void *out_, int64_t dst) {
+    using R = typename raw_t<ESIZE>::type;
+    const R v = src >= 0 ? static_cast<const R *>(x_)[src] : static_cast<R>(fill_bits);
+    static_cast<R *>(out_)[dst] = v;
+}
+
 __global__ __launch_bounds__(kThreads) void strided_gather_forward(Geometry g, const void *__restrict__ x_,
                                                                     const void *__restrict__ w, int wkind, int64_t wzp,
                                                                     uint64_t fill_bits, void *__restrict__ out_,
-                                                                    int64_t total) {
-    using R = typename raw_t<ESIZE>::type;
-    const R *x = static_cast<const R *>(x_);
-    R *out = static_cast<R *>(out_);
-    const R fill = static_cast<R>(fill_bits);
+                                                                    int64_t total, int es_log2) {
     const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
     for (int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; e < total; e += stride) {
         int64_t r = e;
@@ -85,8 +89,14 @@ __global__ __launch_bounds__(kThreads) void strided_gather_forward(Geometry g, c
             idx[d] = o[d] + g.L[d] - sh;
         }
         const int64_t off = resolve(idx, g.S, g.xs + 2, g.pad);
-        const R v = off >= 0 ? x[n * g.xs[0] + c * g.xs[1] + off] : fill;
-        out[n * g.os[0] + c * g.os[1] + o0 * g.os[2] + o1 * g.os[3] + o2 * g.os[4]] = v;
+        const int64_t src = off >= 0 ? n * g.xs[0] + c * g.xs[1] + off : -1;
+        const int64_t dst = n * g.os[0] + c * g.os[1] + o0 * g.os[2] + o1 * g.os[3] + o2 * g.os[4];
+        switch (es_log2) {
+        case 0: gather_element<1>(x_, src, fill_bits, out_, dst); break;
+        case 1: gather_element<2>(x_, src, fill_bits, out_, dst); break;
+        case 2: gather_element<4>(x_, src, fill_bits, out_, dst); break;
+        default: gather_element<8>(x_, src, fill_bits, out_, dst); break;
+        }
     }
 }
 
@@ -286,24 +296,9 @@ int strided_forward(const Geometry &g, int dtype, const void *x, const void *w, 
     const bool gather_only = !g.active || dtype >= SHIFTND_I8;
     note_kernel(gather_only ? "strided_gather_forward" : "strided_active_forward");
     if (gather_only) {
-        switch (dtype_size(dtype)) {
-        case 1:
-            hipLaunchKernelGGL((strided_gather_forward<1>), dim3(grid), dim3(kThreads), 0, st, g, x, w, wkind, wzp,
-                               fill_bits, out, total);
-            break;
-        case 2:
-            hipLaunchKernelGGL((strided_gather_forward<2>), dim3(grid), dim3(kThreads), 0, st, g, x, w, wkind, wzp,
-                               fill_bits, out, total);
-            break;
-        case 4:
-            hipLaunchKernelGGL((strided_gather_forward<4>), dim3(grid), dim3(kThreads), 0, st, g, x, w, wkind, wzp,
-                               fill_bits, out, total);
-            break;
-        default:
-            hipLaunchKernelGGL((strided_gather_forward<8>), dim3(grid), dim3(kThreads), 0, st, g, x, w, wkind, wzp,
-                               fill_bits, out, total);
-            break;
-        }
+        const int es = dtype_size(dtype);
+        hipLaunchKernelGGL(strided_gather_forward, dim3(grid), dim3(kThreads), 0, st, g, x, w, wkind, wzp, fill_bits, out, total,
+                           es == 8 ? 3 : (es == 4 ? 2 : (es == 2 ? 1 : 0)));
         return SHIFTND_OK;
     }
     switch (dtype) {

@@ -1,5 +1,5 @@
-// shiftnd_temporal.hpp -- what the five files of the temporal-shift family share (shiftnd_segment.hip, shiftnd_tshift.hip,
-// shiftnd_frames.hip, shiftnd_frames_learn.hip, shiftnd_inplace.hip): one definition each.  Internal.
+// shiftnd_temporal.hpp -- what the six files of the temporal-shift family share (shiftnd_segment.hip, shiftnd_tshift.hip,
+// shiftnd_frames.hip, shiftnd_frames_learn.hip, shiftnd_inplace.hip, shiftnd_stream.hip): one definition each.  Internal.
 #pragma once
 
 #include <initializer_list>
@@ -54,6 +54,33 @@ template <> struct piece_of<3> { typedef uint32_t type __attribute__((ext_vector
 template <> struct piece_of<2> { typedef uint32_t type; };
 template <> struct piece_of<1> { typedef uint16_t type; };
 template <> struct piece_of<0> { typedef uint8_t type; };
+
+// do table entries [e0, e0 + N) hold the same bits?  N is a compile-time count: exactly N loads inside the table, issued together
+// (shiftnd_frames.hip has its own raw_equal on purpose: a run-time count under 15 clamped loads, against exactly N loads here)
+template <typename R, int N> __device__ __forceinline__ bool raw_equal_fixed(const void *w, int64_t e0) {
+    const R *p = static_cast<const R *>(w) + e0;
+    const R first = p[0];
+    bool same = true;
+#pragma unroll
+    for (int e = 1; e < N; ++e) same = same && p[e] == first;
+    return same;
+}
+// ... the 1 << n_log2 entries of a piece of 1 << UL bytes (n_log2 <= UL, launch-uniform: scalar branches)
+template <typename R, int UL> __device__ __forceinline__ bool raw_equal_pow2(const void *w, int64_t e0, int n_log2) {
+    if constexpr (UL >= 4) if (n_log2 == 4) return raw_equal_fixed<R, 16>(w, e0);
+    if constexpr (UL >= 3) if (n_log2 == 3) return raw_equal_fixed<R, 8>(w, e0);
+    if constexpr (UL >= 2) if (n_log2 == 2) return raw_equal_fixed<R, 4>(w, e0);
+    if constexpr (UL >= 1) if (n_log2 == 1) return raw_equal_fixed<R, 2>(w, e0);
+    return true;
+}
+template <int UL> __device__ __forceinline__ bool piece_entries_equal(const void *w, int wkind, int64_t e0, int n_log2) {
+    switch (wkind) {
+    case SHIFTND_F64: return raw_equal_pow2<uint64_t, UL>(w, e0, n_log2);
+    case SHIFTND_F32: case SHIFTND_I32: return raw_equal_pow2<uint32_t, UL>(w, e0, n_log2);
+    case SHIFTND_F16: case SHIFTND_BF16: return raw_equal_pow2<uint16_t, UL>(w, e0, n_log2);
+    default: return raw_equal_pow2<uint8_t, UL>(w, e0, n_log2);
+    }
+}
 
 // bytes [0, n) of a dword (n clamped to 0..4)
 __device__ __forceinline__ uint32_t low_bytes(int n) { return n <= 0 ? 0u : (n >= 4 ? ~0u : (1u << (8 * n)) - 1u); }

@@ -18,7 +18,9 @@
 //   per clip      torchshifts_per_clip::temporal_shift_learnable_per_clip / _forward / _backward, temporal_shift_per_clip /
 //                 _temporal_shift_per_clip_backward: the temporal shifts under a [N, C] table, one row per clip
 //   in place      torchshifts_inplace::temporal_shift_ / temporal_shift_quantized_: the temporal shift written into the input (composes
-//                 on CPU tensors), the one family that writes its argument
+//                 on CPU tensors), a family that writes its argument
+//   online        torchshifts_online::temporal_shift_online_ / temporal_shift_online_quantized_: one frame per call against a cached
+//                 state of the previous frames, both written (composes on CPU tensors); inference only, no Autograd key
 //
 // Keys: the Autograd, CUDA and QuantizedCUDA kernels of every family are registered here.  The CPU / QuantizedCPU kernels that
 // compute (shift, fixed, fixed pool, temporal, temporal_shift_quantized) live in torch_cpu_backend.cpp; the ones that compose other
@@ -1590,6 +1592,175 @@ Tensor &temporal_quantized_inplace_hip(Tensor &input, const Tensor &shifts, int6
     return input;
 }
 
+// ---- online temporal shift: torchshifts_online::temporal_shift_online_ / temporal_shift_online_quantized_ --------------------------
+// One step of the uni-directional TSM on a frame batch [B, C, ...] against a state [D, B, C, ...] whose slot k holds frame t-1-k
+// (include/shiftnd_hip.h, SHIFTND_STREAM): for a channel with shift s in 1..D the frame shows slot s-1, the slots move one place on
+// and slot 0 takes the incoming frame.  Both tensors are written; the frame is returned.  An inference op: there is no autograd
+// formula and a tensor that requires grad raises.  On HIP tensors a dense frame (contiguous or channels-last,
+// is_channels_last_dense) with a state of 1..kOnlineSlots slots in the same layout is ONE flagged C-ABI call (shiftnd_stream.hip),
+// with no host synchronisation, so a step can be captured in a graph; a table that already has the kernel's kind -- fp32 for 16-bit
+// tensors, the tensor's dtype for fp32 / fp64, int32 for quantized tensors -- is passed as it is, with no allocation (the modules
+// keep such a table), any other table is converted first.  Every other input -- CPU tensors, more slots, views that are not dense --
+// runs the composite below on index_select / index_copy_: the same values.  The composite reads the table on the host, and it alone
+// can refuse a negative entry; the kernel clamps (torchshifts.functional.temporal_shift_online_state validates a table once).
+constexpr int64_t kOnlineSlots = 15;   // (the slots beside the frame in frames_stream's 16 registers: include/shiftnd_hip.h)
+
+// bytes [first, last) a strided tensor can touch, relative to its storage
+std::pair<int64_t, int64_t> byte_extent(const Tensor &t) {
+    int64_t last = t.storage_offset();
+    for (int64_t d = 0; d < t.dim(); ++d) last += (t.size(d) - 1) * t.stride(d);
+    return {t.storage_offset() * static_cast<int64_t>(t.element_size()), (last + 1) * static_cast<int64_t>(t.element_size())};
+}
+
+void online_check(const char *op_name, const Tensor &input, const Tensor &state, const Tensor &shifts) {
+    TORCH_CHECK(input.dim() >= 2 && input.dim() <= 5, op_name, ": expected a [B, C, ...] frame of 2 to 5 dims");
+    TORCH_CHECK(state.dim() == input.dim() + 1 && state.sizes().slice(1) == input.sizes(), op_name, ": state must have shape [D, ",
+                input.sizes(), "], one slot per cached frame, but its shape is ", state.sizes());
+    TORCH_CHECK(state.scalar_type() == input.scalar_type(), op_name, ": state must have the input's dtype (", c10::toString(input.scalar_type()),
+                "), but it is ", c10::toString(state.scalar_type()));
+    TORCH_CHECK(state.device() == input.device(), op_name, ": state must be on the input's device");
+    TORCH_CHECK(shifts.dim() == 1 && shifts.size(0) == input.size(1), op_name, ": shifts must have shape [C]");
+    TORCH_CHECK(shifts.device() == input.device(), op_name, ": shifts must be on the input's device");
+    TORCH_CHECK(!shifts.is_quantized() && is_integer_or_float(shifts), op_name, ": shifts must be integers or floats");
+    TORCH_CHECK(!input.requires_grad() && !state.requires_grad() && !shifts.requires_grad(), op_name,
+                ": an inference op without an autograd formula, but an argument requires grad");
+    if (input.numel() > 0 && state.numel() > 0 && input.storage().is_alias_of(state.storage())) {
+        const auto a = byte_extent(input), b = byte_extent(state);
+        TORCH_CHECK(a.second <= b.first || b.second <= a.first, op_name, ": input and state overlap in memory");
+    }
+}
+
+void online_float_check(const Tensor &input, const Tensor &state, const Tensor &shifts) {
+    TORCH_CHECK(!input.is_quantized() && !state.is_quantized(), "temporal_shift_online_: quantized tensors are not supported");
+    online_check("temporal_shift_online_", input, state, shifts);
+}
+
+void online_quantized_check(const Tensor &input, const Tensor &state, const Tensor &shifts) {
+    const char *op_name = "temporal_shift_online_quantized_";
+    TORCH_CHECK(input.is_quantized(), op_name, ": expected a quantized input");
+    TORCH_CHECK(input.qscheme() == at::kPerTensorAffine, op_name, ": expected a per-tensor quantized input");
+    TORCH_CHECK(state.is_quantized() && state.qscheme() == at::kPerTensorAffine, op_name, ": expected a per-tensor quantized state");
+    online_check(op_name, input, state, shifts);
+    TORCH_CHECK(state.q_scale() == input.q_scale() && state.q_zero_point() == input.q_zero_point(), op_name,
+                ": state must have the input's scale and zero point (", input.q_scale(), ", ", input.q_zero_point(), "), but it has (",
+                state.q_scale(), ", ", state.q_zero_point(), ")");
+}
+
+// both tensors are written below every autograd key: the version counters are bumped here
+void online_bump(Tensor &input, Tensor &state) {
+    input.unsafeGetTensorImpl()->bump_version();
+    state.unsafeGetTensorImpl()->bump_version();
+}
+
+// the step on plain tensors of any strides, one group of channels per shift value.  Reads the table on the host
+void online_composite(const char *op_name, Tensor input, Tensor state, const Tensor &shifts) {
+    const int64_t D = state.size(0);
+    if (D == 0 || input.numel() == 0) return;
+    const Tensor s = (at::isFloatingType(shifts.scalar_type()) ? at::round(shifts.detach()) : shifts.detach()).to(at::kLong);
+    TORCH_CHECK(s.numel() == 0 || s.min().item<int64_t>() >= 0, op_name, ": a negative shift reads the future; an online table is causal (every entry >= 0)");
+    const Tensor clamped = s.clamp_max(D);
+    for (int64_t v = 1; v <= D; ++v) {
+        const Tensor idx = at::nonzero(clamped == v).reshape({-1});
+        if (idx.numel() == 0) continue;
+        const Tensor shown = state.select(0, v - 1).index_select(1, idx);
+        for (int64_t k = v - 1; k >= 1; --k) state.select(0, k).index_copy_(1, idx, state.select(0, k - 1).index_select(1, idx));
+        state.select(0, 0).index_copy_(1, idx, input.index_select(1, idx));
+        input.index_copy_(1, idx, shown);
+    }
+}
+
+Tensor &online_cpu(Tensor &input, Tensor &state, const Tensor &shifts) {
+    online_float_check(input, state, shifts);
+    at::AutoDispatchBelowADInplaceOrView guard;
+    online_bump(input, state);
+    online_composite("temporal_shift_online_", input, state, shifts);
+    return input;
+}
+
+Tensor &online_quantized_composite(Tensor &input, Tensor &state, const Tensor &shifts) {
+    online_composite("temporal_shift_online_quantized_", int_repr_alias(input), int_repr_alias(state), shifts);
+    return input;
+}
+
+Tensor &online_quantized_cpu(Tensor &input, Tensor &state, const Tensor &shifts) {
+    online_quantized_check(input, state, shifts);
+    at::AutoDispatchBelowADInplaceOrView guard;
+    online_bump(input, state);
+    return online_quantized_composite(input, state, shifts);
+}
+
+// served as they lie: a dense frame, 1..kOnlineSlots slots with the frame's own strides, one frame batch apart
+bool online_served(const Tensor &input, const Tensor &state) {
+    const int64_t D = state.size(0);
+    if (D < 1 || D > kOnlineSlots || input.numel() == 0 || !(input.is_contiguous() || is_channels_last_dense(input))) return false;
+    return state.strides().slice(1) == input.strides() && (D == 1 || state.stride(0) == input.numel());
+}
+
+// the writer of the online problem: {B, C, D, M} with the slot stride in the S0 place of the state's strides `ss`; `fs`: the frame's
+void online_problem(shiftnd_problem &p, int64_t ss[5], int64_t fs[5], const Tensor &input, int64_t D, int dtype_bits, const char *who) {
+    const int64_t B = input.size(0), C = input.size(1), M = input.numel() / (B * C);
+    TORCH_CHECK(M <= INT32_MAX, who, ": the frame size must fit 32 bits");
+    const bool channels_last = !input.is_contiguous();
+    p.ndim = 2;
+    p.dtype = dtype_bits | SHIFTND_SHIFT_DIM0 | SHIFTND_STREAM;
+    p.padding_mode = 0;
+    p.active = 0;
+    const int64_t sizes[5] = {B, C, D, M, 1};
+    const int64_t contiguous[5] = {C * M, M, B * C * M, 1, 0}, nhwc[5] = {M * C, 1, B * M * C, C, 0};
+    const int32_t borders[6] = {0, static_cast<int32_t>(D), 0, static_cast<int32_t>(M), 0, 1};
+    for (int i = 0; i < 5; ++i) p.sizes[i] = sizes[i], ss[i] = fs[i] = channels_last ? nhwc[i] : contiguous[i];
+    fs[2] = 0;
+    for (int i = 0; i < 6; ++i) p.borders[i] = borders[i];
+}
+
+// the [C] table in the kind the kernel reads; a table that has it already is passed as it is
+Tensor online_table(const Tensor &shifts, at::ScalarType kind) {
+    if (shifts.scalar_type() == kind && shifts.is_contiguous()) return shifts;
+    const Tensor s = shifts.detach();
+    return (at::isIntegralType(kind, false) && at::isFloatingType(s.scalar_type()) ? at::round(s) : s).to(kind).contiguous();
+}
+
+Tensor &online_hip(Tensor &input, Tensor &state, const Tensor &shifts) {
+    TORCH_CHECK(input.is_cuda(), "temporal_shift_online_: expected a CUDA tensor");
+    online_float_check(input, state, shifts);
+    if (input.numel() == 0 || state.size(0) == 0) return input;
+    at::AutoDispatchBelowADInplaceOrView guard;
+    online_bump(input, state);
+    c10::DeviceGuard device_guard(input.device());
+    if (!online_served(input, state)) {
+        online_composite("temporal_shift_online_", input, state, shifts);
+        return input;
+    }
+    const bool half = input.scalar_type() == at::kHalf || input.scalar_type() == at::kBFloat16;
+    const int dtype = to_shiftnd_dtype(input.scalar_type(), "temporal_shift_online__cuda") | (half ? SHIFTND_WEIGHTS_F32 : 0);
+    const Tensor w = online_table(shifts, half ? at::kFloat : input.scalar_type());
+    shiftnd_problem p;
+    int64_t ss[5], fs[5];
+    online_problem(p, ss, fs, input, state.size(0), dtype, "temporal_shift_online_");
+    check_status(shiftnd_forward(&p, state.data_ptr(), ss, w.data_ptr(), input.data_ptr(), fs, current_stream(input)),
+                 "temporal_shift_online_ (HIP)");
+    return input;
+}
+
+Tensor &online_quantized_hip(Tensor &input, Tensor &state, const Tensor &shifts) {
+    TORCH_CHECK(input.is_cuda(), "temporal_shift_online_quantized_: expected a CUDA tensor");
+    online_quantized_check(input, state, shifts);
+    if (input.numel() == 0 || state.size(0) == 0) return input;
+    at::AutoDispatchBelowADInplaceOrView guard;
+    online_bump(input, state);
+    c10::DeviceGuard device_guard(input.device());
+    if (!online_served(input, state)) return online_quantized_composite(input, state, shifts);
+    const int dtype = quant_dtype(input.scalar_type(), "temporal_shift_online_quantized__cuda");
+    const Tensor w = online_table(shifts, at::kInt);
+    shiftnd_problem p;
+    int64_t ss[5], fs[5];
+    online_problem(p, ss, fs, input, state.size(0), dtype, "temporal_shift_online_quantized_");
+    check_status(shiftnd_forward_quantized(&p, state.data_ptr(), ss, w.data_ptr(), SHIFTND_I32, 0, input.q_zero_point(), input.data_ptr(), fs,
+                                           current_stream(input)),
+                 "temporal_shift_online_quantized_ (HIP)");
+    return input;
+}
+
 int64_t cuda_version() { return -1; }  // no CUDA toolkit: extension.py only compares when torch.version.cuda is set
 int64_t hip_version() { return HIP_VERSION; }
 
@@ -1787,3 +1958,14 @@ TORCH_LIBRARY_IMPL(torchshifts_inplace, CPU, m) { m.impl("temporal_shift_", TORC
 TORCH_LIBRARY_IMPL(torchshifts_inplace, CUDA, m) { m.impl("temporal_shift_", TORCH_FN(temporal_inplace_hip)); }
 TORCH_LIBRARY_IMPL(torchshifts_inplace, QuantizedCPU, m) { m.impl("temporal_shift_quantized_", TORCH_FN(temporal_quantized_inplace_cpu)); }
 TORCH_LIBRARY_IMPL(torchshifts_inplace, QuantizedCUDA, m) { m.impl("temporal_shift_quantized_", TORCH_FN(temporal_quantized_inplace_hip)); }
+
+// the online temporal shift: its own namespace (the op sets of the three above are pinned).  No Autograd key: an inference op
+TORCH_LIBRARY(torchshifts_online, m) {
+    m.def("torchshifts_online::temporal_shift_online_(Tensor(a!) input, Tensor(b!) state, Tensor shifts) -> Tensor(a!)");
+    m.def("torchshifts_online::temporal_shift_online_quantized_(Tensor(a!) input, Tensor(b!) state, Tensor shifts) -> Tensor(a!)");
+}
+
+TORCH_LIBRARY_IMPL(torchshifts_online, CPU, m) { m.impl("temporal_shift_online_", TORCH_FN(online_cpu)); }
+TORCH_LIBRARY_IMPL(torchshifts_online, CUDA, m) { m.impl("temporal_shift_online_", TORCH_FN(online_hip)); }
+TORCH_LIBRARY_IMPL(torchshifts_online, QuantizedCPU, m) { m.impl("temporal_shift_online_quantized_", TORCH_FN(online_quantized_cpu)); }
+TORCH_LIBRARY_IMPL(torchshifts_online, QuantizedCUDA, m) { m.impl("temporal_shift_online_quantized_", TORCH_FN(online_quantized_hip)); }

@@ -21,6 +21,8 @@ FRAMES = 0x400        # SHIFTND_FRAMES: with SHIFT_DIM0 -- every tensor is dense
 #                       frame kernels serve forward (both modes) and backward, or the call is refused
 PER_CLIP = 0x1000     # SHIFTND_PER_CLIP: with SHIFT_DIM0 -- weights / grad_w are [N, C], one row per clip; segment-major tensors, the tshift
 #                       kernels, forward (both modes) and backward (0x800 is not assigned)
+STREAM = 0x2000       # SHIFTND_STREAM: with SHIFT_DIM0 -- one step of the online temporal shift: sizes {B, C, D, spatial...}, x the state
+#                       (read and written, the slot stride in the S0 place), out the frame (read and written), w the [C] table
 PATH_NONE, PATH_EMPTY, PATH_PLANE, PATH_STRIDED, PATH_SWEEP, PATH_CL = range(6)
 
 DTYPES = {torch.float32: F32, torch.float64: F64, torch.float16: F16, torch.bfloat16: BF16,
@@ -133,12 +135,13 @@ def check_borders(sizes, user, ndim):
     return list(out), list(new)[:shift + min(ndim, 3)]
 
 
-def problem(x, pad, active, borders, dtype=None, w=None, shift_dim0=False, frames=False, per_clip=False):
+def problem(x, pad, active, borders, dtype=None, w=None, shift_dim0=False, frames=False, per_clip=False, stream=False):
     """w: the weights of the call, if it has float weights -- fp32 weights with an fp16 / bf16 `x` set WEIGHTS_F32 (mixed precision);
     shift_dim0: set SHIFT_DIM0 (the temporal shift: w is [C] and acts on spatial dim 0; x a segment-major view, or, for the
     sparse forward and the quantized forward, a dense channels-last view [N, C, T, M] with strides {T*M*C, 1, M*C, C});
     frames: set FRAMES (with shift_dim0: every tensor is such a dense channels-last view, forward in both modes and backward);
-    per_clip: set PER_CLIP (with shift_dim0: w is [N, C], one row per clip, x a segment-major view)"""
+    per_clip: set PER_CLIP (with shift_dim0: w is [N, C], one row per clip, x a segment-major view);
+    stream: set STREAM (with shift_dim0: x is the state viewed as [B, C, D, M], see online_views)"""
     p = Problem()
     p.ndim = x.dim() - 2
     p.dtype = DTYPES[x.dtype] if dtype is None else dtype
@@ -150,6 +153,8 @@ def problem(x, pad, active, borders, dtype=None, w=None, shift_dim0=False, frame
         p.dtype |= FRAMES
     if per_clip:
         p.dtype |= PER_CLIP
+    if stream:
+        p.dtype |= STREAM
     p.padding_mode = int(pad)
     p.active = int(bool(active))
     for i in range(5):
@@ -236,6 +241,37 @@ def forward_quantized(xq, wq, w_zero_point, x_zero_point, pad, borders=None, out
                                           int(w_zero_point), int(x_zero_point), out.data_ptr(), strides5(out), _stream()),
           "shiftnd_forward_quantized")
     return out
+
+
+def online_views(frame, state):
+    """the [B, C, D, M] problem view of a state [D, B, C, *spatial] and the [B, C, 1, M] view of its frame [B, C, *spatial], both
+    dense in one layout (contiguous, or channels-last: unit channel stride)"""
+    B, C = frame.shape[:2]
+    M = frame[0, 0].numel()
+    D = state.shape[0]
+    if frame.is_contiguous():
+        return state.view(D, B, C, M).permute(1, 2, 0, 3), frame.view(B, C, 1, M)
+    order = [0] + list(range(2, frame.dim())) + [1]   # memory order B, spatial, C
+    f = frame.permute(order).reshape(B, 1, M, C).permute(0, 3, 1, 2)
+    s = state.permute([0] + [1 + d for d in order]).reshape(D, B, M, C).permute(1, 3, 0, 2)
+    assert f.data_ptr() == frame.data_ptr() and s.data_ptr() == state.data_ptr()
+    return s, f
+
+
+def online_step(frame, state, w, w_zero_point=0, pad=0):
+    """One step of the online temporal shift in place on `frame` [B, C, *spatial] and `state` [D, B, C, *spatial] (device tensors,
+    dense in one layout): the flagged call on their problem views.  w: the [C] table -- x's dtype, or fp32 with an fp16 / bf16
+    frame; an int8 / uint8 / int32 table with an int8 / uint8 / int32 frame (the quantized entry point)."""
+    s, f = online_views(frame, state)
+    p = problem(s, pad, False, None, w=w if w.is_floating_point() else None, shift_dim0=True, stream=True)
+    w = w.contiguous()
+    if w.is_floating_point():
+        check(lib().shiftnd_forward(ctypes.byref(p), s.data_ptr(), strides5(s), w.data_ptr(), f.data_ptr(), strides5(f), _stream()),
+              "shiftnd_forward (online)")
+    else:
+        check(lib().shiftnd_forward_quantized(ctypes.byref(p), s.data_ptr(), strides5(s), w.data_ptr(), DTYPES[w.dtype], int(w_zero_point),
+                                              0, f.data_ptr(), strides5(f), _stream()), "shiftnd_forward_quantized (online)")
+    return frame
 
 
 def _pool_arg(pool, nd):

@@ -305,3 +305,103 @@ def temporal_shift_learnable_per_clip_func(input: Tensor, weights: Tensor, n_seg
     assert weights.is_floating_point(), f"{name}: expected float weights, but they are {weights.dtype}"
     weights = _per_clip_table(name, input, weights, n_segment, padding_mode, "weights")
     return torch.ops.torchshifts_per_clip.temporal_shift_learnable_per_clip(input, weights, n_segment, padding_mode, bool(active_flag))
+
+
+# ---- online temporal shift: one frame per call against a cached state (the uni-directional TSM, arXiv 1811.08383 section 4.2) ------
+# Frames of B independent streams arrive one at a time as [B, C, ...]; the channels that shift are taken from a state of the previous
+# frames.  Sign convention of temporal_shift_func: out[t] = x[t - shifts[c]], so an online table is CAUSAL, every entry >= 0, and the
+# state has D = max(shifts) slots of the frame's shape and layout, state[k] holding frame t-1-k.  One step, for every channel c with
+# s = shifts[c] > 0:
+#   out[:, c] = state[s-1][:, c];   state[k][:, c] = state[k-1][:, c] for k = s-1 .. 1;   state[0][:, c] = x[:, c]
+# Channels with shift 0 are neither read nor written, in the frame or in the state.  Feeding the T frames of a clip-major
+# [B * T, C, ...] tensor one at a time gives, stacked, temporal_shift_func(X, shifts, T, padding_mode) bit for bit: a state of zeros
+# (the zero point of a quantized tensor) is padding_mode 0, a state whose every slot holds the first frame is padding_mode 1
+# (border).  Periodic, reflect and symmetric padding look into the future and are refused.
+# On HIP tensors a dense frame (contiguous, or dense channels-last as for temporal_shift_func) with D <= 15 is ONE kernel over the
+# shifted channels alone -- under the default table an eighth of the frame -- with no host synchronisation, so a step can be captured
+# in a torch.cuda.graph; with a table of the kernel's kind (float32 for 16-bit tensors, the tensor's dtype for float32 / float64,
+# int32 for quantized tensors; OnlineTemporalShift keeps one) nothing is allocated either, any other table is converted per call.
+# Every other input (CPU tensors, D > 15, views that are not dense) runs a composite of index_select / index_copy_ with the same
+# values; the composite reads the table on the host.  Inference only: a tensor that requires grad raises.
+def _online_checks(name: str, input: Tensor, shifts: Tensor):
+    _assert_has_ops()
+    assert 2 <= len(input.shape) <= 5, f"{name}: expected a 2D to 5D tensor [B, C, ...] as input, but it is shape is {input.shape}"
+    assert len(shifts.shape) == 1 and input.shape[1] == shifts.shape[0], \
+        f"{name}: expected [{input.shape[1]}] tensor as shifts, but it is shape is {shifts.shape}"
+    assert input.device == shifts.device, \
+        (f"{name}: expected input and shifts to be on same device, but input is  on {input.device} "
+         f"and shifts is on {shifts.device}")
+
+
+def temporal_shift_online_table(input: Tensor, shifts: Tensor) -> Tensor:
+    """`shifts` in the kind the HIP kernel reads for `input`: a step given this table allocates nothing."""
+    if input.is_quantized:
+        kind = torch.int32
+    else:
+        kind = torch.float32 if input.dtype in (torch.float16, torch.bfloat16) else input.dtype
+    s = shifts.detach()
+    if kind == torch.int32 and s.is_floating_point():
+        s = torch.round(s)
+    return s.to(kind).contiguous()
+
+
+def temporal_shift_online_state(input: Tensor, shifts: Tensor, padding_mode: int = 0) -> Tensor:
+    """The initial state [D, B, C, ...] for frames like `input` under the causal table `shifts`, D = max(shifts), in the input's
+    layout: zeros (the zero point) for padding_mode 0, the input's own values in every slot for padding_mode 1 (pass the FIRST
+    frame).  Validates the table -- integers, all >= 0 -- with the one host synchronisation of the feature."""
+    name = "temporal_shift_online_state()"
+    _online_checks(name, input, shifts)
+    if padding_mode not in (0, 1):
+        raise ValueError(f"{name}: padding_mode must be 0 (zeros) or 1 (border); periodic, reflect and symmetric padding look into "
+                         f"the future, and it is {padding_mode}")
+    s = shifts.detach()
+    if s.is_floating_point():
+        if not bool((s == torch.round(s)).all()):
+            raise ValueError(f"{name}: shifts must hold integers")
+    elif s.dtype == torch.bool or s.is_complex():
+        raise ValueError(f"{name}: shifts must hold integers")
+    low, high = (int(s.min()), int(s.max())) if s.numel() else (0, 0)
+    if low < 0:
+        raise ValueError(f"{name}: a negative shift ({low}) reads the future; an online table is causal (every entry >= 0)")
+    # the buffer in memory order, a view of it in the input's layout (contiguous, or dense channels-last in every slot, the slots one
+    # frame batch apart); a quantized state wraps the same bytes (the wrapper makes a contiguous copy, so the view is taken last)
+    shape = (high,) + tuple(input.shape)
+    plain = input.int_repr() if input.is_quantized else input.detach()
+    memory = torch.empty(shape, dtype=plain.dtype, device=plain.device)
+
+    def lay(t):
+        dense = input.numel() > 0 and (input.is_contiguous() or _is_channels_last_dense(input))
+        return t.as_strided(shape, (input.numel(),) + tuple(input.stride())) if high and dense else t
+
+    if padding_mode == 1:
+        lay(memory).copy_(plain.unsqueeze(0).expand(shape))
+    else:
+        memory.fill_(input.q_zero_point() if input.is_quantized else 0)
+    if input.is_quantized:
+        memory = torch._make_per_tensor_quantized_tensor(memory, input.q_scale(), input.q_zero_point())
+    return lay(memory)
+
+
+def _is_channels_last_dense(t: Tensor) -> bool:
+    if t.dim() < 3 or t.numel() == 0 or t.shape[1] < 2 or t.is_contiguous() or t.stride(1) != 1:
+        return False
+    expect = t.shape[1]
+    for d in range(t.dim() - 1, 1, -1):
+        if t.shape[d] != 1 and t.stride(d) != expect:
+            return False
+        expect *= t.shape[d]
+    return t.shape[0] == 1 or t.stride(0) == expect
+
+
+def temporal_shift_online_func_(input: Tensor, state: Tensor, shifts: Tensor) -> Tensor:
+    """One online step in place on both tensors: `input` [B, C, ...] becomes the shifted frame and is returned, `state`
+    [D, B, C, ...] (temporal_shift_online_state) takes the incoming frame's shifted channels."""
+    name = "temporal_shift_online_func_()"
+    _online_checks(name, input, shifts)
+    assert not input.is_quantized, f"{name}: quantized inputs go through torchshifts.quantized.functional.temporal_shift_online_quantized_"
+    return torch.ops.torchshifts_online.temporal_shift_online_(input, state, shifts)
+
+
+def temporal_shift_online_func(input: Tensor, state: Tensor, shifts: Tensor) -> Tensor:
+    """temporal_shift_online_func_ on input.clone(): the input is left as it was, the state is still updated."""
+    return temporal_shift_online_func_(input.clone(memory_format=torch.preserve_format), state, shifts)

@@ -15,7 +15,8 @@ from torchshifts.functional import (shift1d_fixed_func, shift1d_fixed_pool_func,
                                     shift2d_fixed_pool_func, shift2d_func, shift2d_pool_func, shift3d_fixed_func,
                                     shift3d_fixed_pool_func, shift3d_func, shift3d_pool_func, temporal_shift_func, temporal_shift_func_,
                                     temporal_shift_learnable_func, temporal_shift_learnable_per_clip_func,
-                                    temporal_shift_per_clip_func)
+                                    temporal_shift_online_func, temporal_shift_online_func_, temporal_shift_online_state,
+                                    temporal_shift_online_table, temporal_shift_per_clip_func)
 
 paddings_dict = {'zeros': 0, 'border': 1, 'periodic': 2, 'reflect': 3, 'symmetric': 4}
 
@@ -359,6 +360,96 @@ class TemporalShift(nn.Module):
         pad = {v: k for k, v in paddings_dict.items()}[self.padding]
         return (f'n_segment={self.n_segment}, in_channels={self.in_channels}, fold_div={self.fold_div}, padding_method={pad}, '
                 f'memory_format={self.memory_format}, fixed integer shifts' + (', inplace=True' if self.inplace else ''))
+
+
+class OnlineTemporalShift(nn.Module):
+    """Online Temporal Shift Module (the uni-directional TSM of arXiv 1811.08383, section 4.2): frames of B independent streams
+    arrive one at a time as [B, C, ...], and the channels that shift are taken from a cache of the previous frames.  The table is the
+    persistent buffer `shifts` (int64 [in_channels], every entry >= 0): channel c of the frame at time t shows channel c of the frame
+    at time t - shifts[c].  Fed the frames of a clip one by one, the module returns, stacked, what TemporalShift returns for the clip
+    under the same table and padding.  Inference only: a frame that requires grad raises.
+
+    Arguments:
+        in_channels (int): channels of the frames.
+        fold_div (int): the default table shows the first in_channels // fold_div channels one frame late (shift 1) and leaves the
+            rest. Default 8.
+        shifts (tensor / list): [in_channels] integers >= 0 that replace the default table (fold_div is then unused).
+        padding (str): 'zeros' | 'border': what the first frames see in place of the frames before the stream began -- zeros (the
+            zero point of a quantized frame), or the first frame.  The other paddings look into the future and are refused.
+        inplace (bool): shift the frame itself and return it; otherwise a clone is shifted.  A plain attribute, not part of
+            state_dict. Default False.
+    forward(frame) -> the shifted frame alone.  The state ([max(shifts), B, C, ...] in the frame's layout) is the plain attribute
+    `state`, not part of state_dict: it is made on the first call (torchshifts.functional.temporal_shift_online_state: the one host
+    synchronisation) and dropped by reset(), which starts a new stream.  A later frame of another shape, dtype, device or layout
+    raises.  On HIP tensors a step on a dense frame with max(shifts) <= 15 is one kernel over the shifted channels alone, with no
+    allocation (inplace=True) and no host synchronisation: it can be captured in a torch.cuda.graph once the state exists.
+    """
+    def __init__(self, in_channels, fold_div=8, shifts=None, padding='zeros', inplace=False):
+        super().__init__()
+        assert padding.lower() in paddings_dict.keys(), f'incorrect padding option: {padding}'
+        if paddings_dict[padding.lower()] > 1:
+            raise ValueError(f'{padding} padding looks into the future: an online shift pads with zeros or border')
+        self.padding = paddings_dict[padding.lower()]
+        self.inplace = bool(inplace)
+        self.in_channels = in_channels
+        self.fold_div = int(fold_div)
+        if shifts is None:
+            table = self.default_table(in_channels, self.fold_div)
+        else:
+            table = torch.as_tensor(shifts)
+            assert tuple(table.shape) == (in_channels,), f'shifts must have shape [{in_channels}]'
+            if table.is_floating_point():
+                table = torch.round(table)
+            table = table.detach().to(torch.int64).clone()
+            if table.numel() and int(table.min()) < 0:
+                raise ValueError('a negative shift reads the future: an online table is causal (every entry >= 0)')
+        self.register_buffer('shifts', table, persistent=True)
+        self.state = None
+        self._table = None   # `shifts` in the kind the kernel reads: made with the state
+        self._frame = None   # shape, strides, dtype and device of the frames the state was made for
+
+    @staticmethod
+    def default_table(in_channels, fold_div):
+        table = torch.zeros(in_channels, dtype=torch.int64)
+        table[:in_channels // fold_div] = 1
+        return table
+
+    @classmethod
+    def from_shift(cls, module, inplace=False):
+        """The online form of a TemporalShift whose table is causal (every entry >= 0), with its padding; ValueError otherwise --
+        the published bidirectional table reads one frame ahead."""
+        assert isinstance(module, TemporalShift), 'expected a TemporalShift module'
+        table = module.shifts.detach().cpu()
+        if table.numel() and int(table.min()) < 0:
+            raise ValueError('the table reads the future (a negative shift): no online form')
+        pad = {v: k for k, v in paddings_dict.items()}[module.padding]
+        return cls(module.in_channels, fold_div=module.fold_div, shifts=table, padding=pad, inplace=inplace).to(module.shifts.device)
+
+    def reset(self):
+        """Drop the state: the next frame begins a new stream."""
+        self.state = None
+        self._table = None
+        self._frame = None
+
+    def _step(self, frame, state, table):
+        return (temporal_shift_online_func_ if self.inplace else temporal_shift_online_func)(frame, state, table)
+
+    def forward(self, input):
+        if self.state is None:
+            self.state = temporal_shift_online_state(input, self.shifts, self.padding)
+            self._table = temporal_shift_online_table(input, self.shifts)
+            self._frame = (tuple(input.shape), tuple(input.stride()), input.dtype, input.device)
+        else:
+            frame = (tuple(input.shape), tuple(input.stride()), input.dtype, input.device)
+            if frame != self._frame:
+                raise RuntimeError('OnlineTemporalShift: the state was made for frames of shape %s, strides %s, %s on %s, but this frame '
+                                   'has shape %s, strides %s, %s on %s; reset() starts a new stream' % (self._frame + frame))
+        return self._step(input, self.state, self._table)
+
+    def extra_repr(self):
+        pad = {v: k for k, v in paddings_dict.items()}[self.padding]
+        return (f'in_channels={self.in_channels}, fold_div={self.fold_div}, padding_method={pad}, fixed integer shifts, online'
+                + (', inplace=True' if self.inplace else ''))
 
 
 class LearnableTemporalShift(nn.Module):

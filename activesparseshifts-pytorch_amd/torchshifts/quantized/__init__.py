@@ -21,6 +21,6 @@ def _default_static_mappings():
 
 tndm_mapping = _default_static_mappings()
 
-from .modules import Shift1d, Shift2d, Shift3d, TemporalShift, new_quant_mapping  # noqa: E402,F401
+from .modules import OnlineTemporalShift, Shift1d, Shift2d, Shift3d, TemporalShift, new_quant_mapping  # noqa: E402,F401
 
 quant_mapping = {**tndm_mapping, **new_quant_mapping}

@@ -50,3 +50,21 @@ def temporal_shift_quantized_(input, shifts, n_segment, padding_mode=0):
         raise ValueError("Input to 'temporal_shift_quantized_' must be quantized!")
     _assert_has_ops()
     return torch.ops.torchshifts_inplace.temporal_shift_quantized_(input, shifts, int(n_segment), int(padding_mode))
+
+
+def temporal_shift_online_quantized_(input, state, shifts):
+    """One online step (torchshifts.functional.temporal_shift_online_func_) on a per-tensor quantized frame [B, C, ...] (quint8,
+    qint8, qint32) and its quantized state [D, B, C, ...] (temporal_shift_online_state: the input's scale and zero point, the zero
+    point in every slot for zeros padding; any other state raises).  Both are written, `input` is returned with its scale, zero
+    point and layout.  On HIP tensors a dense frame with D <= 15 is one kernel over the shifted channels alone, with an int32 table."""
+    if not input.is_quantized:
+        raise ValueError("Input to 'temporal_shift_online_quantized_' must be quantized!")
+    _assert_has_ops()
+    return torch.ops.torchshifts_online.temporal_shift_online_quantized_(input, state, shifts)
+
+
+def temporal_shift_online_quantized(input, state, shifts):
+    """temporal_shift_online_quantized_ on a clone of `input`: the input is left as it was, the state is still updated."""
+    if not input.is_quantized:
+        raise ValueError("Input to 'temporal_shift_online_quantized' must be quantized!")
+    return temporal_shift_online_quantized_(input.clone(memory_format=torch.preserve_format), state, shifts)

@@ -1,7 +1,8 @@
 new_quant_mapping = {}
 
-from .shifts import Shift1d, Shift2d, Shift3d, TemporalShift  # noqa: E402
+from .shifts import OnlineTemporalShift, Shift1d, Shift2d, Shift3d, TemporalShift  # noqa: E402
 import torchshifts.modules.shifts as shifts  # noqa: E402
 
 new_quant_mapping.update({shifts.Shift1d: Shift1d, shifts.Shift2d: Shift2d, shifts.Shift3d: Shift3d,
-                          shifts.TemporalShift: TemporalShift, shifts.LearnableTemporalShift: TemporalShift})
+                          shifts.TemporalShift: TemporalShift, shifts.LearnableTemporalShift: TemporalShift,
+                          shifts.OnlineTemporalShift: OnlineTemporalShift})

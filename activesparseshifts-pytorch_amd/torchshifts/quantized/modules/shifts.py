@@ -20,7 +20,7 @@ import torch
 
 import torchshifts.modules.shifts as shifts
 from torchshifts.functional import shift1d_pool_func, shift2d_pool_func, shift3d_pool_func
-from torchshifts.quantized.functional import shift1d_quantized, shift2d_quantized, shift3d_quantized, temporal_shift_quantized, temporal_shift_quantized_
+from torchshifts.quantized.functional import shift1d_quantized, shift2d_quantized, shift3d_quantized, temporal_shift_quantized, temporal_shift_quantized_, temporal_shift_online_quantized, temporal_shift_online_quantized_
 
 _POOL_FUNCS = {1: shift1d_pool_func, 2: shift2d_pool_func, 3: shift3d_pool_func}
 
@@ -170,4 +170,28 @@ class TemporalShift(shifts.TemporalShift):
         assert isinstance(mod, shifts.TemporalShift), 'expected a TemporalShift or LearnableTemporalShift module'
         qshift = cls(mod.n_segment, mod.in_channels, fold_div=mod.fold_div, shifts=mod.shifts.detach().cpu(), padding=rp_dict[mod.padding],
                      memory_format=mod.memory_format, inplace=mod.inplace)
+        return qshift.to(mod.shifts.device)
+
+
+class OnlineTemporalShift(shifts.OnlineTemporalShift):
+    """Quantized online Temporal Shift Module: the float OnlineTemporalShift on per-tensor quantized frames (quint8, qint8, qint32).
+    The table is the same persistent int64 buffer `shifts`, so a float checkpoint loads as it is.  The state is a quantized tensor
+    with the first frame's scale and zero point -- the zero point in every slot under zeros padding -- and the output keeps the
+    frame's scale and zero point; a later frame with other quantization parameters raises.  On HIP tensors the table is passed as
+    int32.
+
+    forward(frame) -> the shifted frame alone.  from_float converts an OnlineTemporalShift and carries `inplace` over.
+    """
+
+    def _step(self, frame, state, table):
+        return (temporal_shift_online_quantized_ if self.inplace else temporal_shift_online_quantized)(frame, state, table)
+
+    def _get_name(self):
+        return 'QuantizedOnlineTemporalShift'
+
+    @classmethod
+    def from_float(cls, mod):
+        assert isinstance(mod, shifts.OnlineTemporalShift), 'expected an OnlineTemporalShift module'
+        qshift = cls(mod.in_channels, fold_div=mod.fold_div, shifts=mod.shifts.detach().cpu(), padding=rp_dict[mod.padding],
+                     inplace=mod.inplace)
         return qshift.to(mod.shifts.device)

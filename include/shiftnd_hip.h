@@ -195,6 +195,39 @@ typedef enum shiftnd_dtype {
  */
 #define SHIFTND_PER_CLIP 0x1000
 
+/*
+ * The ONLINE temporal shift (the uni-directional TSM of arXiv 1811.08383, section 4.2): frames arrive one at a time and the channels
+ * that shift are taken from a cached state of the previous frames.  OR-ed onto a dtype TOGETHER WITH SHIFTND_SHIFT_DIM0 (and, for
+ * F16 / BF16, optionally SHIFTND_WEIGHTS_F32).  One call is one step on a frame batch [B, C, spatial...] of B independent streams:
+ *   p->sizes = {B, C, D, spatial...} (ndim 2 or 3), the whole window, p->active == 0, padding mode 0 or 1 (neither is looked at
+ *   further: the state's initial bytes ARE the padding -- zeros / the zero point for mode 0, the first frame for mode 1);
+ *   `x` is the STATE, D slots of the frame's shape and strides, with the slot stride in the S0 place of x_strides; slot k holds
+ *   frame t-1-k.  It is READ AND WRITTEN although the parameter is const-qualified;
+ *   `out` is the FRAME, read and written; the S0 entry of out_strides is ignored;
+ *   `weights` is the [C] table, in the kinds the in-place form takes: the tensor dtype, or fp32 under SHIFTND_WEIGHTS_F32
+ *   (shiftnd_forward); wq_dtype with w_zero_point (shiftnd_forward_quantized, I8 / U8 / I32 tensors; x_zero_point is not used).
+ * For every channel c with s = min(max(s_c, 0), D) > 0 (out[t] = x[t - s_c]: a positive entry reads the past):
+ *     frame[:, c] <- slot[s-1][:, c];   slot[k][:, c] <- slot[k-1][:, c] for k = s-1 .. 1;   slot[0][:, c] <- the incoming frame[:, c]
+ * A channel with s == 0 is neither read nor written, in the frame or in the state, and slots k >= s of a channel are never touched.
+ * An entry outside [0, D] is clamped: the kernel cannot raise, validating the table is the caller's job.
+ *   Served by csrc/shiftnd_stream.hip: a thread owns one naturally aligned power-of-two piece (at most 16 bytes: the widest that
+ *   divides the plane's bytes, or the channel row's bytes, and both bases) at the same offset in the frame and in every slot of one
+ *   stream, gathers the s + 1 pieces of its line into registers and stores them one place on.  No workspace, no allocation, no
+ *   synchronisation.  shiftnd_last_kernel(): frames_stream for 16-byte pieces, frames_stream_ragged for narrower ones;
+ *   shiftnd_last_path(): SHIFTND_PATH_PLANE for contiguous tensors, SHIFTND_PATH_CL for channels-last ones, SHIFTND_PATH_EMPTY for an
+ *   empty frame or D == 0 (nothing moves).
+ *   Accepted: frame and state both dense contiguous (memory order B, C, spatial) or both dense channels-last (B, spatial, C), slots
+ *   one frame batch apart; a pair both layouts describe is served as contiguous; element-aligned bases; D <= 15 (the kernel keeps a
+ *   line in 16 register slots).  Bounds: those of the in-place form with D in the place of S0.
+ *   Errors, before anything is launched: SHIFTND_FRAMES or SHIFTND_PER_CLIP beside the bit, D > 15, a cut window, p->active == 1,
+ *   padding mode 2..4 (periodic, reflect and symmetric padding look into the future), a layout that is neither dense form, frame
+ *   and state in different layouts, a frame that overlaps the state, a size beyond the bounds, and shiftnd_backward:
+ *   SHIFTND_ERR_INVALID_ARGUMENT.  shiftnd_backward_workspace_bytes answers 0.
+ * Without SHIFTND_SHIFT_DIM0 the bit is an unknown dtype bit on every entry point: SHIFTND_ERR_UNSUPPORTED_DTYPE.  Without the bit
+ * nothing changes.  (0x800 stays unassigned.)
+ */
+#define SHIFTND_STREAM 0x2000
+
 typedef enum shiftnd_status {
     SHIFTND_OK = 0,
     SHIFTND_ERR_INVALID_ARGUMENT = -1,
@@ -218,7 +251,7 @@ typedef enum shiftnd_path {
 /* Problem geometry shared by the entry points. */
 typedef struct shiftnd_problem {
     int32_t ndim;          /* spatial dims: 1, 2 or 3 */
-    int32_t dtype;         /* shiftnd_dtype of input/output (and of float weights), optionally | SHIFTND_WEIGHTS_F32 | SHIFTND_SHIFT_DIM0 | SHIFTND_FRAMES | SHIFTND_PER_CLIP */
+    int32_t dtype;         /* shiftnd_dtype of input/output (and of float weights), optionally | SHIFTND_WEIGHTS_F32 | SHIFTND_SHIFT_DIM0 | SHIFTND_FRAMES | SHIFTND_PER_CLIP | SHIFTND_STREAM */
     int32_t padding_mode;  /* 0..4 */
     int32_t active;        /* 0: sparse shift (rounded integer shift); 1: active (interpolated) */
     int64_t sizes[5];      /* input N, C, H, W, D */
