@@ -275,24 +275,33 @@ int forward_common(const shiftnd_problem *p, const void *x, const int64_t *xs, c
 // SHIFTND_FRAMES beside the flag: the same problem on dense channels-last tensors, all of them (shiftnd_frames_learn.hip; the sparse
 // forward is frames_forward).  The explicit bit takes every such call to the frame kernels -- also tensors that the segment-major
 // layout describes as well -- or refuses it.
-// -> the problem without the flag bits in `q`, the weights' type in `wkind`, the presence of SHIFTND_PER_CLIP and SHIFTND_FRAMES
+// SHIFTND_CLIP_FRAMES beside the flag: both at once under a bit of its own -- dense channels-last tensors, all of them, and [N, C]
+// arrays; the frame kernels under a row stride (FramesParams::wrow), out of place, or the call is refused.  SHIFTND_FRAMES |
+// SHIFTND_PER_CLIP stays refused, and so is the new bit beside either of them.
+// -> the problem without the flag bits in `q`, the weights' type in `wkind`, whether the table is per clip ([N, C]: SHIFTND_PER_CLIP or
+// SHIFTND_CLIP_FRAMES) and whether the frame kernels alone serve the call (SHIFTND_FRAMES or SHIFTND_CLIP_FRAMES)
 int tshift_problem(const shiftnd_problem *p, shiftnd_problem &q, int &wkind, bool &per_clip, bool &frames) {
     shiftnd_problem r = *p;
-    r.dtype = p->dtype & ~(SHIFTND_SHIFT_DIM0 | SHIFTND_PER_CLIP | SHIFTND_FRAMES);
+    r.dtype = p->dtype & ~(SHIFTND_SHIFT_DIM0 | SHIFTND_PER_CLIP | SHIFTND_FRAMES | SHIFTND_CLIP_FRAMES);
+    const bool clip_frames = (p->dtype & SHIFTND_CLIP_FRAMES) != 0;
     per_clip = (p->dtype & SHIFTND_PER_CLIP) != 0;
     frames = (p->dtype & SHIFTND_FRAMES) != 0;
     if (split_dtype(&r, q, wkind) != SHIFTND_OK || !is_float_dtype(q.dtype)) return SHIFTND_ERR_UNSUPPORTED_DTYPE;
-    return frames && per_clip ? SHIFTND_ERR_INVALID_ARGUMENT : SHIFTND_OK;   // (the frame kernels take a [C] table alone)
+    if (frames && per_clip) return SHIFTND_ERR_INVALID_ARGUMENT;   // (under SHIFTND_FRAMES the frame kernels take a [C] table alone)
+    if (clip_frames && (frames || per_clip)) return SHIFTND_ERR_INVALID_ARGUMENT;
+    if (clip_frames) per_clip = frames = true;
+    return SHIFTND_OK;
 }
 
 // the bound SHIFTND_PER_CLIP adds to tshift_geometry_ok's: the [N, C] table is indexed in 32 bits.  (Today N * S0 * C < 2^31 implies
-// it; it is stated on its own because the kernels' table index and the reduction's entry count rest on it.)
+// it; it is stated on its own because the kernels' table index and the reduction's entry count rest on it.)  SHIFTND_CLIP_FRAMES adds
+// it to frames_learn_geometry_ok's, which does not imply it: the reduction counts the N * C entries in an int.
 bool per_clip_table_ok(const Geometry &g) { return g.N * g.C < (1LL << 31); }   // (both factors are below 2^31 here: no overflow)
 
 // the sizes a backward under the flag is served at, and its workspace: the two points where the workspace query and the backward
 // call tell the layouts apart together
 bool tshift_backward_sizes_ok(const Geometry &g, int dtype, bool per_clip, bool frames) {
-    return frames ? frames_learn_geometry_ok(g, dtype) : tshift_geometry_ok(g, dtype) && (!per_clip || per_clip_table_ok(g));
+    return (frames ? frames_learn_geometry_ok(g, dtype) : tshift_geometry_ok(g, dtype)) && (!per_clip || per_clip_table_ok(g));
 }
 size_t tshift_backward_workspace_for(const Geometry &g, int dtype, bool frames) {
     return frames ? frames_backward_workspace(g, dtype) : tshift_backward_workspace(g, dtype);
@@ -327,7 +336,7 @@ int inplace_call(const shiftnd_problem &q, void *x, const int64_t *xs, const int
 // causal), the whole window -- or refused before anything is launched.
 int stream_call(const shiftnd_problem &q, int flags, void *state, const int64_t *xs, void *frame, const int64_t *os, const void *w,
                 int wkind, int64_t wzp, void *stream) {
-    if (flags & (SHIFTND_FRAMES | SHIFTND_PER_CLIP)) return SHIFTND_ERR_INVALID_ARGUMENT;
+    if (flags & (SHIFTND_FRAMES | SHIFTND_PER_CLIP | SHIFTND_CLIP_FRAMES)) return SHIFTND_ERR_INVALID_ARGUMENT;
     if (q.active || q.padding_mode > 1) return SHIFTND_ERR_INVALID_ARGUMENT;
     Geometry g;
     const int rc = build_geometry(&q, xs, os, nullptr, g);
@@ -349,7 +358,7 @@ int tshift_forward_call(const shiftnd_problem *p, const void *x, const int64_t *
     if (p->dtype & SHIFTND_STREAM) {   // the online step: x is the state, read AND written (the header says so)
         shiftnd_problem r = *p, q;
         int wkind;
-        r.dtype = p->dtype & ~(SHIFTND_SHIFT_DIM0 | SHIFTND_STREAM | SHIFTND_FRAMES | SHIFTND_PER_CLIP);
+        r.dtype = p->dtype & ~(SHIFTND_SHIFT_DIM0 | SHIFTND_STREAM | SHIFTND_FRAMES | SHIFTND_PER_CLIP | SHIFTND_CLIP_FRAMES);
         if (split_dtype(&r, q, wkind) != SHIFTND_OK || !is_float_dtype(q.dtype)) return SHIFTND_ERR_UNSUPPORTED_DTYPE;
         return stream_call(q, p->dtype, const_cast<void *>(x), xs, out, os, w, wkind, 0, stream);
     }
@@ -359,7 +368,7 @@ int tshift_forward_call(const shiftnd_problem *p, const void *x, const int64_t *
         bool per_clip, frames;
         if (p->dtype & SHIFTND_FRAMES) return SHIFTND_ERR_INVALID_ARGUMENT;
         const int rc = tshift_problem(p, q, wkind, per_clip, frames);
-        if (rc == SHIFTND_OK && per_clip) return SHIFTND_ERR_INVALID_ARGUMENT;   // (the in-place kernel takes a [C] table alone)
+        if (rc == SHIFTND_OK && per_clip) return SHIFTND_ERR_INVALID_ARGUMENT;   // (the in-place kernel takes a [C] table alone; SHIFTND_CLIP_FRAMES too)
         return rc != SHIFTND_OK ? rc : inplace_call(q, out, xs, os, w, wkind, 0, 0ull, stream);
     }
     shiftnd_problem q;
@@ -372,9 +381,11 @@ int tshift_forward_call(const shiftnd_problem *p, const void *x, const int64_t *
     if (rc != SHIFTND_OK) return rc;
     // without SHIFTND_FRAMES two layouts are served: segment-major (the tshift kernels, sparse and interpolating) and, for the sparse
     // shift, channels-last (shiftnd_frames.hip: frames_geometry_ok refuses `active`).  A tensor both describe (planes or channels of
-    // size 1) stays with the tshift kernels.  A per-clip table: the tshift kernels alone.  With the bit: the frame kernels alone
+    // size 1) stays with the tshift kernels.  A per-clip table: the tshift kernels alone.  With the bit: the frame kernels alone (and
+    // under SHIFTND_CLIP_FRAMES the frame kernels alone with a per-clip table)
     const bool segment_sizes = !frames && tshift_geometry_ok(g, q.dtype) && (!per_clip || per_clip_table_ok(g));
-    const bool frames_sizes = frames ? frames_learn_geometry_ok(g, q.dtype) : !per_clip && frames_geometry_ok(g, q.dtype);
+    const bool frames_sizes = frames ? frames_learn_geometry_ok(g, q.dtype) && (!per_clip || per_clip_table_ok(g))
+                                     : !per_clip && frames_geometry_ok(g, q.dtype);
     if (!segment_sizes && !frames_sizes) return SHIFTND_ERR_INVALID_ARGUMENT;
     if (empty_geometry(g)) {   // (empty_problem's answer: every *_geometry_ok above refuses a cut window)
         g_last_path = SHIFTND_PATH_EMPTY;
@@ -387,8 +398,8 @@ int tshift_forward_call(const shiftnd_problem *p, const void *x, const int64_t *
     }
     if (frames_sizes && frames_tensor_ok(g, q.dtype, x, g.xs) && frames_tensor_ok(g, q.dtype, out, g.os)) {
         g_last_path = SHIFTND_PATH_CL;
-        if (g.active) return finish(frames_active_forward(g, q.dtype, x, w, wkind, out, static_cast<hipStream_t>(stream)));   // (SHIFTND_FRAMES only)
-        return finish(frames_forward(g, q.dtype, x, w, wkind, 0, 0ull, out, static_cast<hipStream_t>(stream)));
+        if (g.active) return finish(frames_active_forward(g, q.dtype, x, w, wkind, per_clip, out, static_cast<hipStream_t>(stream)));   // (SHIFTND_FRAMES / SHIFTND_CLIP_FRAMES only)
+        return finish(frames_forward(g, q.dtype, x, w, wkind, 0, 0ull, per_clip, out, static_cast<hipStream_t>(stream)));
     }
     return SHIFTND_ERR_INVALID_ARGUMENT;
 }
@@ -410,7 +421,7 @@ int frames_quantized_call(const shiftnd_problem *p, const void *x, const int64_t
     if (!x || !wq || !out) return SHIFTND_ERR_INVALID_ARGUMENT;
     if (!frames_tensor_ok(g, q.dtype, x, g.xs) || !frames_tensor_ok(g, q.dtype, out, g.os)) return SHIFTND_ERR_INVALID_ARGUMENT;
     g_last_path = SHIFTND_PATH_CL;
-    return finish(frames_forward(g, q.dtype, x, wq, wq_dtype, wzp, fill, out, static_cast<hipStream_t>(stream)));
+    return finish(frames_forward(g, q.dtype, x, wq, wq_dtype, wzp, fill, false, out, static_cast<hipStream_t>(stream)));
 }
 
 // the backward under the flag, both layouts: `frames` (SHIFTND_FRAMES) picks the sizes, the tensor check, the workspace and the kernels
@@ -440,7 +451,7 @@ int tshift_backward_call(const shiftnd_problem *p, const void *go, const int64_t
     if (!tensor_ok(go, g.os) || !tensor_ok(x, g.xs) || !tensor_ok(gx, g.gs)) return SHIFTND_ERR_INVALID_ARGUMENT;
     if (tshift_backward_workspace_for(g, q.dtype, frames) > workspace_bytes) return SHIFTND_ERR_WORKSPACE_TOO_SMALL;
     g_last_path = frames ? SHIFTND_PATH_CL : SHIFTND_PATH_PLANE;
-    if (frames) return finish(frames_backward(g, q.dtype, go, x, w, wkind, gx, gw, workspace, st));
+    if (frames) return finish(frames_backward(g, q.dtype, go, x, w, wkind, per_clip, gx, gw, workspace, st));
     return finish(tshift_backward(g, q.dtype, go, x, w, wkind, per_clip, gx, gw, workspace, st));
 }
 
@@ -578,7 +589,7 @@ int shiftnd_forward_quantized(const shiftnd_problem *p, const void *x, const int
     // the online step (SHIFTND_STREAM beside the flag; alone it is an unknown dtype bit): SHIFTND_FRAMES / SHIFTND_PER_CLIP beside it
     // are its own refusal, not an unknown dtype
     const bool online = (p->dtype & SHIFTND_SHIFT_DIM0) && (p->dtype & SHIFTND_STREAM);
-    const int dtype = p->dtype & ~(online ? SHIFTND_SHIFT_DIM0 | SHIFTND_STREAM | SHIFTND_FRAMES | SHIFTND_PER_CLIP : SHIFTND_SHIFT_DIM0);   // (the flag with a float dtype or with SHIFTND_WEIGHTS_F32: no quantized dtype)
+    const int dtype = p->dtype & ~(online ? SHIFTND_SHIFT_DIM0 | SHIFTND_STREAM | SHIFTND_FRAMES | SHIFTND_PER_CLIP : SHIFTND_SHIFT_DIM0);   // (the flag with a float dtype or with SHIFTND_WEIGHTS_F32: no quantized dtype; SHIFTND_CLIP_FRAMES is left in: none either)
     if (!is_quant_dtype(dtype) || !is_quant_dtype(wq_dtype)) return SHIFTND_ERR_UNSUPPORTED_DTYPE;
     shiftnd_problem q = *p;
     if (online) {   // x is the state, read AND written; the state's initial bytes are the padding, so x_zero_point is not used
@@ -621,7 +632,7 @@ size_t shiftnd_backward_workspace_bytes(const shiftnd_problem *p) {
     int wkind;
     // every entry point refuses the bit alone, so the answer is 0.  (The path below would not give it: it looks at the geometry and sizes
     // the families' plans whatever unknown bits the dtype carries -- 0x800 on F32 answers 512 bytes there, an answer a test pins)
-    if ((p->dtype & SHIFTND_PER_CLIP) && !(p->dtype & SHIFTND_SHIFT_DIM0)) return 0;
+    if ((p->dtype & (SHIFTND_PER_CLIP | SHIFTND_CLIP_FRAMES)) && !(p->dtype & SHIFTND_SHIFT_DIM0)) return 0;
     if (p->dtype & SHIFTND_STREAM) return 0;   // (alone an unknown bit like the one above; beside the flag the online step: no backward, no workspace)
     if (p->dtype & SHIFTND_SHIFT_DIM0) {   // the walk's plan alone (SHIFTND_FRAMES: the channels-last walk's): no other family runs under the flag, no knob shapes it
         const int64_t unit[5] = {0, 0, 0, 0, 0};

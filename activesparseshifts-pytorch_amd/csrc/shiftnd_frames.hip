@@ -25,6 +25,8 @@
 //   frames_forward          16-byte pieces (rows of whole 16-byte pieces, 16-byte-aligned bases)
 //   frames_forward_ragged   8-, 4-, 2- or 1-byte pieces: the same structure
 // Every access is naturally aligned and lies inside the bytes the tensors occupy; the table is read at entries [0, C) only.
+// A per-clip table (SHIFTND_CLIP_FRAMES: [N, C], one row per clip) is a launch-uniform row stride, FramesParams::wrow: a workgroup lies
+// inside one frame of one clip n, so it forms its row's base once and reads entries [n * C, (n + 1) * C) of the table.
 // The input gradient of the op is this kernel on the gradient under the negated table.
 #include <algorithm>
 
@@ -46,6 +48,7 @@ struct FramesParams {
     int pad, wkind, es_log2, unit_log2;   // element bytes and piece bytes as powers of two
     uint32_t T, P, span, rps;             // frames per clip, pieces per row, min(P, 256), rows per step = max(1, 256 / P)
     uint32_t chunks, rows_per_wg;         // workgroups per frame, rows (a multiple of rps * kInFlight) of each
+    uint32_t wrow;                        // shift of (n, c): entry n * wrow + c -- 0 for a [C] table, C for a per-clip [N, C] one
     FastDiv d_chunks, d_T, d_span, d_per; // d_per: by map_period(T, pad)
     int64_t M, R, frame_bytes;            // pixels per frame, bytes per row, bytes per frame
     int64_t wzp;                          // zero point of an integer table
@@ -97,13 +100,14 @@ __device__ __forceinline__ int source_frame(const FramesParams &q, const void *w
 }
 
 template <int UL>
-__device__ __forceinline__ void frames_body(const FramesParams &q, const char *__restrict__ x, const void *__restrict__ w,
+__device__ __forceinline__ void frames_body(const FramesParams &q, const char *__restrict__ x, const void *__restrict__ table,
                                             char *__restrict__ out) {
     constexpr int kUnit = 1 << UL;
     const uint32_t frame = fdiv(blockIdx.x, q.d_chunks);   // n * T + t
     const uint32_t chunk = blockIdx.x - frame * q.chunks;
     const uint32_t n = fdiv(frame, q.d_T);
     const int t = static_cast<int>(frame - n * q.T);
+    const void *const w = table_row(table, q.wkind, n, q.wrow);   // the clip's row of the table: once per workgroup, scalar
     const uint32_t rl = fdiv(threadIdx.x, q.d_span);       // the thread's row of a step, its piece of the row
     const uint32_t k0 = threadIdx.x - rl * q.span;
     if (rl >= q.rps) return;                               // (idle tail lanes where P does not divide 256)
@@ -215,13 +219,14 @@ bool frames_tensor_ok(const Geometry &g, int dtype, const void *p, const int64_t
     return g.N == 1 || st[0] == T * A * B * g.C;
 }
 
-int frames_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, int64_t wzp, uint64_t fill_bits, void *out,
-                   hipStream_t st) {
+int frames_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, int64_t wzp, uint64_t fill_bits, bool per_clip,
+                   void *out, hipStream_t st) {
     const int es = dtype_size(dtype);
     FramesParams q;
     q.pad = g.pad;
     q.wkind = wkind;
     q.wzp = wzp;
+    q.wrow = per_clip ? static_cast<uint32_t>(g.C) : 0;
     q.es_log2 = es_log2(es);
     q.fill = fill_dword(es, fill_bits);
     q.T = static_cast<uint32_t>(g.S[3 - g.nd]);

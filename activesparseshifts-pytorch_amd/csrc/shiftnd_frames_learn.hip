@@ -22,6 +22,8 @@
 //                          grad_w: ONE fp64 sum per element of the thread's piece of grad_out * (x[B] - x[A]) (difference and
 //                          product in fp64), summed over the workgroup's rows in LDS in a fixed order, one partial record
 //                          (group * C + c) * 3 with group = n * chunks + chunk, finished by launch_reduce_weight_grads.
+//                          A per-clip table (SHIFTND_CLIP_FRAMES: [N, C], FramesLearnParams::wrow = C) re-indexes the same
+//                          records as ((chunk * N + n) * C + c) * 3: `chunks` groups of N * C entries, one sum per (n, c).
 //                          Deviation from the clip tile in LDS: no LDS staging, hence no limit on T and no refusal for it.
 //
 // ONE kernel per pass: the element type and the piece (`elems` elements, 16 bytes down to one element) are launch-uniform
@@ -42,6 +44,7 @@ struct FramesLearnParams {
     uint32_t T, P, span, rps;               // frames per clip, pieces per row, min(P, 256), rows per step = max(1, 256 / P)
     uint32_t chunks, rows_per_wg;           // workgroups per frame (forward) / per clip (backward), rows of each
     uint32_t C;
+    uint32_t wrow, clips;                   // weight of (n, c): entry n * wrow + c -- 0 for a [C] table, C for a per-clip [N, C] one; N
     FastDiv d_chunks, d_T, d_span, d_per;   // d_per: by map_period(T, pad)
     int64_t M, R, frame_bytes;              // pixels per frame, bytes per row, bytes per frame
 };
@@ -79,7 +82,7 @@ __device__ __forceinline__ Unit<T, E> blend_units(const Unit<T, E> &a, const Uni
 }
 
 template <typename T, int E>
-__device__ __forceinline__ void forward_body(const FramesLearnParams &q, const char *__restrict__ x, const void *__restrict__ w,
+__device__ __forceinline__ void forward_body(const FramesLearnParams &q, const char *__restrict__ x, const void *__restrict__ table,
                                              char *__restrict__ out) {
     using CT = typename T::C;
     constexpr int V = sizeof(typename T::S) * E;
@@ -87,6 +90,7 @@ __device__ __forceinline__ void forward_body(const FramesLearnParams &q, const c
     const uint32_t chunk = blockIdx.x - frame * q.chunks;
     const uint32_t n = fdiv(frame, q.d_T);
     const int t = static_cast<int>(frame - n * q.T), Tn = static_cast<int>(q.T);
+    const void *const w = table_row(table, q.wkind, n, q.wrow);   // the clip's row of the table: once per workgroup, scalar
     const uint32_t rl = fdiv(threadIdx.x, q.d_span);       // the thread's row of a step, its piece of the row
     const uint32_t k0 = threadIdx.x - rl * q.span;
     if (rl >= q.rps) return;                               // (idle tail lanes where P does not divide 256)
@@ -146,18 +150,20 @@ __device__ __forceinline__ void forward_body(const FramesLearnParams &q, const c
 // `red`: kThreads * kMaxElems doubles of LDS
 template <typename T, int E>
 __device__ __forceinline__ void backward_body(const FramesLearnParams &q, const char *__restrict__ go, const char *__restrict__ x,
-                                              const void *__restrict__ w, char *__restrict__ gx, double *__restrict__ partials,
+                                              const void *__restrict__ table, char *__restrict__ gx, double *__restrict__ partials,
                                               double *red) {
     using CT = typename T::C;
     constexpr int V = sizeof(typename T::S) * E;
     const int Tn = static_cast<int>(q.T);
     const uint32_t n = fdiv(blockIdx.x, q.d_chunks), chunk = blockIdx.x - n * q.chunks;
+    const void *const w = table_row(table, q.wkind, n, q.wrow);   // the clip's row of the table: once per workgroup, scalar
     const uint32_t rl = fdiv(threadIdx.x, q.d_span), k0 = threadIdx.x - rl * q.span;
     const int64_t first_row = static_cast<int64_t>(chunk) * q.rows_per_wg;
     const int rows = static_cast<int>(first_row + q.rows_per_wg < q.M ? q.rows_per_wg : q.M - first_row);
     const int rps = static_cast<int>(q.rps);
     const int64_t clip = static_cast<int64_t>(n) * q.T * q.frame_bytes + first_row * q.R;   // the workgroup's rows of the clip's frame 0
-    const size_t group = static_cast<size_t>(n) * q.chunks + chunk;
+    // a per-clip table: `chunks` groups of N * C entries, so that the reduction sums per (n, c) -- as tshift_backward
+    const size_t group = q.wrow ? static_cast<size_t>(chunk) * q.clips + n : static_cast<size_t>(n) * q.chunks + chunk;
 #pragma unroll 1
     for (uint32_t kb = 0; kb < q.P; kb += kThreads) {      // (once unless a row has more than 256 pieces; uniform: barriers inside)
         const uint32_t k = kb + k0;
@@ -248,7 +254,7 @@ __global__ __launch_bounds__(kThreads) void frames_backward(FramesLearnParams q,
                        [&](auto ty, auto e) { backward_body<decltype(ty), decltype(e)::value>(q, go, x, w, gx, partials, red); });
 }
 
-FramesLearnParams make_params(const Geometry &g, int dtype, int wkind, int unit) {
+FramesLearnParams make_params(const Geometry &g, int dtype, int wkind, int unit, bool per_clip) {
     FramesLearnParams q;
     const int es = dtype_size(dtype);
     q.pad = g.pad;
@@ -258,6 +264,8 @@ FramesLearnParams make_params(const Geometry &g, int dtype, int wkind, int unit)
     q.elems = unit / es;
     q.T = static_cast<uint32_t>(g.S[3 - g.nd]);
     q.C = static_cast<uint32_t>(g.C);
+    q.wrow = per_clip ? q.C : 0;
+    q.clips = static_cast<uint32_t>(g.N);
     q.M = frame_pixels(g);
     q.R = g.C * es;
     q.frame_bytes = q.M * q.R;
@@ -297,9 +305,10 @@ bool frames_learn_geometry_ok(const Geometry &g, int dtype) {
     return groups < (1LL << 31) && groups <= (1LL << 46) / (g.C * 24);
 }
 
-int frames_active_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, void *out, hipStream_t st) {
+int frames_active_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, bool per_clip, void *out,
+                          hipStream_t st) {
     const int unit = piece_bytes(g.C * dtype_size(dtype), {x, out});
-    FramesLearnParams q = make_params(g, dtype, wkind, unit);
+    FramesLearnParams q = make_params(g, dtype, wkind, unit, per_clip);
     // workgroups per frame: at least one batch of kFwdInFlight steps each, more steps while the grid is large
     const int64_t frames = g.N * q.T, batch_rows = static_cast<int64_t>(q.rps) * kFwdInFlight;
     const int64_t most = (q.M + batch_rows - 1) / batch_rows;
@@ -320,10 +329,10 @@ size_t frames_backward_workspace(const Geometry &g, int dtype) {
     return static_cast<size_t>(g.N * backward_chunks(g, dtype) * g.C) * 3 * sizeof(double);
 }
 
-int frames_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw,
-                    void *workspace, hipStream_t st) {
+int frames_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, bool per_clip, void *gx,
+                    void *gw, void *workspace, hipStream_t st) {
     const int unit = piece_bytes(g.C * dtype_size(dtype), {go, x, gx});
-    FramesLearnParams q = make_params(g, dtype, wkind, unit);
+    FramesLearnParams q = make_params(g, dtype, wkind, unit, per_clip);
     q.rows_per_wg = static_cast<uint32_t>(backward_rows_per_wg(g, dtype));
     q.chunks = static_cast<uint32_t>(backward_chunks(g, dtype));
     q.d_chunks = make_fastdiv(q.chunks);
@@ -333,7 +342,9 @@ int frames_backward(const Geometry &g, int dtype, const void *go, const void *x,
     const int64_t groups = g.N * q.chunks;   // (below 2^31: frames_learn_geometry_ok)
     hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(groups)), dim3(kThreads), 0, st, q, static_cast<const char *>(go),
                        static_cast<const char *>(x), w, static_cast<char *>(gx), partials);
-    launch_reduce_weight_grads(wkind, partials, static_cast<int>(groups), static_cast<int>(g.C), 1, gw, st);
+    // (per clip: N * C entries below 2^31 -- the caller has checked)
+    const int64_t sums = per_clip ? q.chunks : groups, entries = per_clip ? g.N * g.C : g.C;
+    launch_reduce_weight_grads(wkind, partials, static_cast<int>(sums), static_cast<int>(entries), 1, gw, st);
     return SHIFTND_OK;
 }
 

@@ -235,20 +235,23 @@ int tshift_backward(const Geometry &g, int dtype, const void *go, const void *x,
 // along S0 of float and quantized (I8, U8, I32) tensors in memory order N, S0, S1, S2, C, `w` a [C] table, whole window; channel
 // pieces are copied from the same pixel of another frame or filled with `fill_bits`.  frames_geometry_ok: the sizes (and
 // active == 0); frames_tensor_ok: one tensor's base and strides (normalised order).  No fallback: every such call is served.
+// `per_clip` (SHIFTND_CLIP_FRAMES), here and in the learnable kernels below: `w` and `gw` are [N, C] arrays, one row per clip -- the
+// same kernels, the same workspace; the caller has checked N * C < 2^31.
 bool frames_geometry_ok(const Geometry &g, int dtype);
 bool frames_tensor_ok(const Geometry &g, int dtype, const void *p, const int64_t *strides);
-int frames_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, int64_t wzp, uint64_t fill_bits, void *out,
-                   hipStream_t st);
+int frames_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, int64_t wzp, uint64_t fill_bits, bool per_clip,
+                   void *out, hipStream_t st);
 
 // ---- the LEARNABLE temporal shift of channels-last tensors (shiftnd_frames_learn.hip; SHIFTND_SHIFT_DIM0 | SHIFTND_FRAMES): the
 // interpolating forward and the backward (sparse and interpolating) of float tensors in memory order N, S0, S1, S2, C, `w` and `gw`
 // [C] arrays, whole window; every tensor passes frames_tensor_ok.  frames_learn_geometry_ok: the sizes (frames_geometry_ok's and the
 // backward's groups).  The workspace plan depends on the geometry alone.  No fallback: every such call is served.
 bool frames_learn_geometry_ok(const Geometry &g, int dtype);
-int frames_active_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, void *out, hipStream_t st);
+int frames_active_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, bool per_clip, void *out,
+                          hipStream_t st);
 size_t frames_backward_workspace(const Geometry &g, int dtype);
-int frames_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw,
-                    void *workspace, hipStream_t st);
+int frames_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, bool per_clip, void *gx,
+                    void *gw, void *workspace, hipStream_t st);
 
 // ---- the temporal shift IN PLACE (shiftnd_inplace.hip; SHIFTND_SHIFT_DIM0 with out == x): the sparse shift along S0 of float and
 // quantized (I8, U8, I32) tensors in either dense layout, `w` a [C] table, whole window, at most 16 frames per clip; only the bytes

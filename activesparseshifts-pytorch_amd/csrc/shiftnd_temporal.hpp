@@ -47,6 +47,18 @@ template <int E, typename F> __device__ __forceinline__ void with_unit(int elems
 // source frame (segment) of coordinate p in [0, T] under the canonical shift cs (a size-1 dim ignores its shift), or -1 (fill)
 __device__ __forceinline__ int source_frame(int p, int cs, int T, int pad) { return T == 1 ? 0 : fold_index(p - cs, T, pad); }
 
+// row n of a table whose rows are `wrow` entries apart (0: a [C] table, every clip reads row 0; C: a per-clip [N, C] one).  The
+// kernels call it with a workgroup-uniform n, once per workgroup: scalar arithmetic, none of it inside their loops
+__device__ __forceinline__ const void *table_row(const void *w, int wkind, uint32_t n, uint32_t wrow) {
+    const int64_t first = static_cast<int64_t>(n) * wrow;
+    switch (wkind) {
+    case SHIFTND_F64: return static_cast<const uint64_t *>(w) + first;
+    case SHIFTND_F32: case SHIFTND_I32: return static_cast<const uint32_t *>(w) + first;
+    case SHIFTND_F16: case SHIFTND_BF16: return static_cast<const uint16_t *>(w) + first;
+    default: return static_cast<const uint8_t *>(w) + first;
+    }
+}
+
 // the type a piece of 1 << UL bytes is moved as
 template <int UL> struct piece_of;
 template <> struct piece_of<4> { typedef shiftnd_u4 type; };

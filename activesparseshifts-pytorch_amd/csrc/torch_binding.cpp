@@ -17,6 +17,8 @@
 // ... and, in namespaces of their own (registered last), the families that came after the op set of torchshifts:: was pinned:
 //   per clip      torchshifts_per_clip::temporal_shift_learnable_per_clip / _forward / _backward, temporal_shift_per_clip /
 //                 _temporal_shift_per_clip_backward: the temporal shifts under a [N, C] table, one row per clip
+//   per clip, channels-last  torchshifts_per_clip_cl::temporal_shift_learnable_per_clip_cl / _forward / _backward,
+//                 temporal_shift_per_clip_cl / _temporal_shift_per_clip_cl_backward: the same with the argument's layout kept
 //   in place      torchshifts_inplace::temporal_shift_ / temporal_shift_quantized_: the temporal shift written into the input (composes
 //                 on CPU tensors), a family that writes its argument
 //   online        torchshifts_online::temporal_shift_online_ / temporal_shift_online_quantized_: one frame per call against a cached
@@ -99,9 +101,11 @@ struct TemporalClOps {
     static auto &forward() { static auto op = typed_op<temporal_sig>("temporal_shift_cl"); return op; }
     static auto &backward() { static auto op = typed_op<temporal_sig>("_temporal_shift_cl_backward"); return op; }
 };
-// The three learnable families also carry what their HIP adapters (tsl_forward_hip / tsl_backward_hip) differ in: the names
+// The four learnable families also carry what their HIP adapters (tsl_forward_hip / tsl_backward_hip) differ in: the names
 // check_same's messages speak under, the argument check, the flag bits of the C-ABI call, the name segment_problem's refusal speaks
-// under, and whether the route takes a dense channels-last tensor as it lies (every other tensor then goes the plain family's way).
+// under, and whether the route takes a dense channels-last tensor as it lies (kAsItLies).  A family with kAsItLies MUST also name
+// `Plain`, the family every other tensor goes to; the adapters name Ops::Plain only inside `if constexpr (Ops::kAsItLies)`, so a
+// family without kAsItLies needs none and has none.
 void tsl_check(const Tensor &input, const Tensor &weights, int64_t n_segment, int64_t padding_mode);
 void tslpc_check(const Tensor &input, const Tensor &weights, int64_t n_segment, int64_t padding_mode);
 struct LearnableOps {
@@ -123,6 +127,7 @@ struct LearnableClOps {
     static constexpr int kFlags = SHIFTND_SHIFT_DIM0 | SHIFTND_FRAMES;
     static constexpr const char *kProblemName = "temporal_shift";   // (a known slip)
     static constexpr bool kAsItLies = true;
+    using Plain = LearnableOps;   // where a tensor that is not dense channels-last goes
 };
 struct PerClipLearnableOps {
     static const char *name() { return "temporal_shift_learnable_per_clip"; }
@@ -133,6 +138,17 @@ struct PerClipLearnableOps {
     static constexpr int kFlags = SHIFTND_SHIFT_DIM0 | SHIFTND_PER_CLIP;
     static constexpr const char *kProblemName = "temporal_shift_learnable_per_clip";
     static constexpr bool kAsItLies = false;
+};
+struct PerClipLearnableClOps {
+    static const char *name() { return "temporal_shift_learnable_per_clip_cl"; }
+    static auto &forward() { static auto op = typed_op<tsl_forward_sig>("_temporal_shift_learnable_per_clip_cl_forward", "torchshifts_per_clip_cl"); return op; }
+    static auto &backward() { static auto op = typed_op<tsl_backward_sig>("_temporal_shift_learnable_per_clip_cl_backward", "torchshifts_per_clip_cl"); return op; }
+    static constexpr const char *kCuda = "temporal_shift_learnable_per_clip_cl_cuda", *kBackwardCuda = "temporal_shift_learnable_per_clip_cl_backward_cuda";
+    static constexpr auto check = tslpc_check;
+    static constexpr int kFlags = SHIFTND_SHIFT_DIM0 | SHIFTND_CLIP_FRAMES;
+    static constexpr const char *kProblemName = "temporal_shift_learnable_per_clip_cl";
+    static constexpr bool kAsItLies = true;
+    using Plain = PerClipLearnableOps;   // (as LearnableClOps::Plain)
 };
 
 // ---- the double-backward guard ------------------------------------------------------------------------
@@ -1250,15 +1266,15 @@ void tsl_check_size(const Tensor &input, const char *who) {
                 "or split the batch");
 }
 
-// HIP tensors, the three learnable families (Ops: LearnableOps, LearnableClOps, PerClipLearnableOps): one flagged C-ABI call per
-// pass.  The plain and the per-clip route make their tensors contiguous, refuse what the segment-major kernels cannot count, and
-// answer an empty tensor themselves; the _cl route (Ops::kAsItLies) hands every tensor that is not dense channels-last to the plain
-// route first and then takes its tensors as they lie -- no contiguous(), no size check (the frame kernels have no such limit), no
+// HIP tensors, the four learnable families (Ops: LearnableOps, LearnableClOps, PerClipLearnableOps, PerClipLearnableClOps): one
+// flagged C-ABI call per pass.  The plain and the per-clip route make their tensors contiguous, refuse what the segment-major kernels
+// cannot count, and answer an empty tensor themselves; the _cl routes (Ops::kAsItLies) hand every tensor that is not dense
+// channels-last to their plain route (Ops::Plain) first and then take their tensors as they lie -- no contiguous(), no size check (the frame kernels have no such limit), no
 // empty tensor (none is dense channels-last), results in the argument's strides (grad_x: the gradient's).
 template <class Ops>
 Tensor tsl_forward_hip(const Tensor &input_, const Tensor &weights, int64_t n_segment, int64_t padding_mode, bool active_flag) {
     if constexpr (Ops::kAsItLies)
-        if (!is_channels_last_dense(input_)) return tsl_forward_hip<LearnableOps>(input_, weights, n_segment, padding_mode, active_flag);
+        if (!is_channels_last_dense(input_)) return tsl_forward_hip<typename Ops::Plain>(input_, weights, n_segment, padding_mode, active_flag);
     TORCH_CHECK(input_.is_cuda(), Ops::name(), ": expected a CUDA tensor");
     Ops::check(input_, weights, n_segment, padding_mode);
     const int mixed = weights_flag(Ops::kCuda, input_, "input", weights);
@@ -1283,7 +1299,7 @@ std::tuple<Tensor, Tensor> tsl_backward_hip(const Tensor &grad_, const Tensor &w
                                             int64_t padding_mode, bool active_flag) {
     if constexpr (Ops::kAsItLies)
         if (!is_channels_last_dense(input_) || !is_channels_last_dense(grad_) || grad_.sizes() != input_.sizes())
-            return tsl_backward_hip<LearnableOps>(grad_, weights, input_, n_segment, padding_mode, active_flag);   // (contiguous grad_x)
+            return tsl_backward_hip<typename Ops::Plain>(grad_, weights, input_, n_segment, padding_mode, active_flag);   // (contiguous grad_x)
     TORCH_CHECK(grad_.is_cuda() && input_.is_cuda(), Ops::name(), ": expected CUDA tensors");
     Ops::check(input_, weights, n_segment, padding_mode);
     check_same(Ops::kBackwardCuda, grad_, "grad", input_, "input");
@@ -1344,6 +1360,11 @@ struct PerClipOps {   // (the learnable pair: PerClipLearnableOps, beside Learna
     static auto &forward() { static auto op = typed_op<temporal_sig>("temporal_shift_per_clip", "torchshifts_per_clip"); return op; }
     static auto &backward() { static auto op = typed_op<temporal_sig>("_temporal_shift_per_clip_backward", "torchshifts_per_clip"); return op; }
 };
+struct PerClipClOps {   // (the learnable pair: PerClipLearnableClOps)
+    static const char *name() { return "temporal_shift_per_clip_cl"; }
+    static auto &forward() { static auto op = typed_op<temporal_sig>("temporal_shift_per_clip_cl", "torchshifts_per_clip_cl"); return op; }
+    static auto &backward() { static auto op = typed_op<temporal_sig>("_temporal_shift_per_clip_cl_backward", "torchshifts_per_clip_cl"); return op; }
+};
 
 void tslpc_check(const Tensor &input, const Tensor &weights, int64_t n_segment, int64_t padding_mode) {
     TORCH_CHECK(!input.is_quantized(), "temporal_shift_learnable_per_clip: quantized inputs are not supported");
@@ -1357,27 +1378,29 @@ void tpc_check(const Tensor &input, const Tensor &shifts, int64_t n_segment, int
 }
 
 // the public entry and the Autograd-key kernels: the nodes are temporal_shift_learnable's (input and weights kept) and
-// temporal_shift's (the table alone kept)
-Tensor tslpc_public(const Tensor &input, const Tensor &weights, int64_t n_segment, int64_t padding_mode, bool active_flag) {
+// temporal_shift's (the table alone kept).  Ops: PerClipLearnableOps / PerClipOps, and the _cl families' PerClipLearnableClOps /
+// PerClipClOps
+template <class Ops> Tensor tslpc_public(const Tensor &input, const Tensor &weights, int64_t n_segment, int64_t padding_mode, bool active_flag) {
     tslpc_check(input, weights, n_segment, padding_mode);
-    return PerClipLearnableOps::forward().call(input, weights, n_segment, padding_mode, active_flag);
+    return Ops::forward().call(input, weights, n_segment, padding_mode, active_flag);
 }
-Tensor tslpc_autograd(const Tensor &input, const Tensor &weights, int64_t n_segment, int64_t padding_mode, bool active_flag) {
+template <class Ops> Tensor tslpc_autograd(const Tensor &input, const Tensor &weights, int64_t n_segment, int64_t padding_mode, bool active_flag) {
     tslpc_check(input, weights, n_segment, padding_mode);
-    return LearnableTemporalShiftFunction<PerClipLearnableOps>::apply(input, weights, n_segment, padding_mode, active_flag)[0];
+    return LearnableTemporalShiftFunction<Ops>::apply(input, weights, n_segment, padding_mode, active_flag)[0];
 }
+template <class Ops>
 std::tuple<Tensor, Tensor> tslpc_autograd_backward(const Tensor &grad, const Tensor &weights, const Tensor &input, int64_t n_segment,
                                                    int64_t padding_mode, bool active_flag) {
     tslpc_check(input, weights, n_segment, padding_mode);
-    return GuardedBackward<PerClipLearnableOps>::kernel(grad, weights, input, n_segment, padding_mode, active_flag);
+    return GuardedBackward<Ops>::kernel(grad, weights, input, n_segment, padding_mode, active_flag);
 }
-Tensor tpc_autograd(const Tensor &input, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+template <class Ops> Tensor tpc_autograd(const Tensor &input, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
     tpc_check(input, shifts, n_segment, padding_mode);
-    return TemporalShiftFunction<PerClipOps>::apply(input, shifts, n_segment, padding_mode)[0];
+    return TemporalShiftFunction<Ops>::apply(input, shifts, n_segment, padding_mode)[0];
 }
-Tensor tpc_autograd_backward(const Tensor &grad, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+template <class Ops> Tensor tpc_autograd_backward(const Tensor &grad, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
     tpc_check(grad, shifts, n_segment, padding_mode);
-    return GuardedBackward<PerClipOps>::kernel(grad, shifts, n_segment, padding_mode);
+    return GuardedBackward<Ops>::kernel(grad, shifts, n_segment, padding_mode);
 }
 
 // CPU tensors: the loop of the definition over the per-channel CPU routines
@@ -1428,15 +1451,19 @@ Tensor tpc_backward_cpu(const Tensor &grad, const Tensor &shifts, int64_t n_segm
 
 // HIP tensors: one call under SHIFTND_SHIFT_DIM0 | SHIFTND_PER_CLIP on the segment-major strides (the learnable pair: tsl_forward_hip /
 // tsl_backward_hip under PerClipLearnableOps)
-Tensor tpc_hip(const Tensor &t_, const Tensor &shifts, int64_t n_segment, int64_t padding_mode, bool backward) {
+// `as_it_lies` (the _cl op): a dense channels-last tensor is the call under SHIFTND_SHIFT_DIM0 | SHIFTND_CLIP_FRAMES on the tensor as it
+// lies (shiftnd_frames.hip) -- no contiguous(), no size check (the frame kernels have no such limit), the result in the argument's
+// strides; every other tensor goes the plain way
+Tensor tpc_hip(const Tensor &t_, const Tensor &shifts, int64_t n_segment, int64_t padding_mode, bool backward, bool as_it_lies = false) {
     TORCH_CHECK(t_.is_cuda(), "temporal_shift_per_clip: expected a CUDA tensor");
     tpc_check(t_, shifts, n_segment, padding_mode);
     c10::DeviceGuard device_guard(t_.device());
     const bool half = t_.scalar_type() == at::kHalf || t_.scalar_type() == at::kBFloat16;
     const int dtype = to_shiftnd_dtype(t_.scalar_type(), "temporal_shift_per_clip_cuda") | (half ? SHIFTND_WEIGHTS_F32 : 0);
-    tsl_check_size(t_, "temporal_shift_per_clip");
-    const Tensor t = t_.contiguous();
-    Tensor out = at::empty(t.sizes(), t.options(), at::MemoryFormat::Contiguous);
+    const bool lies = as_it_lies && is_channels_last_dense(t_);
+    if (!lies) tsl_check_size(t_, "temporal_shift_per_clip");
+    const Tensor t = lies ? t_ : t_.contiguous();
+    Tensor out = lies ? at::empty_strided(t.sizes(), t.strides(), t.options()) : at::empty(t.sizes(), t.options(), at::MemoryFormat::Contiguous);
     if (t.numel() == 0) return out;
     Tensor w = shifts.detach();
     if (at::isFloatingType(w.scalar_type())) w = w.round();   // (half to even, before the table's type can move an entry onto a half)
@@ -1446,8 +1473,10 @@ Tensor tpc_hip(const Tensor &t_, const Tensor &shifts, int64_t n_segment, int64_
     w = (backward ? w.neg() : w).contiguous();
     shiftnd_problem p;
     int64_t st[5];
-    segment_problem(p, st, t, n_segment, padding_mode, false, dtype | SHIFTND_SHIFT_DIM0 | SHIFTND_PER_CLIP, false, "temporal_shift_per_clip");
-    check_status(shiftnd_forward(&p, t.data_ptr(), st, w.data_ptr(), out.data_ptr(), st, current_stream(t)), "temporal_shift_per_clip (HIP)");
+    segment_problem(p, st, t, n_segment, padding_mode, false, dtype | SHIFTND_SHIFT_DIM0 | (lies ? SHIFTND_CLIP_FRAMES : SHIFTND_PER_CLIP), lies,
+                    lies ? "temporal_shift_per_clip_cl" : "temporal_shift_per_clip");
+    check_status(shiftnd_forward(&p, t.data_ptr(), st, w.data_ptr(), out.data_ptr(), st, current_stream(t)),
+                 lies ? "temporal_shift_per_clip_cl (HIP)" : "temporal_shift_per_clip (HIP)");
     return out;
 }
 Tensor tpc_forward_hip(const Tensor &input, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
@@ -1455,6 +1484,36 @@ Tensor tpc_forward_hip(const Tensor &input, const Tensor &shifts, int64_t n_segm
 }
 Tensor tpc_backward_hip(const Tensor &grad, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
     return tpc_hip(grad, shifts, n_segment, padding_mode, true);
+}
+
+// ---- channels-last per-clip temporal shift: torchshifts_per_clip_cl::temporal_shift_learnable_per_clip_cl / temporal_shift_per_clip_cl --
+// The values and gradients of the per-clip ops with the layout of the argument kept (memory_format=torch.preserve_format in the
+// Python wrappers).  On HIP tensors a dense channels-last input is ONE C-ABI call per pass on the tensors as they lie, under
+// SHIFTND_SHIFT_DIM0 | SHIFTND_CLIP_FRAMES (the frame kernels under a row stride): the learnable pair through tsl_forward_hip /
+// tsl_backward_hip under PerClipLearnableClOps -- the backward takes the route when the saved input and the gradient are both dense
+// channels-last, grad_x then has the gradient's strides -- the fixed op through tpc_hip, whose backward is the forward call on the
+// gradient under the negated table.  Every other HIP tensor goes the plain per-clip op's way.  CPU tensors: the per-clip CPU routines
+// compute and the results are laid into the arguments' strides.  The entry, the nodes and the Autograd-key kernels are the per-clip
+// family's under PerClipLearnableClOps / PerClipClOps; a namespace of its own, so that the op set of torchshifts_per_clip:: stays.
+Tensor tslpc_cl_forward_cpu(const Tensor &input, const Tensor &weights, int64_t n_segment, int64_t padding_mode, bool active_flag) {
+    return in_layout_of(tslpc_forward_cpu(input, weights, n_segment, padding_mode, active_flag), input);
+}
+std::tuple<Tensor, Tensor> tslpc_cl_backward_cpu(const Tensor &grad, const Tensor &weights, const Tensor &input, int64_t n_segment,
+                                                 int64_t padding_mode, bool active_flag) {
+    auto result = tslpc_backward_cpu(grad, weights, input, n_segment, padding_mode, active_flag);
+    return std::make_tuple(in_layout_of(std::get<0>(result), grad), std::get<1>(result));
+}
+Tensor tpc_cl_forward_cpu(const Tensor &input, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    return in_layout_of(tpc_forward_cpu(input, shifts, n_segment, padding_mode), input);
+}
+Tensor tpc_cl_backward_cpu(const Tensor &grad, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    return in_layout_of(tpc_backward_cpu(grad, shifts, n_segment, padding_mode), grad);
+}
+Tensor tpc_cl_forward_hip(const Tensor &input, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    return tpc_hip(input, shifts, n_segment, padding_mode, false, true);
+}
+Tensor tpc_cl_backward_hip(const Tensor &grad, const Tensor &shifts, int64_t n_segment, int64_t padding_mode) {
+    return tpc_hip(grad, shifts, n_segment, padding_mode, true, true);
 }
 
 // ---- in-place temporal shift: torchshifts_inplace::temporal_shift_ / temporal_shift_quantized_ -------------------------------------
@@ -1921,7 +1980,7 @@ TORCH_LIBRARY_IMPL(torchshifts, QuantizedCUDA, m) {
 
 // the per-clip temporal shifts: their own namespace (the op set of torchshifts:: is pinned)
 TORCH_LIBRARY(torchshifts_per_clip, m) {
-    m.def("torchshifts_per_clip::temporal_shift_learnable_per_clip(Tensor input, Tensor weights, int n_segment, int padding_mode, bool active_flag) -> Tensor", &tslpc_public);
+    m.def("torchshifts_per_clip::temporal_shift_learnable_per_clip(Tensor input, Tensor weights, int n_segment, int padding_mode, bool active_flag) -> Tensor", &tslpc_public<PerClipLearnableOps>);
     m.def("torchshifts_per_clip::_temporal_shift_learnable_per_clip_forward(Tensor input, Tensor weights, int n_segment, int padding_mode, bool active_flag) -> Tensor");
     m.def("torchshifts_per_clip::_temporal_shift_learnable_per_clip_backward(Tensor grad, Tensor weights, Tensor input, int n_segment, int padding_mode, bool active_flag) -> (Tensor, Tensor)");
     m.def("torchshifts_per_clip::temporal_shift_per_clip(Tensor input, Tensor shifts, int n_segment, int padding_mode) -> Tensor");
@@ -1929,10 +1988,10 @@ TORCH_LIBRARY(torchshifts_per_clip, m) {
 }
 
 TORCH_LIBRARY_IMPL(torchshifts_per_clip, Autograd, m) {
-    m.impl("_temporal_shift_learnable_per_clip_forward", TORCH_FN(tslpc_autograd));
-    m.impl("_temporal_shift_learnable_per_clip_backward", TORCH_FN(tslpc_autograd_backward));
-    m.impl("temporal_shift_per_clip", TORCH_FN(tpc_autograd));
-    m.impl("_temporal_shift_per_clip_backward", TORCH_FN(tpc_autograd_backward));
+    m.impl("_temporal_shift_learnable_per_clip_forward", TORCH_FN(tslpc_autograd<PerClipLearnableOps>));
+    m.impl("_temporal_shift_learnable_per_clip_backward", TORCH_FN(tslpc_autograd_backward<PerClipLearnableOps>));
+    m.impl("temporal_shift_per_clip", TORCH_FN(tpc_autograd<PerClipOps>));
+    m.impl("_temporal_shift_per_clip_backward", TORCH_FN(tpc_autograd_backward<PerClipOps>));
 }
 TORCH_LIBRARY_IMPL(torchshifts_per_clip, CPU, m) {
     m.impl("_temporal_shift_learnable_per_clip_forward", TORCH_FN(tslpc_forward_cpu));
@@ -1945,6 +2004,33 @@ TORCH_LIBRARY_IMPL(torchshifts_per_clip, CUDA, m) {
     m.impl("_temporal_shift_learnable_per_clip_backward", TORCH_FN(tsl_backward_hip<PerClipLearnableOps>));
     m.impl("temporal_shift_per_clip", TORCH_FN(tpc_forward_hip));
     m.impl("_temporal_shift_per_clip_backward", TORCH_FN(tpc_backward_hip));
+}
+
+// the per-clip temporal shifts with the argument's layout kept: a namespace of its own, so that torchshifts_per_clip:: keeps its op set
+TORCH_LIBRARY(torchshifts_per_clip_cl, m) {
+    m.def("torchshifts_per_clip_cl::temporal_shift_learnable_per_clip_cl(Tensor input, Tensor weights, int n_segment, int padding_mode, bool active_flag) -> Tensor", &tslpc_public<PerClipLearnableClOps>);
+    m.def("torchshifts_per_clip_cl::_temporal_shift_learnable_per_clip_cl_forward(Tensor input, Tensor weights, int n_segment, int padding_mode, bool active_flag) -> Tensor");
+    m.def("torchshifts_per_clip_cl::_temporal_shift_learnable_per_clip_cl_backward(Tensor grad, Tensor weights, Tensor input, int n_segment, int padding_mode, bool active_flag) -> (Tensor, Tensor)");
+    m.def("torchshifts_per_clip_cl::temporal_shift_per_clip_cl(Tensor input, Tensor shifts, int n_segment, int padding_mode) -> Tensor");
+    m.def("torchshifts_per_clip_cl::_temporal_shift_per_clip_cl_backward(Tensor grad, Tensor shifts, int n_segment, int padding_mode) -> Tensor");
+}
+TORCH_LIBRARY_IMPL(torchshifts_per_clip_cl, Autograd, m) {
+    m.impl("_temporal_shift_learnable_per_clip_cl_forward", TORCH_FN(tslpc_autograd<PerClipLearnableClOps>));
+    m.impl("_temporal_shift_learnable_per_clip_cl_backward", TORCH_FN(tslpc_autograd_backward<PerClipLearnableClOps>));
+    m.impl("temporal_shift_per_clip_cl", TORCH_FN(tpc_autograd<PerClipClOps>));
+    m.impl("_temporal_shift_per_clip_cl_backward", TORCH_FN(tpc_autograd_backward<PerClipClOps>));
+}
+TORCH_LIBRARY_IMPL(torchshifts_per_clip_cl, CPU, m) {
+    m.impl("_temporal_shift_learnable_per_clip_cl_forward", TORCH_FN(tslpc_cl_forward_cpu));
+    m.impl("_temporal_shift_learnable_per_clip_cl_backward", TORCH_FN(tslpc_cl_backward_cpu));
+    m.impl("temporal_shift_per_clip_cl", TORCH_FN(tpc_cl_forward_cpu));
+    m.impl("_temporal_shift_per_clip_cl_backward", TORCH_FN(tpc_cl_backward_cpu));
+}
+TORCH_LIBRARY_IMPL(torchshifts_per_clip_cl, CUDA, m) {
+    m.impl("_temporal_shift_learnable_per_clip_cl_forward", TORCH_FN(tsl_forward_hip<PerClipLearnableClOps>));
+    m.impl("_temporal_shift_learnable_per_clip_cl_backward", TORCH_FN(tsl_backward_hip<PerClipLearnableClOps>));
+    m.impl("temporal_shift_per_clip_cl", TORCH_FN(tpc_cl_forward_hip));
+    m.impl("_temporal_shift_per_clip_cl_backward", TORCH_FN(tpc_cl_backward_hip));
 }
 
 // the in-place temporal shift: its own namespace (the op set of torchshifts:: is pinned)

@@ -23,6 +23,8 @@ PER_CLIP = 0x1000     # SHIFTND_PER_CLIP: with SHIFT_DIM0 -- weights / grad_w ar
 #                       kernels, forward (both modes) and backward (0x800 is not assigned)
 STREAM = 0x2000       # SHIFTND_STREAM: with SHIFT_DIM0 -- one step of the online temporal shift: sizes {B, C, D, spatial...}, x the state
 #                       (read and written, the slot stride in the S0 place), out the frame (read and written), w the [C] table
+CLIP_FRAMES = 0x4000  # SHIFTND_CLIP_FRAMES: with SHIFT_DIM0 -- every tensor is dense channels-last as under FRAMES and weights / grad_w are
+#                       [N, C] as under PER_CLIP; the frame kernels serve forward (both modes) and backward, or the call is refused
 PATH_NONE, PATH_EMPTY, PATH_PLANE, PATH_STRIDED, PATH_SWEEP, PATH_CL = range(6)
 
 DTYPES = {torch.float32: F32, torch.float64: F64, torch.float16: F16, torch.bfloat16: BF16,
@@ -135,13 +137,15 @@ def check_borders(sizes, user, ndim):
     return list(out), list(new)[:shift + min(ndim, 3)]
 
 
-def problem(x, pad, active, borders, dtype=None, w=None, shift_dim0=False, frames=False, per_clip=False, stream=False):
+def problem(x, pad, active, borders, dtype=None, w=None, shift_dim0=False, frames=False, per_clip=False, stream=False,
+            clip_frames=False):
     """w: the weights of the call, if it has float weights -- fp32 weights with an fp16 / bf16 `x` set WEIGHTS_F32 (mixed precision);
     shift_dim0: set SHIFT_DIM0 (the temporal shift: w is [C] and acts on spatial dim 0; x a segment-major view, or, for the
     sparse forward and the quantized forward, a dense channels-last view [N, C, T, M] with strides {T*M*C, 1, M*C, C});
     frames: set FRAMES (with shift_dim0: every tensor is such a dense channels-last view, forward in both modes and backward);
     per_clip: set PER_CLIP (with shift_dim0: w is [N, C], one row per clip, x a segment-major view);
-    stream: set STREAM (with shift_dim0: x is the state viewed as [B, C, D, M], see online_views)"""
+    stream: set STREAM (with shift_dim0: x is the state viewed as [B, C, D, M], see online_views);
+    clip_frames: set CLIP_FRAMES (with shift_dim0: w is [N, C], one row per clip, every tensor a dense channels-last view)"""
     p = Problem()
     p.ndim = x.dim() - 2
     p.dtype = DTYPES[x.dtype] if dtype is None else dtype
@@ -155,6 +159,8 @@ def problem(x, pad, active, borders, dtype=None, w=None, shift_dim0=False, frame
         p.dtype |= PER_CLIP
     if stream:
         p.dtype |= STREAM
+    if clip_frames:
+        p.dtype |= CLIP_FRAMES
     p.padding_mode = int(pad)
     p.active = int(bool(active))
     for i in range(5):
@@ -174,13 +180,14 @@ def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def forward(x, w, pad, active, borders=None, out=None, shift_dim0=False, frames=False, per_clip=False):
+def forward(x, w, pad, active, borders=None, out=None, shift_dim0=False, frames=False, per_clip=False, clip_frames=False):
     """x, w: device tensors (float dtypes; w of x's dtype, or fp32 with an fp16 / bf16 x).  Returns a new contiguous output (or
     fills `out`).  shift_dim0: the flagged call (w [C]; x and out segment-major views, or -- active False -- both dense
     channels-last views, memory order N, S0, S1, S2, C: pass `out`, a new output is contiguous).  frames: with shift_dim0, the
     channels-last call in both modes (pass `out`).  out=x with shift_dim0 (active False): the in-place call, either dense layout.
-    per_clip: with shift_dim0, w is [N, C] and x, out are segment-major views."""
-    p = problem(x, pad, active, borders, w=w, shift_dim0=shift_dim0, frames=frames, per_clip=per_clip)
+    per_clip: with shift_dim0, w is [N, C] and x, out are segment-major views.  clip_frames: with shift_dim0, w is [N, C] and x, out
+    are dense channels-last views (pass `out`)."""
+    p = problem(x, pad, active, borders, w=w, shift_dim0=shift_dim0, frames=frames, per_clip=per_clip, clip_frames=clip_frames)
     if out is None:
         out = _new(out_shape(x, borders), x)
     w = w.contiguous()
@@ -189,23 +196,24 @@ def forward(x, w, pad, active, borders=None, out=None, shift_dim0=False, frames=
     return out
 
 
-def backward_workspace(x, pad, active, borders=None, shift_dim0=False, frames=False, per_clip=False):
-    p = problem(x, pad, active, borders, shift_dim0=shift_dim0, frames=frames, per_clip=per_clip)
+def backward_workspace(x, pad, active, borders=None, shift_dim0=False, frames=False, per_clip=False, clip_frames=False):
+    p = problem(x, pad, active, borders, shift_dim0=shift_dim0, frames=frames, per_clip=per_clip, clip_frames=clip_frames)
     return torch.empty(int(lib().shiftnd_backward_workspace_bytes(ctypes.byref(p))), dtype=torch.uint8, device=x.device)
 
 
 def backward(grad_out, w, x, pad, active, borders=None, grad_x=None, grad_w=None, workspace=None, shift_dim0=False, frames=False,
-             per_clip=False):
+             per_clip=False, clip_frames=False):
     """grad_w comes back in w's dtype (fp32 for fp32 weights with a 16-bit x).  frames: with shift_dim0, grad_out, x and grad_x are
-    dense channels-last views (pass `grad_x`).  per_clip: with shift_dim0, w and grad_w are [N, C]"""
-    p = problem(x, pad, active, borders, w=w, shift_dim0=shift_dim0, frames=frames, per_clip=per_clip)
+    dense channels-last views (pass `grad_x`).  per_clip: with shift_dim0, w and grad_w are [N, C].  clip_frames: with shift_dim0,
+    both: dense channels-last views (pass `grad_x`), w and grad_w [N, C]"""
+    p = problem(x, pad, active, borders, w=w, shift_dim0=shift_dim0, frames=frames, per_clip=per_clip, clip_frames=clip_frames)
     w = w.contiguous()
     if grad_x is None:
         grad_x = _new(x.shape, x)
     if grad_w is None:
         grad_w = _new(w.shape, w)
     if workspace is None:
-        workspace = backward_workspace(x, pad, active, borders, shift_dim0, frames, per_clip)
+        workspace = backward_workspace(x, pad, active, borders, shift_dim0, frames, per_clip, clip_frames)
     check(lib().shiftnd_backward(ctypes.byref(p), grad_out.data_ptr(), strides5(grad_out), x.data_ptr(), strides5(x),
                                  w.data_ptr(), grad_x.data_ptr(), strides5(grad_x), grad_w.data_ptr(),
                                  workspace.data_ptr(), workspace.numel(), _stream()), "shiftnd_backward")

@@ -270,6 +270,12 @@ def temporal_shift_learnable_func(input: Tensor, weights: Tensor, n_segment: int
 # x.grad carry the loop's bits, weights.grad is deterministic.  The result is contiguous.
 # The table is [N, n_channels], or [N, n_groups] with n_channels % n_groups == 0 (TIN's groups: entry g serves the n_channels //
 # n_groups consecutive channels of group g); a group table is expanded here, so autograd sums a group's gradient.
+#
+# memory_format: torch.contiguous_format (the default) is the call above.  With torch.preserve_format a dense channels-last input (as
+# for temporal_shift_func) comes back in its own strides with the same values, and x.grad takes the layout of the incoming gradient
+# when that is dense channels-last too; every other input gives what the default gives.  On HIP tensors the channels-last tensors
+# are served as they lie, one kernel per pass (the frame kernels under the clip's row of the table), no layout change in either
+# direction.  A group table whose groups are whole 16-byte pieces of a pixel's channel row takes those kernels' fast path.
 def _per_clip_table(name: str, input: Tensor, table: Tensor, n_segment: int, padding_mode: int, kind: str) -> Tensor:
     _assert_has_ops()
     assert padding_mode in [0, 1, 2, 3, 4], f"{name} expected padding_mode can be {_PADDING_DOC}"
@@ -289,21 +295,35 @@ def _per_clip_table(name: str, input: Tensor, table: Tensor, n_segment: int, pad
     return table
 
 
-def temporal_shift_per_clip_func(input: Tensor, shifts: Tensor, n_segment: int, padding_mode: int = 0) -> Tensor:
+def temporal_shift_per_clip_func(input: Tensor, shifts: Tensor, n_segment: int, padding_mode: int = 0,
+                                 memory_format: torch.memory_format = torch.contiguous_format) -> Tensor:
     """Shift the channels of a [N * n_segment, C, ...] tensor (2 to 5 dims) across the frames of each clip by the integers
-    shifts[n, c] of its own clip n.  Floats are rounded half to even; the autograd node keeps the table alone."""
+    shifts[n, c] of its own clip n.  Floats are rounded half to even; the autograd node keeps the table alone.
+    memory_format=torch.preserve_format keeps a dense channels-last input's layout.  On the GPU it pays under a GROUP table whose
+    groups span whole 16-byte pieces of a pixel's channel row (8 fp16 / 4 fp32 channels or more); under an ungrouped [N, C] table
+    keep the default: the backward then moves channels one by one and is slower than the default route with its layout changes."""
     name = "temporal_shift_per_clip_func()"
+    assert memory_format in (torch.contiguous_format, torch.preserve_format), \
+        f"{name} expected memory_format to be torch.contiguous_format or torch.preserve_format, but it is {memory_format}"
     shifts = _per_clip_table(name, input, shifts, n_segment, padding_mode, "shifts")
+    if memory_format == torch.preserve_format:
+        return torch.ops.torchshifts_per_clip_cl.temporal_shift_per_clip_cl(input, shifts, n_segment, padding_mode)
     return torch.ops.torchshifts_per_clip.temporal_shift_per_clip(input, shifts, n_segment, padding_mode)
 
 
 def temporal_shift_learnable_per_clip_func(input: Tensor, weights: Tensor, n_segment: int, padding_mode: int = 0,
-                                           active_flag: bool = False) -> Tensor:
+                                           active_flag: bool = False,
+                                           memory_format: torch.memory_format = torch.contiguous_format) -> Tensor:
     """Shift the channels of a [N * n_segment, C, ...] tensor (2 to 5 dims) across the frames of each clip by weights[n, c] of its
     own clip n, sparse (rounded) or active (interpolated); differentiable in input and weights."""
     name = "temporal_shift_learnable_per_clip_func()"
+    assert memory_format in (torch.contiguous_format, torch.preserve_format), \
+        f"{name} expected memory_format to be torch.contiguous_format or torch.preserve_format, but it is {memory_format}"
     assert weights.is_floating_point(), f"{name}: expected float weights, but they are {weights.dtype}"
     weights = _per_clip_table(name, input, weights, n_segment, padding_mode, "weights")
+    if memory_format == torch.preserve_format:
+        return torch.ops.torchshifts_per_clip_cl.temporal_shift_learnable_per_clip_cl(input, weights, n_segment, padding_mode,
+                                                                                      bool(active_flag))
     return torch.ops.torchshifts_per_clip.temporal_shift_learnable_per_clip(input, weights, n_segment, padding_mode, bool(active_flag))
 
 

@@ -519,23 +519,31 @@ class PerClipTemporalShift(nn.Module):
     Arguments:
         n_segment (int): frames per clip, T.
         padding (str): 'zeros' | 'border' | 'periodic' | 'reflect' | 'symmetric'. Default 'zeros'.
+        memory_format: torch.contiguous_format (default: a contiguous output) or torch.preserve_format (a dense channels-last
+            input comes back channels-last; on the GPU it is shifted as it lies, without a layout change).  Choose it with a group
+            table [N, G] whose groups span whole 16-byte pieces of a pixel's channel row (8 fp16 / 4 fp32 channels or more); under
+            an ungrouped [N, C] table keep the default, whose backward is faster although it changes the layout twice.
     forward(x, table) -> output, the tensor alone.  table: [N, C] integers (floats are rounded half to even), or [N, G] with
     C % G == 0, entry g serving the C // G consecutive channels of group g.
     """
 
-    def __init__(self, n_segment, padding='zeros'):
+    def __init__(self, n_segment, padding='zeros', memory_format=torch.contiguous_format):
         super().__init__()
         assert padding.lower() in paddings_dict.keys(), f'incorrect padding option: {padding}'
         assert int(n_segment) >= 1, 'n_segment must be >= 1'
+        assert memory_format in (torch.contiguous_format, torch.preserve_format), \
+            f'memory_format must be torch.contiguous_format or torch.preserve_format, not {memory_format}'
         self.padding = paddings_dict[padding.lower()]
         self.n_segment = int(n_segment)
+        self.memory_format = memory_format
 
     def forward(self, input, table):
-        return temporal_shift_per_clip_func(input, table, self.n_segment, self.padding)
+        return temporal_shift_per_clip_func(input, table, self.n_segment, self.padding, self.memory_format)
 
     def extra_repr(self):
         pad = {v: k for k, v in paddings_dict.items()}[self.padding]
-        return f'n_segment={self.n_segment}, padding_method={pad}, per-clip integer shifts'
+        fmt = '' if self.memory_format == torch.contiguous_format else f', memory_format={self.memory_format}'
+        return f'n_segment={self.n_segment}, padding_method={pad}, per-clip integer shifts' + fmt
 
 
 class LearnablePerClipTemporalShift(nn.Module):
@@ -548,22 +556,30 @@ class LearnablePerClipTemporalShift(nn.Module):
         n_segment (int): frames per clip, T.
         padding (str): 'zeros' | 'border' | 'periodic' | 'reflect' | 'symmetric'. Default 'zeros'.
         active_flag (bool): interpolate on the forward pass (active shift). Default False.
+        memory_format: torch.contiguous_format (default: a contiguous output) or torch.preserve_format (a dense channels-last
+            input comes back channels-last, x.grad in the layout of the incoming gradient; on the GPU both passes run on the
+            tensors as they lie).
     forward(x, table) -> output, the tensor alone.  table: [N, C] floats of the input's dtype (float32 with a float16 / bfloat16
     input works too), or [N, G] with C % G == 0 (TIN's groups): a group's gradient is the sum over its channels.
     """
 
-    def __init__(self, n_segment, padding='zeros', active_flag=False):
+    def __init__(self, n_segment, padding='zeros', active_flag=False, memory_format=torch.contiguous_format):
         super().__init__()
         assert padding.lower() in paddings_dict.keys(), f'incorrect padding option: {padding}'
         assert int(n_segment) >= 1, 'n_segment must be >= 1'
+        assert memory_format in (torch.contiguous_format, torch.preserve_format), \
+            f'memory_format must be torch.contiguous_format or torch.preserve_format, not {memory_format}'
         self.padding = paddings_dict[padding.lower()]
         self.n_segment = int(n_segment)
         self._active_flag = active_flag
+        self.memory_format = memory_format
 
     def forward(self, input, table):
-        return temporal_shift_learnable_per_clip_func(input, table, self.n_segment, self.padding, self._active_flag)
+        return temporal_shift_learnable_per_clip_func(input, table, self.n_segment, self.padding, self._active_flag,
+                                                      self.memory_format)
 
     def extra_repr(self):
         pad = {v: k for k, v in paddings_dict.items()}[self.padding]
         active = f'Active shift on forward pass: {"Yes" if self._active_flag else "No"}'
-        return f'n_segment={self.n_segment}, padding_method={pad}, {active}, per-clip weights'
+        fmt = '' if self.memory_format == torch.contiguous_format else f', memory_format={self.memory_format}'
+        return f'n_segment={self.n_segment}, padding_method={pad}, {active}, per-clip weights' + fmt

@@ -228,6 +228,31 @@ typedef enum shiftnd_dtype {
  */
 #define SHIFTND_STREAM 0x2000
 
+/*
+ * The temporal shift under a PER-CLIP table on CHANNELS-LAST tensors: SHIFTND_PER_CLIP's table on SHIFTND_FRAMES' layout, under a
+ * bit of its own (SHIFTND_FRAMES | SHIFTND_PER_CLIP stays refused).  OR-ed onto a float dtype TOGETHER WITH SHIFTND_SHIFT_DIM0 (and,
+ * for F16 / BF16, optionally SHIFTND_WEIGHTS_F32): the tensors are dense channels-last exactly as under SHIFTND_FRAMES (memory order
+ * N, S0, S1, S2, C; strides {T*M*C, 1, M*C, C}), and `weights` / `grad_w` are contiguous [N, C] arrays, one row per clip, exactly
+ * as under SHIFTND_PER_CLIP.  Clip n is the SHIFTND_SHIFT_DIM0 | SHIFTND_FRAMES problem {1, C, S0, S1, S2} on its own frames under
+ * row n: out and grad_x carry the bits of that call, and grad_w[n] is the fp64 sum of clip n's products in a fixed order, narrowed
+ * once to the weights' type, deterministic.
+ *   shiftnd_forward, p->active == 0: frames_forward / frames_forward_ragged;  p->active == 1: frames_active_forward / *_ragged.
+ *   shiftnd_backward, full form: frames_backward / *_ragged.  The same kernels as under SHIFTND_FRAMES -- the table's row stride is
+ *   a run-time field of theirs, and a workgroup lies inside one clip, so it forms its row's base once.
+ *   shiftnd_backward_workspace_bytes: the bytes it answers for the same geometry under SHIFTND_FRAMES (the partial records are
+ *   re-indexed, not multiplied); sizeof(double) for an empty problem.
+ *   Served calls report SHIFTND_PATH_CL; an empty problem SHIFTND_PATH_EMPTY, with the N * C entries of grad_w zeroed.
+ *   Accepted: what SHIFTND_FRAMES accepts (ndim 2 or 3; F32, F64, F16, BF16; every padding mode; the whole window; element-aligned
+ *   bases; its bounds), and N * C below 2^31.
+ *   Errors, before anything is launched (the workspace query answers 0): a quantized dtype, the bit on shiftnd_forward_quantized or
+ *   on the pooled entry points, and the bit without SHIFTND_SHIFT_DIM0 (an unknown dtype bit, on every entry point):
+ *   SHIFTND_ERR_UNSUPPORTED_DTYPE; the bit beside SHIFTND_FRAMES, SHIFTND_PER_CLIP or SHIFTND_STREAM, out == x, ndim 1, a cut
+ *   window, any tensor that is not dense channels-last, the x == NULL form of shiftnd_backward, N * C of 2^31 or more, a size
+ *   beyond the bounds: SHIFTND_ERR_INVALID_ARGUMENT; a workspace below the plan: SHIFTND_ERR_WORKSPACE_TOO_SMALL.
+ * Without the bit nothing changes.  (0x800 stays unassigned.)
+ */
+#define SHIFTND_CLIP_FRAMES 0x4000
+
 typedef enum shiftnd_status {
     SHIFTND_OK = 0,
     SHIFTND_ERR_INVALID_ARGUMENT = -1,
@@ -251,7 +276,7 @@ typedef enum shiftnd_path {
 /* Problem geometry shared by the entry points. */
 typedef struct shiftnd_problem {
     int32_t ndim;          /* spatial dims: 1, 2 or 3 */
-    int32_t dtype;         /* shiftnd_dtype of input/output (and of float weights), optionally | SHIFTND_WEIGHTS_F32 | SHIFTND_SHIFT_DIM0 | SHIFTND_FRAMES | SHIFTND_PER_CLIP | SHIFTND_STREAM */
+    int32_t dtype;         /* shiftnd_dtype of input/output (and of float weights), optionally | SHIFTND_WEIGHTS_F32 | SHIFTND_SHIFT_DIM0 | SHIFTND_FRAMES | SHIFTND_PER_CLIP | SHIFTND_STREAM | SHIFTND_CLIP_FRAMES */
     int32_t padding_mode;  /* 0..4 */
     int32_t active;        /* 0: sparse shift (rounded integer shift); 1: active (interpolated) */
     int64_t sizes[5];      /* input N, C, H, W, D */
