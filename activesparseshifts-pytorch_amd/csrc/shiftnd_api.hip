@@ -455,6 +455,84 @@ int tshift_backward_call(const shiftnd_problem *p, const void *go, const int64_t
     return finish(tshift_backward(g, q.dtype, go, x, w, wkind, per_clip, gx, gw, workspace, st));
 }
 
+// ---- SHIFTND_SHIFT_DIM0 | SHIFTND_INTERLACE: temporal interlacing (shiftnd_interlace.hip) -- the per-clip shift times a scale per
+// (n, t, c) plane.  `weights` / `grad_w` are ONE packed array each, [N, C] offsets followed by [N, S0, C] scales.  Segment-major
+// tensors alone, out of place, under the geometry and limits of SHIFTND_PER_CLIP; served by its own kernels or refused before
+// anything is launched.  No other form under SHIFTND_SHIFT_DIM0 combines with the bit.
+// -> the problem without the flag bits in `q`, the weights' type in `wkind`
+int interlace_problem(const shiftnd_problem *p, shiftnd_problem &q, int &wkind) {
+    constexpr int others = SHIFTND_FRAMES | SHIFTND_PER_CLIP | SHIFTND_STREAM | SHIFTND_CLIP_FRAMES;
+    shiftnd_problem r = *p;
+    r.dtype = p->dtype & ~(SHIFTND_SHIFT_DIM0 | SHIFTND_INTERLACE | others);
+    if (split_dtype(&r, q, wkind) != SHIFTND_OK || !is_float_dtype(q.dtype)) return SHIFTND_ERR_UNSUPPORTED_DTYPE;
+    return (p->dtype & others) ? SHIFTND_ERR_INVALID_ARGUMENT : SHIFTND_OK;
+}
+
+// tshift_geometry_ok's sizes, the [N, C] offsets indexed in 32 bits, and N * S0 * C < 2^31: the scales' index and the entry count of
+// their reduction.  (tshift_geometry_ok implies the last two today; they are stated because the kernels rest on them.)
+bool interlace_sizes_ok(const Geometry &g, int dtype) {
+    if (!tshift_geometry_ok(g, dtype) || !per_clip_table_ok(g)) return false;
+    return g.N * g.S[3 - g.nd] * g.C < (1LL << 31);   // (N * S0 and C are below 2^31 here: no overflow)
+}
+
+int interlace_forward_call(const shiftnd_problem *p, const void *x, const int64_t *xs, const void *w, void *out, const int64_t *os,
+                           void *stream) {
+    shiftnd_problem q;
+    int wkind;
+    int rc = interlace_problem(p, q, wkind);
+    if (rc != SHIFTND_OK) return rc;
+    if (out && out == x) return SHIFTND_ERR_INVALID_ARGUMENT;   // (the in-place form takes a [C] table alone)
+    Geometry g;
+    rc = build_geometry(&q, xs, os, nullptr, g);
+    if (rc != SHIFTND_OK) return rc;
+    if (!interlace_sizes_ok(g, q.dtype)) return SHIFTND_ERR_INVALID_ARGUMENT;
+    if (empty_geometry(g)) {
+        g_last_path = SHIFTND_PATH_EMPTY;
+        return SHIFTND_OK;
+    }
+    if (!x || !w || !out) return SHIFTND_ERR_INVALID_ARGUMENT;
+    if (!tshift_tensor_ok(g, q.dtype, x, g.xs) || !tshift_tensor_ok(g, q.dtype, out, g.os)) return SHIFTND_ERR_INVALID_ARGUMENT;
+    g_last_path = SHIFTND_PATH_PLANE;
+    return finish(tinterlace_forward(g, q.dtype, x, w, wkind, out, static_cast<hipStream_t>(stream)));
+}
+
+int interlace_backward_call(const shiftnd_problem *p, const void *go, const int64_t *gos, const void *x, const int64_t *xs,
+                            const void *w, void *gx, const int64_t *gxs, void *gw, void *workspace, size_t workspace_bytes,
+                            void *stream) {
+    shiftnd_problem q;
+    int wkind;
+    int rc = interlace_problem(p, q, wkind);
+    if (rc != SHIFTND_OK) return rc;
+    if (!x || !xs || !gw) return SHIFTND_ERR_INVALID_ARGUMENT;   // (the x == NULL form does not exist under the flag)
+    Geometry g;
+    rc = build_geometry(&q, xs, gos, gxs, g);
+    if (rc != SHIFTND_OK) return rc;
+    if (!interlace_sizes_ok(g, q.dtype)) return SHIFTND_ERR_INVALID_ARGUMENT;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (empty_geometry(g)) {
+        g_last_path = SHIFTND_PATH_EMPTY;
+        const size_t entries = static_cast<size_t>(g.N * g.C * (1 + g.S[3 - g.nd]));   // offsets and scales
+        if (entries > 0 && hipMemsetAsync(gw, 0, entries * dtype_size(wkind), st) != hipSuccess) return SHIFTND_ERR_LAUNCH_FAILED;
+        return SHIFTND_OK;
+    }
+    if (!go || !w || !gx || !workspace) return SHIFTND_ERR_INVALID_ARGUMENT;
+    if (!tshift_tensor_ok(g, q.dtype, go, g.os) || !tshift_tensor_ok(g, q.dtype, x, g.xs) || !tshift_tensor_ok(g, q.dtype, gx, g.gs))
+        return SHIFTND_ERR_INVALID_ARGUMENT;
+    if (tinterlace_backward_workspace(g, q.dtype) > workspace_bytes) return SHIFTND_ERR_WORKSPACE_TOO_SMALL;
+    g_last_path = SHIFTND_PATH_PLANE;
+    return finish(tinterlace_backward(g, q.dtype, go, x, w, wkind, gx, gw, workspace, st));
+}
+
+size_t interlace_workspace_bytes(const shiftnd_problem *p) {
+    const int64_t unit[5] = {0, 0, 0, 0, 0};
+    shiftnd_problem q;
+    int wkind;
+    Geometry g;
+    if (interlace_problem(p, q, wkind) != SHIFTND_OK || build_geometry(&q, unit, unit, unit, g) != SHIFTND_OK) return 0;
+    if (!interlace_sizes_ok(g, q.dtype)) return 0;
+    return empty_geometry(g) ? sizeof(double) : tinterlace_backward_workspace(g, q.dtype);
+}
+
 }  // namespace
 
 namespace shiftnd {
@@ -575,6 +653,8 @@ int shiftnd_backward_serves_channels_last(const shiftnd_problem *p, const void *
 int shiftnd_forward(const shiftnd_problem *p, const void *x, const int64_t x_strides[5], const void *weights, void *out,
                     const int64_t out_strides[5], void *stream) {
     if (!p || !x_strides || !out_strides) return SHIFTND_ERR_INVALID_ARGUMENT;
+    if ((p->dtype & SHIFTND_SHIFT_DIM0) && (p->dtype & SHIFTND_INTERLACE))   // (the bit alone is an unknown dtype bit, below)
+        return interlace_forward_call(p, x, x_strides, weights, out, out_strides, stream);
     if (p->dtype & SHIFTND_SHIFT_DIM0) return tshift_forward_call(p, x, x_strides, weights, out, out_strides, stream);
     shiftnd_problem q;
     int wkind;
@@ -632,7 +712,8 @@ size_t shiftnd_backward_workspace_bytes(const shiftnd_problem *p) {
     int wkind;
     // every entry point refuses the bit alone, so the answer is 0.  (The path below would not give it: it looks at the geometry and sizes
     // the families' plans whatever unknown bits the dtype carries -- 0x800 on F32 answers 512 bytes there, an answer a test pins)
-    if ((p->dtype & (SHIFTND_PER_CLIP | SHIFTND_CLIP_FRAMES)) && !(p->dtype & SHIFTND_SHIFT_DIM0)) return 0;
+    if ((p->dtype & (SHIFTND_PER_CLIP | SHIFTND_CLIP_FRAMES | SHIFTND_INTERLACE)) && !(p->dtype & SHIFTND_SHIFT_DIM0)) return 0;
+    if (p->dtype & SHIFTND_INTERLACE) return interlace_workspace_bytes(p);   // both partial sets of shiftnd_interlace.hip, or 0 for a refused problem
     if (p->dtype & SHIFTND_STREAM) return 0;   // (alone an unknown bit like the one above; beside the flag the online step: no backward, no workspace)
     if (p->dtype & SHIFTND_SHIFT_DIM0) {   // the walk's plan alone (SHIFTND_FRAMES: the channels-last walk's): no other family runs under the flag, no knob shapes it
         const int64_t unit[5] = {0, 0, 0, 0, 0};
@@ -664,6 +745,11 @@ static int backward_planned(const shiftnd_problem *p, const void *grad_out, cons
 int shiftnd_backward(const shiftnd_problem *p, const void *grad_out, const int64_t grad_out_strides[5], const void *x,
                      const int64_t x_strides[5], const void *weights, void *grad_x, const int64_t grad_x_strides[5],
                      void *grad_w, void *workspace, size_t workspace_bytes, void *stream) {
+    if (p && (p->dtype & SHIFTND_SHIFT_DIM0) && (p->dtype & SHIFTND_INTERLACE)) {
+        if (!grad_out_strides || !grad_x_strides) return SHIFTND_ERR_INVALID_ARGUMENT;
+        return interlace_backward_call(p, grad_out, grad_out_strides, x, x_strides, weights, grad_x, grad_x_strides, grad_w, workspace,
+                                       workspace_bytes, stream);
+    }
     if (p && (p->dtype & SHIFTND_SHIFT_DIM0)) {
         if (p->dtype & SHIFTND_STREAM) return SHIFTND_ERR_INVALID_ARGUMENT;   // (the online step is an inference call: no backward)
         if (!grad_out_strides || !grad_x_strides) return SHIFTND_ERR_INVALID_ARGUMENT;

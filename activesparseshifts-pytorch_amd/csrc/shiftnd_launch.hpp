@@ -231,6 +231,15 @@ size_t tshift_backward_workspace(const Geometry &g, int dtype);
 int tshift_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, bool per_clip, void *gx,
                     void *gw, void *workspace, hipStream_t st);
 
+// ---- temporal interlacing (shiftnd_interlace.hip; SHIFTND_SHIFT_DIM0 | SHIFTND_INTERLACE): the per-clip temporal shift times a scale
+// per (n, t, c) plane.  `w` and `gw` are ONE packed array each: [N, C] offsets followed by [N, S0, C] scales.  The geometry and the
+// tensors pass tshift_geometry_ok / tshift_tensor_ok (which holds N * S0 * C below 2^31: the scales' index and the reduction's entry
+// count); the workspace holds both partial sets and depends on the geometry alone.  No fallback.
+int tinterlace_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, void *out, hipStream_t st);
+size_t tinterlace_backward_workspace(const Geometry &g, int dtype);
+int tinterlace_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw,
+                        void *workspace, hipStream_t st);
+
 // ---- the temporal shift of channels-last tensors (shiftnd_frames.hip; SHIFTND_SHIFT_DIM0 on a channels-last view): the sparse shift
 // along S0 of float and quantized (I8, U8, I32) tensors in memory order N, S0, S1, S2, C, `w` a [C] table, whole window; channel
 // pieces are copied from the same pixel of another frame or filled with `fill_bits`.  frames_geometry_ok: the sizes (and

@@ -19,6 +19,8 @@
 //                 _temporal_shift_per_clip_backward: the temporal shifts under a [N, C] table, one row per clip
 //   per clip, channels-last  torchshifts_per_clip_cl::temporal_shift_learnable_per_clip_cl / _forward / _backward,
 //                 temporal_shift_per_clip_cl / _temporal_shift_per_clip_cl_backward: the same with the argument's layout kept
+//   interlace     torchshifts_interlace::temporal_interlace / _temporal_interlace_forward / _backward: the per-clip shift times a scale
+//                 per clip, frame and channel (TIN), two tables
 //   in place      torchshifts_inplace::temporal_shift_ / temporal_shift_quantized_: the temporal shift written into the input (composes
 //                 on CPU tensors), a family that writes its argument
 //   online        torchshifts_online::temporal_shift_online_ / temporal_shift_online_quantized_: one frame per call against a cached
@@ -150,6 +152,14 @@ struct PerClipLearnableClOps {
     static constexpr bool kAsItLies = true;
     using Plain = PerClipLearnableOps;   // (as LearnableClOps::Plain)
 };
+// temporal interlacing: two tables (offsets [N, C], scales [N, T, C]), so signatures and adapters of its own (further down)
+using tin_forward_sig = Tensor(const Tensor &, const Tensor &, const Tensor &, int64_t, int64_t, bool);
+using tin_backward_sig = std::tuple<Tensor, Tensor, Tensor>(const Tensor &, const Tensor &, const Tensor &, const Tensor &, int64_t, int64_t, bool);
+struct InterlaceOps {
+    static const char *name() { return "temporal_interlace"; }
+    static auto &forward() { static auto op = typed_op<tin_forward_sig>("_temporal_interlace_forward", "torchshifts_interlace"); return op; }
+    static auto &backward() { static auto op = typed_op<tin_backward_sig>("_temporal_interlace_backward", "torchshifts_interlace"); return op; }
+};
 
 // ---- the double-backward guard ------------------------------------------------------------------------
 // A backward op is itself differentiable only to the extent of raising on a second backward.  GuardedBackward<Ops>::kernel is the
@@ -157,6 +167,7 @@ struct PerClipLearnableClOps {
 // hangs a node on the results whose backward raises under Ops::name().
 inline variable_list as_list(const Tensor &t) { return {t}; }
 inline variable_list as_list(const std::tuple<Tensor, Tensor> &t) { return {std::get<0>(t), std::get<1>(t)}; }
+inline variable_list as_list(const std::tuple<Tensor, Tensor, Tensor> &t) { return {std::get<0>(t), std::get<1>(t), std::get<2>(t)}; }
 
 template <class Ops, class Handle = std::remove_reference_t<decltype(Ops::backward())>> struct GuardedBackward;
 template <class Ops, class R, class... A>
@@ -171,6 +182,7 @@ struct GuardedBackward<Ops, c10::TypedOperatorHandle<R(A...)>> : public torch::a
     static R kernel(A... args) {
         auto result = GuardedBackward::apply(args...);
         if constexpr (std::is_same_v<R, Tensor>) return result[0];
+        else if constexpr (std::tuple_size_v<R> == 3) return std::make_tuple(result[0], result[1], result[2]);
         else return std::make_tuple(result[0], result[1]);
     }
 };
@@ -1486,6 +1498,145 @@ Tensor tpc_backward_hip(const Tensor &grad, const Tensor &shifts, int64_t n_segm
     return tpc_hip(grad, shifts, n_segment, padding_mode, true);
 }
 
+// ---- temporal interlacing: torchshifts_interlace::temporal_interlace / _temporal_interlace_forward / _backward ----------------------
+// The TIN layer's core (arXiv 2001.06499): the per-clip interpolating shift followed by a per-clip, per-frame, per-channel weight.
+// By definition, with offsets [N, C] and scales [N, T, C]:
+//     y   = temporal_shift_learnable_per_clip(input, offsets, n_segment, padding_mode, active_flag)
+//     out = y * scales.reshape(N*T, C, 1, ...)
+// and the gradients are that composition's.  The CPU key is literally that, on the per-clip ops.  On HIP tensors every pass is ONE
+// C-ABI call on the contiguous tensor under SHIFTND_SHIFT_DIM0 | SHIFTND_INTERLACE (shiftnd_interlace.hip): the two small tables
+// travel as one packed array (one cat), the packed gradient is split back into views.  The autograd node keeps the input and the two
+// tables, nothing of the output's size.  A namespace of its own for the reason torchshifts_inplace:: has one.
+void tin_check(const Tensor &input, const Tensor &offsets, const Tensor &scales, int64_t n_segment, int64_t padding_mode) {
+    TORCH_CHECK(!input.is_quantized(), "temporal_interlace: quantized inputs are not supported");
+    segment_check("temporal_interlace", input, offsets, n_segment, padding_mode, "offsets", at::isFloatingType(offsets.scalar_type()),
+                  "floats", true);
+    TORCH_CHECK(scales.dim() == 3 && scales.size(0) == offsets.size(0) && scales.size(1) == n_segment && scales.size(2) == input.size(1),
+                "temporal_interlace: scales must have shape [N, T, C] = [", offsets.size(0), ", ", n_segment, ", ", input.size(1), "]");
+    TORCH_CHECK(scales.device() == input.device(), "temporal_interlace: scales must be on the input's device");
+    TORCH_CHECK(scales.scalar_type() == offsets.scalar_type(), "temporal_interlace: scales must have the offsets' type (",
+                c10::toString(offsets.scalar_type()), "), not ", c10::toString(scales.scalar_type()));
+}
+
+Tensor tin_public(const Tensor &input, const Tensor &offsets, const Tensor &scales, int64_t n_segment, int64_t padding_mode,
+                  bool active_flag) {
+    tin_check(input, offsets, scales, n_segment, padding_mode);
+    return InterlaceOps::forward().call(input, offsets, scales, n_segment, padding_mode, active_flag);
+}
+
+struct InterlaceFunction : public torch::autograd::Function<InterlaceFunction> {
+    static variable_list forward(AutogradContext *ctx, const Tensor &input, const Tensor &offsets, const Tensor &scales,
+                                 int64_t n_segment, int64_t padding_mode, bool active_flag) {
+        at::AutoDispatchBelowADInplaceOrView guard;
+        auto output = InterlaceOps::forward().call(input, offsets, scales, n_segment, padding_mode, active_flag);
+        ctx->saved_data["n_segment"] = n_segment;
+        ctx->saved_data["padding_mode"] = padding_mode;
+        ctx->saved_data["active_flag"] = active_flag;
+        ctx->save_for_backward({input, offsets, scales});
+        return {output};
+    }
+    static variable_list backward(AutogradContext *ctx, const variable_list &grad_output) {
+        auto saved = ctx->get_saved_variables();
+        auto result = InterlaceOps::backward().call(grad_output[0], saved[1], saved[2], saved[0], ctx->saved_data["n_segment"].toInt(),
+                                                    ctx->saved_data["padding_mode"].toInt(), ctx->saved_data["active_flag"].toBool());
+        return {std::get<0>(result), std::get<1>(result), std::get<2>(result), Tensor(), Tensor(), Tensor()};
+    }
+};
+
+Tensor tin_autograd(const Tensor &input, const Tensor &offsets, const Tensor &scales, int64_t n_segment, int64_t padding_mode,
+                    bool active_flag) {
+    tin_check(input, offsets, scales, n_segment, padding_mode);
+    return InterlaceFunction::apply(input, offsets, scales, n_segment, padding_mode, active_flag)[0];
+}
+std::tuple<Tensor, Tensor, Tensor> tin_autograd_backward(const Tensor &grad, const Tensor &offsets, const Tensor &scales,
+                                                         const Tensor &input, int64_t n_segment, int64_t padding_mode, bool active_flag) {
+    tin_check(input, offsets, scales, n_segment, padding_mode);
+    return GuardedBackward<InterlaceOps>::kernel(grad, offsets, scales, input, n_segment, padding_mode, active_flag);
+}
+
+// scales [N, T, C] as a factor of the [N*T, C, ...] tensor `like`: [N*T, C, 1, ...]
+Tensor tin_plane_scales(const Tensor &scales, const Tensor &like) {
+    std::vector<int64_t> shape(like.dim(), 1);
+    shape[0] = like.size(0);
+    shape[1] = like.size(1);
+    return scales.reshape(shape);
+}
+
+// CPU tensors: the definition, on the per-clip ops
+Tensor tin_forward_cpu(const Tensor &input, const Tensor &offsets, const Tensor &scales, int64_t n_segment, int64_t padding_mode,
+                       bool active_flag) {
+    TORCH_CHECK(input.device().is_cpu() && offsets.device().is_cpu() && scales.device().is_cpu(), "temporal_interlace_cpu: expected CPU tensors");
+    tin_check(input, offsets, scales, n_segment, padding_mode);
+    const Tensor y = PerClipLearnableOps::forward().call(input, offsets, n_segment, padding_mode, active_flag);
+    return y * tin_plane_scales(scales, input);
+}
+
+std::tuple<Tensor, Tensor, Tensor> tin_backward_cpu(const Tensor &grad, const Tensor &offsets, const Tensor &scales, const Tensor &input,
+                                                    int64_t n_segment, int64_t padding_mode, bool active_flag) {
+    TORCH_CHECK(grad.device().is_cpu() && input.device().is_cpu() && offsets.device().is_cpu() && scales.device().is_cpu(),
+                "temporal_interlace_cpu: expected CPU tensors");
+    tin_check(input, offsets, scales, n_segment, padding_mode);
+    TORCH_CHECK(grad.sizes() == input.sizes(), "temporal_interlace backward: grad does not match the input");
+    const Tensor y = PerClipLearnableOps::forward().call(input, offsets, n_segment, padding_mode, active_flag);
+    auto shifted = PerClipLearnableOps::backward().call(grad * tin_plane_scales(scales, input), offsets, input, n_segment, padding_mode,
+                                                        active_flag);
+    if (input.numel() == 0) return std::make_tuple(std::get<0>(shifted), std::get<1>(shifted), at::zeros_like(scales));
+    const Tensor grad_scales = (grad * y).reshape({scales.size(0), scales.size(1), scales.size(2), -1}).sum(3).to(scales.scalar_type());
+    return std::make_tuple(std::get<0>(shifted), std::get<1>(shifted), grad_scales);
+}
+
+// HIP tensors: one flagged C-ABI call per pass under the packed table
+Tensor tin_forward_hip(const Tensor &input_, const Tensor &offsets, const Tensor &scales, int64_t n_segment, int64_t padding_mode,
+                       bool active_flag) {
+    TORCH_CHECK(input_.is_cuda(), "temporal_interlace: expected a CUDA tensor");
+    tin_check(input_, offsets, scales, n_segment, padding_mode);
+    const int mixed = weights_flag("temporal_interlace_cuda", input_, "input", offsets);
+    c10::DeviceGuard device_guard(input_.device());
+    const int dtype = to_shiftnd_dtype(input_.scalar_type(), "temporal_interlace_cuda") | mixed;
+    tsl_check_size(input_, "temporal_interlace");
+    const Tensor input = input_.contiguous();   // (a channels-last input is made contiguous first, as the default per-clip op does)
+    Tensor output = at::empty(input.sizes(), input.options(), at::MemoryFormat::Contiguous);
+    if (input.numel() == 0) return output;
+    const Tensor table = at::cat({offsets.reshape({-1}), scales.reshape({-1})});
+    shiftnd_problem p;
+    int64_t st[5];
+    segment_problem(p, st, input, n_segment, padding_mode, active_flag, dtype | SHIFTND_SHIFT_DIM0 | SHIFTND_INTERLACE, false,
+                    "temporal_interlace");
+    check_status(shiftnd_forward(&p, input.data_ptr(), st, table.data_ptr(), output.data_ptr(), st, current_stream(input)),
+                 "temporal_interlace (HIP)");
+    return output;
+}
+
+std::tuple<Tensor, Tensor, Tensor> tin_backward_hip(const Tensor &grad_, const Tensor &offsets, const Tensor &scales, const Tensor &input_,
+                                                    int64_t n_segment, int64_t padding_mode, bool active_flag) {
+    TORCH_CHECK(grad_.is_cuda() && input_.is_cuda(), "temporal_interlace: expected CUDA tensors");
+    tin_check(input_, offsets, scales, n_segment, padding_mode);
+    check_same("temporal_interlace_backward_cuda", grad_, "grad", input_, "input");
+    const int mixed = weights_flag("temporal_interlace_backward_cuda", grad_, "grad", offsets);
+    TORCH_CHECK(grad_.sizes() == input_.sizes(), "temporal_interlace backward: grad does not match the input");
+    c10::DeviceGuard device_guard(grad_.device());
+    const int dtype = to_shiftnd_dtype(grad_.scalar_type(), "temporal_interlace_backward_cuda") | mixed;
+    tsl_check_size(input_, "temporal_interlace backward");
+    const Tensor input = input_.contiguous(), grad = grad_.contiguous();
+    Tensor grad_input = at::empty(input.sizes(), input.options(), at::MemoryFormat::Contiguous);
+    const Tensor table = at::cat({offsets.reshape({-1}), scales.reshape({-1})});
+    Tensor grad_table = at::empty_like(table);   // (the tables' dtype: fp32 for a mixed call)
+    if (input.numel() == 0) grad_table.zero_();   // (no kernel runs: the zero gradient is written here)
+    else {
+        shiftnd_problem p;
+        int64_t st[5];
+        segment_problem(p, st, input, n_segment, padding_mode, active_flag, dtype | SHIFTND_SHIFT_DIM0 | SHIFTND_INTERLACE, false,
+                        "temporal_interlace");
+        const size_t ws_bytes = shiftnd_backward_workspace_bytes(&p);
+        Tensor workspace = workspace_like(input, ws_bytes);
+        check_status(shiftnd_backward(&p, grad.data_ptr(), st, input.data_ptr(), st, table.data_ptr(), grad_input.data_ptr(), st,
+                                      grad_table.data_ptr(), workspace.data_ptr(), ws_bytes, current_stream(grad)),
+                     "temporal_interlace backward (HIP)");
+    }
+    return std::make_tuple(grad_input, grad_table.narrow(0, 0, offsets.numel()).view(offsets.sizes()),
+                           grad_table.narrow(0, offsets.numel(), scales.numel()).view(scales.sizes()));
+}
+
 // ---- channels-last per-clip temporal shift: torchshifts_per_clip_cl::temporal_shift_learnable_per_clip_cl / temporal_shift_per_clip_cl --
 // The values and gradients of the per-clip ops with the layout of the argument kept (memory_format=torch.preserve_format in the
 // Python wrappers).  On HIP tensors a dense channels-last input is ONE C-ABI call per pass on the tensors as they lie, under
@@ -2031,6 +2182,26 @@ TORCH_LIBRARY_IMPL(torchshifts_per_clip_cl, CUDA, m) {
     m.impl("_temporal_shift_learnable_per_clip_cl_backward", TORCH_FN(tsl_backward_hip<PerClipLearnableClOps>));
     m.impl("temporal_shift_per_clip_cl", TORCH_FN(tpc_cl_forward_hip));
     m.impl("_temporal_shift_per_clip_cl_backward", TORCH_FN(tpc_cl_backward_hip));
+}
+
+// temporal interlacing (the per-clip shift times a scale per clip, frame and channel): a namespace of its own, so that the op sets
+// of the namespaces above stay
+TORCH_LIBRARY(torchshifts_interlace, m) {
+    m.def("torchshifts_interlace::temporal_interlace(Tensor input, Tensor offsets, Tensor scales, int n_segment, int padding_mode, bool active_flag) -> Tensor", &tin_public);
+    m.def("torchshifts_interlace::_temporal_interlace_forward(Tensor input, Tensor offsets, Tensor scales, int n_segment, int padding_mode, bool active_flag) -> Tensor");
+    m.def("torchshifts_interlace::_temporal_interlace_backward(Tensor grad, Tensor offsets, Tensor scales, Tensor input, int n_segment, int padding_mode, bool active_flag) -> (Tensor, Tensor, Tensor)");
+}
+TORCH_LIBRARY_IMPL(torchshifts_interlace, Autograd, m) {
+    m.impl("_temporal_interlace_forward", TORCH_FN(tin_autograd));
+    m.impl("_temporal_interlace_backward", TORCH_FN(tin_autograd_backward));
+}
+TORCH_LIBRARY_IMPL(torchshifts_interlace, CPU, m) {
+    m.impl("_temporal_interlace_forward", TORCH_FN(tin_forward_cpu));
+    m.impl("_temporal_interlace_backward", TORCH_FN(tin_backward_cpu));
+}
+TORCH_LIBRARY_IMPL(torchshifts_interlace, CUDA, m) {
+    m.impl("_temporal_interlace_forward", TORCH_FN(tin_forward_hip));
+    m.impl("_temporal_interlace_backward", TORCH_FN(tin_backward_hip));
 }
 
 // the in-place temporal shift: its own namespace (the op set of torchshifts:: is pinned)

@@ -327,6 +327,39 @@ def temporal_shift_learnable_per_clip_func(input: Tensor, weights: Tensor, n_seg
     return torch.ops.torchshifts_per_clip.temporal_shift_learnable_per_clip(input, weights, n_segment, padding_mode, bool(active_flag))
 
 
+# ---- temporal interlacing (the TIN layer, arXiv 2001.06499): the per-clip shift fused with a per-clip, per-frame weight --------------
+# By definition, with N = input.shape[0] // n_segment, offsets [N, C] and scales [N, T, C]:
+#   y   = temporal_shift_learnable_per_clip_func(input, offsets, n_segment, padding_mode, active_flag)
+#   out = y * scales.reshape(N * T, C, 1, ...)                # out[n, t, c, :] = scales[n, t, c] * shift(x)[n, t, c, :]
+# and the gradients are that composition's: input.grad is the per-clip backward of scales * grad_out, offsets.grad its table gradient,
+# scales.grad[n, t, c] the sum over the plane of grad_out * y.  CPU tensors run exactly that.  On HIP tensors each pass is ONE kernel
+# (csrc/shiftnd_interlace.hip): the forward reads and writes the tensor once, the backward has the traffic of the per-clip backward
+# alone, and the autograd node keeps input, offsets and scales -- no shifted activation of the output's size.  float32 / float64 out
+# and input.grad carry the composition's bits; float16 / bfloat16 are interpolated and scaled in float32 and rounded once; both table
+# gradients are deterministic.  Group tables [N, G] / [N, T, G] (C % G == 0) are expanded here, so autograd sums a group's gradient.
+def temporal_interlace_func(input: Tensor, offsets: Tensor, scales: Tensor, n_segment: int, padding_mode: int = 0,
+                            active_flag: bool = True) -> Tensor:
+    """Shift the channels of a [N * n_segment, C, ...] tensor (2 to 5 dims) across the frames of each clip by offsets[n, c]
+    (out[t] = x[t - w]; interpolated with active_flag, rounded without) and weight frame t of clip n by scales[n, t, c];
+    differentiable in input, offsets and scales.  offsets: [N, C] or [N, G]; scales: [N, n_segment, C] or [N, n_segment, G]."""
+    name = "temporal_interlace_func()"
+    assert offsets.is_floating_point(), f"{name}: expected float offsets, but they are {offsets.dtype}"
+    assert scales.is_floating_point(), f"{name}: expected float scales, but they are {scales.dtype}"
+    offsets = _per_clip_table(name, input, offsets, n_segment, padding_mode, "offsets")
+    clips, channels = input.shape[0] // n_segment, input.shape[1]
+    assert (len(scales.shape) == 3 and scales.shape[0] == clips and scales.shape[1] == n_segment and scales.shape[2] >= 1
+            and channels % scales.shape[2] == 0), \
+        (f"{name}: expected [{clips}, {n_segment}, {channels}] tensor (one entry per clip, frame and channel; or [{clips}, {n_segment}, "
+         f"n_groups] with {channels} % n_groups == 0) as scales, but it is shape is {scales.shape}")
+    assert input.device == scales.device, \
+        (f"{name}: expected input and scales to be on same device, but input is  on {input.device} "
+         f"and scales is on {scales.device}")
+    assert scales.dtype == offsets.dtype, f"{name}: expected offsets and scales of one dtype, but they are {offsets.dtype} and {scales.dtype}"
+    if scales.shape[2] != channels:
+        scales = scales.repeat_interleave(channels // scales.shape[2], dim=2)
+    return torch.ops.torchshifts_interlace.temporal_interlace(input, offsets, scales, n_segment, padding_mode, bool(active_flag))
+
+
 # ---- online temporal shift: one frame per call against a cached state (the uni-directional TSM, arXiv 1811.08383 section 4.2) ------
 # Frames of B independent streams arrive one at a time as [B, C, ...]; the channels that shift are taken from a state of the previous
 # frames.  Sign convention of temporal_shift_func: out[t] = x[t - shifts[c]], so an online table is CAUSAL, every entry >= 0, and the

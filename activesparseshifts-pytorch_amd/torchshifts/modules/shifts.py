@@ -14,7 +14,7 @@ from torch import nn
 from torchshifts.functional import (shift1d_fixed_func, shift1d_fixed_pool_func, shift1d_func, shift1d_pool_func, shift2d_fixed_func,
                                     shift2d_fixed_pool_func, shift2d_func, shift2d_pool_func, shift3d_fixed_func,
                                     shift3d_fixed_pool_func, shift3d_func, shift3d_pool_func, temporal_shift_func, temporal_shift_func_,
-                                    temporal_shift_learnable_func, temporal_shift_learnable_per_clip_func,
+                                    temporal_interlace_func, temporal_shift_learnable_func, temporal_shift_learnable_per_clip_func,
                                     temporal_shift_online_func, temporal_shift_online_func_, temporal_shift_online_state,
                                     temporal_shift_online_table, temporal_shift_per_clip_func)
 
@@ -583,3 +583,88 @@ class LearnablePerClipTemporalShift(nn.Module):
         active = f'Active shift on forward pass: {"Yes" if self._active_flag else "No"}'
         fmt = '' if self.memory_format == torch.contiguous_format else f', memory_format={self.memory_format}'
         return f'n_segment={self.n_segment}, padding_method={pad}, {active}, per-clip weights' + fmt
+
+
+class OffsetNet(nn.Module):
+    """TIN's offset predictor (arXiv 2001.06499): a clip's descriptor [N, fold, T] -> two offsets per clip in (-2, 2), [N, 2].
+    Conv1d(fold, 1, 3, padding=1) -> [N, T] -> Linear(T, T) -> ReLU -> Linear(T, 2) -> 4 * (sigmoid - 0.5); the last Linear's bias
+    starts at 0.5108."""
+
+    def __init__(self, in_channels, n_segment):
+        super().__init__()
+        self.conv = nn.Conv1d(in_channels, 1, 3, padding=1)
+        self.fc1 = nn.Linear(n_segment, n_segment)
+        self.fc2 = nn.Linear(n_segment, 2)
+        nn.init.constant_(self.fc2.bias, 0.5108)
+
+    def forward(self, desc):
+        h = self.conv(desc).view(desc.shape[0], desc.shape[2])
+        return 4 * (torch.sigmoid(self.fc2(torch.relu(self.fc1(h)))) - 0.5)
+
+
+class WeightNet(nn.Module):
+    """TIN's weight predictor: a clip's descriptor [N, fold, T] -> two weights per clip and frame in (0, 2), [N, T, 2].
+    Conv1d(fold, 2, 3, padding=1) -> permute -> 2 * sigmoid; the Conv1d's bias starts at 0."""
+
+    def __init__(self, in_channels):
+        super().__init__()
+        self.conv = nn.Conv1d(in_channels, 2, 3, padding=1)
+        nn.init.constant_(self.conv.bias, 0.0)
+
+    def forward(self, desc):
+        return 2 * torch.sigmoid(self.conv(desc).permute(0, 2, 1))
+
+
+class TemporalInterlace(nn.Module):
+    """The Temporal Interlacing layer (TIN, arXiv 2001.06499) on a [N * n_segment, C, ...] tensor: an OffsetNet and a WeightNet look
+    at the spatial mean of the first fold = in_channels // shift_div channels of each clip and predict two offsets o [N, 2] and two
+    per-frame weights w [N, T, 2]; the four channel groups of the fold are shifted by (o, -o) -- the published sampler reads
+    x[t + offset] -- interpolating between two frames, and weighted by (w, w); channels from fold up pass through (offset 0,
+    weight 1).  The whole layer is ONE temporal_interlace_func call on the whole tensor: no slice and no cat of the activation.
+
+    Arguments:
+        n_segment (int): frames per clip, T.
+        in_channels (int): C.
+        shift_div (int): the first C // shift_div channels are interlaced. Default 1 (all of them).
+        padding (str): 'zeros' | 'border' | 'periodic' | 'reflect' | 'symmetric'. Default 'zeros'.
+    forward(x) -> output, the tensor alone.
+    """
+
+    def __init__(self, n_segment, in_channels, shift_div=1, padding='zeros'):
+        super().__init__()
+        assert padding.lower() in paddings_dict.keys(), f'incorrect padding option: {padding}'
+        assert int(n_segment) >= 1, 'n_segment must be >= 1'
+        self.n_segment = int(n_segment)
+        self.in_channels = int(in_channels)
+        self.shift_div = int(shift_div)
+        self.fold = self.in_channels // self.shift_div
+        assert self.fold >= 4 and self.fold % 4 == 0, \
+            f'in_channels // shift_div ({self.fold}) must be a positive multiple of 4: the fold holds four channel groups'
+        self.padding = paddings_dict[padding.lower()]
+        self.offset_net = OffsetNet(self.fold, self.n_segment)
+        self.weight_net = WeightNet(self.fold)
+
+    def tables(self, input):
+        """offsets [N, C] and scales [N, T, C] of the one call, from the nets' [N, 2] and [N, T, 2]"""
+        T, C, fold = self.n_segment, self.in_channels, self.fold
+        N = input.shape[0] // T
+        desc = input[:, :fold].reshape(N, T, fold, -1).mean(3).permute(0, 2, 1).to(self.offset_net.conv.weight.dtype)
+        o, w = self.offset_net(desc), self.weight_net(desc)
+        table, weight = torch.cat((o, -o), 1), torch.cat((w, w), 2)          # [N, 4], [N, T, 4]
+        offsets = (-table).repeat_interleave(fold // 4, dim=1)               # (the op's sign: out[t] = x[t - w])
+        scales = weight.repeat_interleave(fold // 4, dim=2)
+        if fold < C:
+            offsets = torch.cat((offsets, offsets.new_zeros(N, C - fold)), 1)
+            scales = torch.cat((scales, scales.new_ones(N, T, C - fold)), 2)
+        kind = torch.float32 if input.dtype in (torch.float16, torch.bfloat16) else input.dtype
+        return offsets.to(kind), scales.to(kind)
+
+    def forward(self, input):
+        assert input.shape[1] == self.in_channels and input.shape[0] % self.n_segment == 0, \
+            f'expected a [N * {self.n_segment}, {self.in_channels}, ...] tensor, but it is shape is {tuple(input.shape)}'
+        offsets, scales = self.tables(input)
+        return temporal_interlace_func(input, offsets, scales, self.n_segment, self.padding, True)
+
+    def extra_repr(self):
+        pad = {v: k for k, v in paddings_dict.items()}[self.padding]
+        return f'n_segment={self.n_segment}, in_channels={self.in_channels}, shift_div={self.shift_div}, padding_method={pad}'

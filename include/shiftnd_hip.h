@@ -253,6 +253,39 @@ typedef enum shiftnd_dtype {
  */
 #define SHIFTND_CLIP_FRAMES 0x4000
 
+/*
+ * Temporal INTERLACING (the TIN layer, arXiv 2001.06499): the per-clip temporal shift followed by a per-clip, per-frame, per-channel
+ * weight, in one kernel per pass.  OR-ed onto a float dtype TOGETHER WITH SHIFTND_SHIFT_DIM0 (and, for F16 / BF16, optionally
+ * SHIFTND_WEIGHTS_F32).  With y = the SHIFTND_SHIFT_DIM0 | SHIFTND_PER_CLIP result under offsets[N, C] (out[t] = x[t - w]):
+ *     out[n, t, c, :] = scale[n, t, c] * y[n, t, c, :]
+ * and the gradients are that composition's: grad_x is the per-clip backward applied to scale * grad_out, grad_offsets[n, c] that
+ * backward's table gradient, grad_scale[n, t, c] = sum over the plane of grad_out * y.
+ *   The call signatures have no room for a second table, so under the flag `weights` points to ONE contiguous array: the N * C
+ *   offsets [N, C] immediately followed by the N * S0 * C scales [N, S0, C], both of the weights' type (the tensor dtype; fp32 under
+ *   SHIFTND_WEIGHTS_F32).  `grad_w` has the same layout and is fully overwritten.
+ *   Numerics: F32 / F64 -- out and grad_x carry the bits of the composition: the scale is a multiply of its own, applied AFTER the
+ *   lerp in the forward and to each loaded gradient frame BEFORE the lerp in the backward, no FMA contraction across it.  F16 / BF16 --
+ *   widened to fp32, interpolated, scaled and rounded ONCE (the composition rounds twice).  Both gradient tables: products accumulated
+ *   in fp64 in a fixed order, narrowed once to the weights' type, deterministic; y in grad_scale's sum is the unrounded compute-type
+ *   value.  p->active == 0 keeps the sparse kernels' rule: out is the source plane times the scale, and the table gradient is formed
+ *   as tshift_backward forms it.
+ *   Honoured by shiftnd_forward (both values of p->active), shiftnd_backward (full form) and shiftnd_backward_workspace_bytes, which
+ *   sizes both sets of partial records (per workgroup for the offsets, per wave and frame for the scales) as a function of the
+ *   geometry alone; sizeof(double) for an empty problem.
+ *   Accepted: the geometry, layout and limits of SHIFTND_PER_CLIP -- segment-major tensors (memory order N, S0, C, S1, S2), ndim 2 or
+ *   3, the whole window, every padding mode, element-aligned bases, out of place -- and N * S0 * C below 2^31 (the scales' index).
+ *   Served by csrc/shiftnd_interlace.hip without a fallback: shiftnd_last_kernel() reports tinterlace_forward / tinterlace_backward
+ *   (*_ragged for planes that are not whole 16-byte pieces or bases off the 16-byte grid), shiftnd_last_path() SHIFTND_PATH_PLANE.  An
+ *   empty problem: SHIFTND_PATH_EMPTY, with the N * C + N * S0 * C entries of grad_w zeroed.
+ *   Errors, before anything is launched (the workspace query answers 0): a quantized dtype, the bit on shiftnd_forward_quantized or
+ *   on the pooled entry points, and the bit without SHIFTND_SHIFT_DIM0 (an unknown dtype bit, on every entry point):
+ *   SHIFTND_ERR_UNSUPPORTED_DTYPE; the bit beside SHIFTND_FRAMES, SHIFTND_PER_CLIP, SHIFTND_STREAM or SHIFTND_CLIP_FRAMES, out == x,
+ *   channels-last tensors, ndim 1, a cut window, the x == NULL form of shiftnd_backward, a size beyond the bounds:
+ *   SHIFTND_ERR_INVALID_ARGUMENT; a workspace below the plan: SHIFTND_ERR_WORKSPACE_TOO_SMALL.
+ * Without the bit nothing changes.  (0x800 stays unassigned.)
+ */
+#define SHIFTND_INTERLACE 0x8000
+
 typedef enum shiftnd_status {
     SHIFTND_OK = 0,
     SHIFTND_ERR_INVALID_ARGUMENT = -1,
@@ -276,7 +309,7 @@ typedef enum shiftnd_path {
 /* Problem geometry shared by the entry points. */
 typedef struct shiftnd_problem {
     int32_t ndim;          /* spatial dims: 1, 2 or 3 */
-    int32_t dtype;         /* shiftnd_dtype of input/output (and of float weights), optionally | SHIFTND_WEIGHTS_F32 | SHIFTND_SHIFT_DIM0 | SHIFTND_FRAMES | SHIFTND_PER_CLIP | SHIFTND_STREAM | SHIFTND_CLIP_FRAMES */
+    int32_t dtype;         /* shiftnd_dtype of input/output (and of float weights), optionally | SHIFTND_WEIGHTS_F32 | SHIFTND_SHIFT_DIM0 | SHIFTND_FRAMES | SHIFTND_PER_CLIP | SHIFTND_STREAM | SHIFTND_CLIP_FRAMES | SHIFTND_INTERLACE */
     int32_t padding_mode;  /* 0..4 */
     int32_t active;        /* 0: sparse shift (rounded integer shift); 1: active (interpolated) */
     int64_t sizes[5];      /* input N, C, H, W, D */
