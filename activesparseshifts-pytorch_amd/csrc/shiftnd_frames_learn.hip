@@ -35,6 +35,7 @@ namespace shiftnd {
 namespace {
 
 constexpr int kFwdInFlight = 4;        // pieces per thread of the forward, every load issued before the first store
+constexpr int64_t kWantWorkgroups = 6144;   // the forward cuts frames into more workgroups while its grid is short of this many (as frames_forward)
 constexpr int kMaxRowSteps = 8;        // the backward's workgroup walks at most this many steps of rows ...
 constexpr int64_t kWantGroups = 2048;  // ... fewer while the grid is short of this many workgroups (8 per CU)
 constexpr int kMaxElems = 8;           // elements of a 16-byte piece (2-byte types)
@@ -312,7 +313,7 @@ int frames_active_forward(const Geometry &g, int dtype, const void *x, const voi
     // workgroups per frame: at least one batch of kFwdInFlight steps each, more steps while the grid is large
     const int64_t frames = g.N * q.T, batch_rows = static_cast<int64_t>(q.rps) * kFwdInFlight;
     const int64_t most = (q.M + batch_rows - 1) / batch_rows;
-    const int64_t wanted = (6144 + frames - 1) / frames;
+    const int64_t wanted = (kWantWorkgroups + frames - 1) / frames;
     const int64_t chunks = most < wanted ? most : wanted;
     q.rows_per_wg = static_cast<uint32_t>(((q.M + chunks - 1) / chunks + batch_rows - 1) / batch_rows * batch_rows);
     q.chunks = static_cast<uint32_t>((q.M + q.rows_per_wg - 1) / q.rows_per_wg);

@@ -49,7 +49,12 @@ RAGGED_CASES = [((2, 3, 5, 5), F16, 0),       # 2-byte pieces
                 ((2, 3, 5, 12), BF16, 0),     # 8-byte pieces
                 ((2, 3, 5, 3), F32, 0),       # 4-byte pieces
                 ((2, 3, 4, 3), F64, 0),       # 8-byte pieces
-                ((2, 3, 5, 8), F16, 1)]       # bases one element off the 16-byte grid
+                ((2, 3, 5, 8), F16, 1),       # bases one element off the 16-byte grid
+                # rows enough for the backward's row loop to iterate: the plan assumes 16-byte pieces (256 rows a step), the kernel
+                # steps by its own rows per step (tests/temporal_plans.py: backward_plan)
+                ((2, 3, 196, 5), F16, 0),     # 2-byte pieces, 51 rows a step: four trips
+                ((2, 3, 90, 6), BF16, 0),     # 4-byte pieces, 85 rows a step: two trips, the second of five rows
+                ((1, 2, 130, 3), F64, 0)]     # 8-byte pieces, 85 rows a step under a plan of 128: two workgroups, two trips in the first
 DEGENERATE_CASES = [((2, 1, 5, 8), F32, 0), ((2, 3, 1, 8), F32, 0), ((2, 4, 6, 1), F32, 0)]
 CASES = WHOLE_CASES + RAGGED_CASES + DEGENERATE_CASES
 TABLES = ("specials", "pieces", "runs")
