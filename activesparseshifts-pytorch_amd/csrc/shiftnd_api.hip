@@ -533,6 +533,76 @@ size_t interlace_workspace_bytes(const shiftnd_problem *p) {
     return empty_geometry(g) ? sizeof(double) : tinterlace_backward_workspace(g, q.dtype);
 }
 
+// ---- SHIFTND_SHIFT_DIM0 | SHIFTND_INTERLACE_FRAMES: temporal interlacing of dense channels-last tensors, all of them
+// (shiftnd_interlace_frames.hip) -- SHIFTND_INTERLACE's problem and packed table on SHIFTND_FRAMES' layout, out of place; served by its
+// own kernels or refused before anything is launched.  No other bit of the family combines with it, SHIFTND_INTERLACE included.
+// -> the problem without the flag bits in `q`, the weights' type in `wkind`
+int interlace_frames_problem(const shiftnd_problem *p, shiftnd_problem &q, int &wkind) {
+    constexpr int others = SHIFTND_FRAMES | SHIFTND_PER_CLIP | SHIFTND_STREAM | SHIFTND_CLIP_FRAMES | SHIFTND_INTERLACE;
+    shiftnd_problem r = *p;
+    r.dtype = p->dtype & ~(SHIFTND_SHIFT_DIM0 | SHIFTND_INTERLACE_FRAMES | others);
+    if (split_dtype(&r, q, wkind) != SHIFTND_OK || !is_float_dtype(q.dtype)) return SHIFTND_ERR_UNSUPPORTED_DTYPE;
+    return (p->dtype & others) ? SHIFTND_ERR_INVALID_ARGUMENT : SHIFTND_OK;
+}
+
+int interlace_frames_forward_call(const shiftnd_problem *p, const void *x, const int64_t *xs, const void *w, void *out,
+                                  const int64_t *os, void *stream) {
+    shiftnd_problem q;
+    int wkind;
+    int rc = interlace_frames_problem(p, q, wkind);
+    if (rc != SHIFTND_OK) return rc;
+    if (out && out == x) return SHIFTND_ERR_INVALID_ARGUMENT;   // (no in-place form)
+    Geometry g;
+    rc = build_geometry(&q, xs, os, nullptr, g);
+    if (rc != SHIFTND_OK) return rc;
+    if (!frames_interlace_geometry_ok(g, q.dtype)) return SHIFTND_ERR_INVALID_ARGUMENT;   // (ndim 1, a cut window, the sizes)
+    if (empty_geometry(g)) {
+        g_last_path = SHIFTND_PATH_EMPTY;
+        return SHIFTND_OK;
+    }
+    if (!x || !w || !out) return SHIFTND_ERR_INVALID_ARGUMENT;
+    if (!frames_tensor_ok(g, q.dtype, x, g.xs) || !frames_tensor_ok(g, q.dtype, out, g.os)) return SHIFTND_ERR_INVALID_ARGUMENT;
+    g_last_path = SHIFTND_PATH_CL;
+    return finish(frames_interlace_forward(g, q.dtype, x, w, wkind, out, static_cast<hipStream_t>(stream)));
+}
+
+int interlace_frames_backward_call(const shiftnd_problem *p, const void *go, const int64_t *gos, const void *x, const int64_t *xs,
+                                   const void *w, void *gx, const int64_t *gxs, void *gw, void *workspace, size_t workspace_bytes,
+                                   void *stream) {
+    shiftnd_problem q;
+    int wkind;
+    int rc = interlace_frames_problem(p, q, wkind);
+    if (rc != SHIFTND_OK) return rc;
+    if (!x || !xs || !gw) return SHIFTND_ERR_INVALID_ARGUMENT;   // (the x == NULL form does not exist under the flag)
+    Geometry g;
+    rc = build_geometry(&q, xs, gos, gxs, g);
+    if (rc != SHIFTND_OK) return rc;
+    if (!frames_interlace_geometry_ok(g, q.dtype)) return SHIFTND_ERR_INVALID_ARGUMENT;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (empty_geometry(g)) {
+        g_last_path = SHIFTND_PATH_EMPTY;
+        const size_t entries = static_cast<size_t>(g.N * g.C * (1 + g.S[3 - g.nd]));   // offsets and scales
+        if (entries > 0 && hipMemsetAsync(gw, 0, entries * dtype_size(wkind), st) != hipSuccess) return SHIFTND_ERR_LAUNCH_FAILED;
+        return SHIFTND_OK;
+    }
+    if (!go || !w || !gx || !workspace) return SHIFTND_ERR_INVALID_ARGUMENT;
+    if (!frames_tensor_ok(g, q.dtype, go, g.os) || !frames_tensor_ok(g, q.dtype, x, g.xs) || !frames_tensor_ok(g, q.dtype, gx, g.gs))
+        return SHIFTND_ERR_INVALID_ARGUMENT;
+    if (frames_interlace_backward_workspace(g, q.dtype) > workspace_bytes) return SHIFTND_ERR_WORKSPACE_TOO_SMALL;
+    g_last_path = SHIFTND_PATH_CL;
+    return finish(frames_interlace_backward(g, q.dtype, go, x, w, wkind, gx, gw, workspace, st));
+}
+
+size_t interlace_frames_workspace_bytes(const shiftnd_problem *p) {
+    const int64_t unit[5] = {0, 0, 0, 0, 0};
+    shiftnd_problem q;
+    int wkind;
+    Geometry g;
+    if (interlace_frames_problem(p, q, wkind) != SHIFTND_OK || build_geometry(&q, unit, unit, unit, g) != SHIFTND_OK) return 0;
+    if (!frames_interlace_geometry_ok(g, q.dtype)) return 0;
+    return empty_geometry(g) ? sizeof(double) : frames_interlace_backward_workspace(g, q.dtype);
+}
+
 }  // namespace
 
 namespace shiftnd {
@@ -653,6 +723,8 @@ int shiftnd_backward_serves_channels_last(const shiftnd_problem *p, const void *
 int shiftnd_forward(const shiftnd_problem *p, const void *x, const int64_t x_strides[5], const void *weights, void *out,
                     const int64_t out_strides[5], void *stream) {
     if (!p || !x_strides || !out_strides) return SHIFTND_ERR_INVALID_ARGUMENT;
+    if ((p->dtype & SHIFTND_SHIFT_DIM0) && (p->dtype & SHIFTND_INTERLACE_FRAMES))   // (first: beside SHIFTND_INTERLACE it is this family's refusal)
+        return interlace_frames_forward_call(p, x, x_strides, weights, out, out_strides, stream);
     if ((p->dtype & SHIFTND_SHIFT_DIM0) && (p->dtype & SHIFTND_INTERLACE))   // (the bit alone is an unknown dtype bit, below)
         return interlace_forward_call(p, x, x_strides, weights, out, out_strides, stream);
     if (p->dtype & SHIFTND_SHIFT_DIM0) return tshift_forward_call(p, x, x_strides, weights, out, out_strides, stream);
@@ -712,7 +784,8 @@ size_t shiftnd_backward_workspace_bytes(const shiftnd_problem *p) {
     int wkind;
     // every entry point refuses the bit alone, so the answer is 0.  (The path below would not give it: it looks at the geometry and sizes
     // the families' plans whatever unknown bits the dtype carries -- 0x800 on F32 answers 512 bytes there, an answer a test pins)
-    if ((p->dtype & (SHIFTND_PER_CLIP | SHIFTND_CLIP_FRAMES | SHIFTND_INTERLACE)) && !(p->dtype & SHIFTND_SHIFT_DIM0)) return 0;
+    if ((p->dtype & (SHIFTND_PER_CLIP | SHIFTND_CLIP_FRAMES | SHIFTND_INTERLACE | SHIFTND_INTERLACE_FRAMES)) && !(p->dtype & SHIFTND_SHIFT_DIM0)) return 0;
+    if (p->dtype & SHIFTND_INTERLACE_FRAMES) return interlace_frames_workspace_bytes(p);   // both partial sets of shiftnd_interlace_frames.hip, or 0 for a refused problem
     if (p->dtype & SHIFTND_INTERLACE) return interlace_workspace_bytes(p);   // both partial sets of shiftnd_interlace.hip, or 0 for a refused problem
     if (p->dtype & SHIFTND_STREAM) return 0;   // (alone an unknown bit like the one above; beside the flag the online step: no backward, no workspace)
     if (p->dtype & SHIFTND_SHIFT_DIM0) {   // the walk's plan alone (SHIFTND_FRAMES: the channels-last walk's): no other family runs under the flag, no knob shapes it
@@ -745,6 +818,11 @@ static int backward_planned(const shiftnd_problem *p, const void *grad_out, cons
 int shiftnd_backward(const shiftnd_problem *p, const void *grad_out, const int64_t grad_out_strides[5], const void *x,
                      const int64_t x_strides[5], const void *weights, void *grad_x, const int64_t grad_x_strides[5],
                      void *grad_w, void *workspace, size_t workspace_bytes, void *stream) {
+    if (p && (p->dtype & SHIFTND_SHIFT_DIM0) && (p->dtype & SHIFTND_INTERLACE_FRAMES)) {
+        if (!grad_out_strides || !grad_x_strides) return SHIFTND_ERR_INVALID_ARGUMENT;
+        return interlace_frames_backward_call(p, grad_out, grad_out_strides, x, x_strides, weights, grad_x, grad_x_strides, grad_w,
+                                              workspace, workspace_bytes, stream);
+    }
     if (p && (p->dtype & SHIFTND_SHIFT_DIM0) && (p->dtype & SHIFTND_INTERLACE)) {
         if (!grad_out_strides || !grad_x_strides) return SHIFTND_ERR_INVALID_ARGUMENT;
         return interlace_backward_call(p, grad_out, grad_out_strides, x, x_strides, weights, grad_x, grad_x_strides, grad_w, workspace,

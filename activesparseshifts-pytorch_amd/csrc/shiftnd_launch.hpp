@@ -262,6 +262,17 @@ size_t frames_backward_workspace(const Geometry &g, int dtype);
 int frames_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, bool per_clip, void *gx,
                     void *gw, void *workspace, hipStream_t st);
 
+// ---- temporal interlacing of channels-last tensors (shiftnd_interlace_frames.hip; SHIFTND_SHIFT_DIM0 | SHIFTND_INTERLACE_FRAMES):
+// the problem of shiftnd_interlace.hip on tensors in memory order N, S0, S1, S2, C, `w` and `gw` the packed arrays ([N, C] offsets
+// followed by [N, S0, C] scales), whole window, both modes; every tensor passes frames_tensor_ok.  frames_interlace_geometry_ok: the
+// sizes (frames_learn_geometry_ok's, N * S0 * C below 2^31, the backward's groups and records).  The workspace holds both partial
+// sets and depends on the geometry alone.  No fallback: every such call is served.
+bool frames_interlace_geometry_ok(const Geometry &g, int dtype);
+int frames_interlace_forward(const Geometry &g, int dtype, const void *x, const void *w, int wkind, void *out, hipStream_t st);
+size_t frames_interlace_backward_workspace(const Geometry &g, int dtype);
+int frames_interlace_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, void *gx, void *gw,
+                              void *workspace, hipStream_t st);
+
 // ---- the temporal shift IN PLACE (shiftnd_inplace.hip; SHIFTND_SHIFT_DIM0 with out == x): the sparse shift along S0 of float and
 // quantized (I8, U8, I32) tensors in either dense layout, `w` a [C] table, whole window, at most 16 frames per clip; only the bytes
 // of shifted channels are read or written.  inplace_geometry_ok: the sizes (frames_geometry_ok's, S0 <= 16, the grid);

@@ -15,33 +15,31 @@
 namespace shiftnd {
 // the final stage of every family's weight-gradient reduction (declared in shiftnd_common.hpp)
 namespace {
-template <typename T>
+// ONE kernel for the four table types (wkind is launch-uniform: a scalar branch around the one narrowing store; the sum, which is
+// all the kernel does otherwise, is fp64 whatever the type).  The three kernels saved pay for shiftnd_interlace_frames.hip's
+// (DESIGN 3.39).
 __global__ __launch_bounds__(64) void reduce_weight_grads(const double *__restrict__ partials, int groups, int C, int nd,
-                                                           typename T::S *__restrict__ grad_w) {
+                                                           void *__restrict__ grad_w, int wkind, int record) {
     // one wave per output element: lanes stride over the groups (fixed order), then a fixed shuffle tree
     const int t = blockIdx.x;
     const int c = t / nd, s = t - c * nd;
     double acc = 0.0;
-    for (int g = threadIdx.x; g < groups; g += 64) acc += partials[(static_cast<size_t>(g) * C + c) * 3 + s];
+    for (int g = threadIdx.x; g < groups; g += 64) acc += partials[(static_cast<size_t>(g) * C + c) * record + s];
     acc = wave_sum(acc);
     if (threadIdx.x == 0) {
-        if constexpr (sizeof(typename T::S) == 8) {
-            grad_w[t] = acc;
-        } else {
-            grad_w[t] = narrow<T>(static_cast<float>(acc));
+        switch (wkind) {
+        case SHIFTND_F64: static_cast<double *>(grad_w)[t] = acc; break;
+        case SHIFTND_F32: static_cast<float *>(grad_w)[t] = narrow<f32_t>(static_cast<float>(acc)); break;
+        case SHIFTND_F16: static_cast<f16_t::S *>(grad_w)[t] = narrow<f16_t>(static_cast<float>(acc)); break;
+        default: static_cast<bf16_t::S *>(grad_w)[t] = narrow<bf16_t>(static_cast<float>(acc)); break;
         }
     }
 }
 }  // namespace
 
-void launch_reduce_weight_grads(int wkind, const double *partials, int groups, int C, int nd, void *grad_w, hipStream_t st) {
+void launch_reduce_weight_grads(int wkind, const double *partials, int groups, int C, int nd, void *grad_w, hipStream_t st, int record) {
     const dim3 grid(static_cast<unsigned>(C) * nd), block(64);
-    switch (wkind) {
-    case SHIFTND_F32: hipLaunchKernelGGL((reduce_weight_grads<f32_t>), grid, block, 0, st, partials, groups, C, nd, static_cast<float *>(grad_w)); break;
-    case SHIFTND_F64: hipLaunchKernelGGL((reduce_weight_grads<f64_t>), grid, block, 0, st, partials, groups, C, nd, static_cast<double *>(grad_w)); break;
-    case SHIFTND_F16: hipLaunchKernelGGL((reduce_weight_grads<f16_t>), grid, block, 0, st, partials, groups, C, nd, static_cast<f16_t::S *>(grad_w)); break;
-    default: hipLaunchKernelGGL((reduce_weight_grads<bf16_t>), grid, block, 0, st, partials, groups, C, nd, static_cast<bf16_t::S *>(grad_w)); break;
-    }
+    hipLaunchKernelGGL(reduce_weight_grads, grid, block, 0, st, partials, groups, C, nd, grad_w, wkind, record);
 }
 
 namespace {

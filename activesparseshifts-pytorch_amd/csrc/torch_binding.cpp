@@ -155,10 +155,23 @@ struct PerClipLearnableClOps {
 // temporal interlacing: two tables (offsets [N, C], scales [N, T, C]), so signatures and adapters of its own (further down)
 using tin_forward_sig = Tensor(const Tensor &, const Tensor &, const Tensor &, int64_t, int64_t, bool);
 using tin_backward_sig = std::tuple<Tensor, Tensor, Tensor>(const Tensor &, const Tensor &, const Tensor &, const Tensor &, int64_t, int64_t, bool);
+// (what the HIP adapters tin_forward_hip / tin_backward_hip differ in travels with the family, as for the learnable families above)
 struct InterlaceOps {
     static const char *name() { return "temporal_interlace"; }
     static auto &forward() { static auto op = typed_op<tin_forward_sig>("_temporal_interlace_forward", "torchshifts_interlace"); return op; }
     static auto &backward() { static auto op = typed_op<tin_backward_sig>("_temporal_interlace_backward", "torchshifts_interlace"); return op; }
+    static constexpr const char *kCuda = "temporal_interlace_cuda", *kBackwardCuda = "temporal_interlace_backward_cuda";
+    static constexpr int kFlags = SHIFTND_SHIFT_DIM0 | SHIFTND_INTERLACE;
+    static constexpr bool kAsItLies = false;
+};
+struct InterlaceClOps {
+    static const char *name() { return "temporal_interlace_cl"; }
+    static auto &forward() { static auto op = typed_op<tin_forward_sig>("_temporal_interlace_cl_forward", "torchshifts_interlace_cl"); return op; }
+    static auto &backward() { static auto op = typed_op<tin_backward_sig>("_temporal_interlace_cl_backward", "torchshifts_interlace_cl"); return op; }
+    static constexpr const char *kCuda = "temporal_interlace_cl_cuda", *kBackwardCuda = "temporal_interlace_cl_backward_cuda";
+    static constexpr int kFlags = SHIFTND_SHIFT_DIM0 | SHIFTND_INTERLACE_FRAMES;
+    static constexpr bool kAsItLies = true;
+    using Plain = InterlaceOps;   // (as LearnableClOps::Plain)
 };
 
 // ---- the double-backward guard ------------------------------------------------------------------------
@@ -1518,17 +1531,19 @@ void tin_check(const Tensor &input, const Tensor &offsets, const Tensor &scales,
                 c10::toString(offsets.scalar_type()), "), not ", c10::toString(scales.scalar_type()));
 }
 
+// the public entry, the node and the Autograd-key kernels.  Ops: InterlaceOps, and the _cl family's InterlaceClOps
+template <class Ops>
 Tensor tin_public(const Tensor &input, const Tensor &offsets, const Tensor &scales, int64_t n_segment, int64_t padding_mode,
                   bool active_flag) {
     tin_check(input, offsets, scales, n_segment, padding_mode);
-    return InterlaceOps::forward().call(input, offsets, scales, n_segment, padding_mode, active_flag);
+    return Ops::forward().call(input, offsets, scales, n_segment, padding_mode, active_flag);
 }
 
-struct InterlaceFunction : public torch::autograd::Function<InterlaceFunction> {
+template <class Ops> struct InterlaceFunction : public torch::autograd::Function<InterlaceFunction<Ops>> {
     static variable_list forward(AutogradContext *ctx, const Tensor &input, const Tensor &offsets, const Tensor &scales,
                                  int64_t n_segment, int64_t padding_mode, bool active_flag) {
         at::AutoDispatchBelowADInplaceOrView guard;
-        auto output = InterlaceOps::forward().call(input, offsets, scales, n_segment, padding_mode, active_flag);
+        auto output = Ops::forward().call(input, offsets, scales, n_segment, padding_mode, active_flag);
         ctx->saved_data["n_segment"] = n_segment;
         ctx->saved_data["padding_mode"] = padding_mode;
         ctx->saved_data["active_flag"] = active_flag;
@@ -1537,21 +1552,23 @@ struct InterlaceFunction : public torch::autograd::Function<InterlaceFunction> {
     }
     static variable_list backward(AutogradContext *ctx, const variable_list &grad_output) {
         auto saved = ctx->get_saved_variables();
-        auto result = InterlaceOps::backward().call(grad_output[0], saved[1], saved[2], saved[0], ctx->saved_data["n_segment"].toInt(),
-                                                    ctx->saved_data["padding_mode"].toInt(), ctx->saved_data["active_flag"].toBool());
+        auto result = Ops::backward().call(grad_output[0], saved[1], saved[2], saved[0], ctx->saved_data["n_segment"].toInt(),
+                                           ctx->saved_data["padding_mode"].toInt(), ctx->saved_data["active_flag"].toBool());
         return {std::get<0>(result), std::get<1>(result), std::get<2>(result), Tensor(), Tensor(), Tensor()};
     }
 };
 
+template <class Ops>
 Tensor tin_autograd(const Tensor &input, const Tensor &offsets, const Tensor &scales, int64_t n_segment, int64_t padding_mode,
                     bool active_flag) {
     tin_check(input, offsets, scales, n_segment, padding_mode);
-    return InterlaceFunction::apply(input, offsets, scales, n_segment, padding_mode, active_flag)[0];
+    return InterlaceFunction<Ops>::apply(input, offsets, scales, n_segment, padding_mode, active_flag)[0];
 }
+template <class Ops>
 std::tuple<Tensor, Tensor, Tensor> tin_autograd_backward(const Tensor &grad, const Tensor &offsets, const Tensor &scales,
                                                          const Tensor &input, int64_t n_segment, int64_t padding_mode, bool active_flag) {
     tin_check(input, offsets, scales, n_segment, padding_mode);
-    return GuardedBackward<InterlaceOps>::kernel(grad, offsets, scales, input, n_segment, padding_mode, active_flag);
+    return GuardedBackward<Ops>::kernel(grad, offsets, scales, input, n_segment, padding_mode, active_flag);
 }
 
 // scales [N, T, C] as a factor of the [N*T, C, ...] tensor `like`: [N*T, C, 1, ...]
@@ -1585,56 +1602,102 @@ std::tuple<Tensor, Tensor, Tensor> tin_backward_cpu(const Tensor &grad, const Te
     return std::make_tuple(std::get<0>(shifted), std::get<1>(shifted), grad_scales);
 }
 
-// HIP tensors: one flagged C-ABI call per pass under the packed table
+// HIP tensors: one flagged C-ABI call per pass under the packed table.  Ops: InterlaceOps -- the tensors made contiguous, what the
+// segment-major kernels cannot count refused -- and InterlaceClOps (Ops::kAsItLies), which hands every tensor that is not dense
+// channels-last to InterlaceOps first and then takes its tensors as they lie under SHIFTND_INTERLACE_FRAMES: no contiguous(), results
+// in the argument's strides (grad_x: the gradient's).  The segment-major size check (2^31 two-byte units) does not apply; the frame
+// kernels' own bounds do -- N * T * C < 2^31 for the packed table, which the plain route needs as well, and the backward's groups and
+// records (include/shiftnd_hip.h) -- and a tensor beyond them raises "invalid argument" here: there is no route to fall back to that
+// takes what these refuse
+template <class Ops>
 Tensor tin_forward_hip(const Tensor &input_, const Tensor &offsets, const Tensor &scales, int64_t n_segment, int64_t padding_mode,
                        bool active_flag) {
-    TORCH_CHECK(input_.is_cuda(), "temporal_interlace: expected a CUDA tensor");
+    if constexpr (Ops::kAsItLies)
+        if (!is_channels_last_dense(input_)) return tin_forward_hip<typename Ops::Plain>(input_, offsets, scales, n_segment, padding_mode, active_flag);
+    TORCH_CHECK(input_.is_cuda(), Ops::name(), ": expected a CUDA tensor");
     tin_check(input_, offsets, scales, n_segment, padding_mode);
-    const int mixed = weights_flag("temporal_interlace_cuda", input_, "input", offsets);
+    const int mixed = weights_flag(Ops::kCuda, input_, "input", offsets);
     c10::DeviceGuard device_guard(input_.device());
-    const int dtype = to_shiftnd_dtype(input_.scalar_type(), "temporal_interlace_cuda") | mixed;
-    tsl_check_size(input_, "temporal_interlace");
-    const Tensor input = input_.contiguous();   // (a channels-last input is made contiguous first, as the default per-clip op does)
-    Tensor output = at::empty(input.sizes(), input.options(), at::MemoryFormat::Contiguous);
+    const int dtype = to_shiftnd_dtype(input_.scalar_type(), Ops::kCuda) | mixed;
+    if (!Ops::kAsItLies) tsl_check_size(input_, "temporal_interlace");
+    const Tensor input = Ops::kAsItLies ? input_ : input_.contiguous();   // (the default op makes a channels-last input contiguous first)
+    Tensor output = Ops::kAsItLies ? at::empty_strided(input.sizes(), input.strides(), input.options())
+                                   : at::empty(input.sizes(), input.options(), at::MemoryFormat::Contiguous);
     if (input.numel() == 0) return output;
     const Tensor table = at::cat({offsets.reshape({-1}), scales.reshape({-1})});
     shiftnd_problem p;
     int64_t st[5];
-    segment_problem(p, st, input, n_segment, padding_mode, active_flag, dtype | SHIFTND_SHIFT_DIM0 | SHIFTND_INTERLACE, false,
-                    "temporal_interlace");
-    check_status(shiftnd_forward(&p, input.data_ptr(), st, table.data_ptr(), output.data_ptr(), st, current_stream(input)),
-                 "temporal_interlace (HIP)");
+    segment_problem(p, st, input, n_segment, padding_mode, active_flag, dtype | Ops::kFlags, Ops::kAsItLies, Ops::name());
+    const int rc = shiftnd_forward(&p, input.data_ptr(), st, table.data_ptr(), output.data_ptr(), st, current_stream(input));
+    TORCH_CHECK(rc == SHIFTND_OK, Ops::name(), " (HIP): ", shiftnd_status_string(rc));
     return output;
 }
 
+template <class Ops>
 std::tuple<Tensor, Tensor, Tensor> tin_backward_hip(const Tensor &grad_, const Tensor &offsets, const Tensor &scales, const Tensor &input_,
                                                     int64_t n_segment, int64_t padding_mode, bool active_flag) {
-    TORCH_CHECK(grad_.is_cuda() && input_.is_cuda(), "temporal_interlace: expected CUDA tensors");
+    if constexpr (Ops::kAsItLies)
+        if (!is_channels_last_dense(input_) || !is_channels_last_dense(grad_) || grad_.sizes() != input_.sizes())
+            return tin_backward_hip<typename Ops::Plain>(grad_, offsets, scales, input_, n_segment, padding_mode, active_flag);   // (contiguous grad_x)
+    TORCH_CHECK(grad_.is_cuda() && input_.is_cuda(), Ops::name(), ": expected CUDA tensors");
     tin_check(input_, offsets, scales, n_segment, padding_mode);
-    check_same("temporal_interlace_backward_cuda", grad_, "grad", input_, "input");
-    const int mixed = weights_flag("temporal_interlace_backward_cuda", grad_, "grad", offsets);
-    TORCH_CHECK(grad_.sizes() == input_.sizes(), "temporal_interlace backward: grad does not match the input");
+    check_same(Ops::kBackwardCuda, grad_, "grad", input_, "input");
+    const int mixed = weights_flag(Ops::kBackwardCuda, grad_, "grad", offsets);
+    TORCH_CHECK(grad_.sizes() == input_.sizes(), Ops::name(), " backward: grad does not match the input");
     c10::DeviceGuard device_guard(grad_.device());
-    const int dtype = to_shiftnd_dtype(grad_.scalar_type(), "temporal_interlace_backward_cuda") | mixed;
-    tsl_check_size(input_, "temporal_interlace backward");
-    const Tensor input = input_.contiguous(), grad = grad_.contiguous();
-    Tensor grad_input = at::empty(input.sizes(), input.options(), at::MemoryFormat::Contiguous);
+    const int dtype = to_shiftnd_dtype(grad_.scalar_type(), Ops::kBackwardCuda) | mixed;
+    if (!Ops::kAsItLies) tsl_check_size(input_, "temporal_interlace backward");
+    const Tensor input = Ops::kAsItLies ? input_ : input_.contiguous(), grad = Ops::kAsItLies ? grad_ : grad_.contiguous();
+    Tensor grad_input = Ops::kAsItLies ? at::empty_strided(grad.sizes(), grad.strides(), grad.options())
+                                       : at::empty(input.sizes(), input.options(), at::MemoryFormat::Contiguous);
     const Tensor table = at::cat({offsets.reshape({-1}), scales.reshape({-1})});
     Tensor grad_table = at::empty_like(table);   // (the tables' dtype: fp32 for a mixed call)
     if (input.numel() == 0) grad_table.zero_();   // (no kernel runs: the zero gradient is written here)
     else {
         shiftnd_problem p;
         int64_t st[5];
-        segment_problem(p, st, input, n_segment, padding_mode, active_flag, dtype | SHIFTND_SHIFT_DIM0 | SHIFTND_INTERLACE, false,
-                        "temporal_interlace");
+        segment_problem(p, st, input, n_segment, padding_mode, active_flag, dtype | Ops::kFlags, Ops::kAsItLies, Ops::name());
         const size_t ws_bytes = shiftnd_backward_workspace_bytes(&p);
         Tensor workspace = workspace_like(input, ws_bytes);
-        check_status(shiftnd_backward(&p, grad.data_ptr(), st, input.data_ptr(), st, table.data_ptr(), grad_input.data_ptr(), st,
-                                      grad_table.data_ptr(), workspace.data_ptr(), ws_bytes, current_stream(grad)),
-                     "temporal_interlace backward (HIP)");
+        const int rc = shiftnd_backward(&p, grad.data_ptr(), st, input.data_ptr(), st, table.data_ptr(), grad_input.data_ptr(), st,
+                                        grad_table.data_ptr(), workspace.data_ptr(), ws_bytes, current_stream(grad));
+        TORCH_CHECK(rc == SHIFTND_OK, Ops::name(), " backward (HIP): ", shiftnd_status_string(rc));
     }
     return std::make_tuple(grad_input, grad_table.narrow(0, 0, offsets.numel()).view(offsets.sizes()),
                            grad_table.narrow(0, offsets.numel(), scales.numel()).view(scales.sizes()));
+}
+
+// ---- channels-last temporal interlacing: torchshifts_interlace_cl::temporal_interlace_cl / _temporal_interlace_cl_forward / _backward --
+// The values and gradients of temporal_interlace with the layout of the argument kept (memory_format=torch.preserve_format in the
+// Python wrappers).  On HIP tensors a dense channels-last input is ONE C-ABI call per pass on the tensors as they lie, under
+// SHIFTND_SHIFT_DIM0 | SHIFTND_INTERLACE_FRAMES (shiftnd_interlace_frames.hip), through tin_forward_hip / tin_backward_hip under
+// InterlaceClOps -- the backward takes the route when the saved input and the gradient are both dense channels-last, grad_x then
+// has the gradient's strides; every other HIP tensor goes the plain op's way.  CPU tensors: the definition on the channels-last
+// per-clip ops, laid out in the argument's strides; a tensor that is not dense channels-last runs the plain op's routine, so its
+// results are the default's bit for bit.  The node keeps input, offsets and scales (InterlaceFunction<InterlaceClOps>).  A
+// namespace of its own, so that the op set of torchshifts_interlace:: stays.
+Tensor tin_cl_forward_cpu(const Tensor &input, const Tensor &offsets, const Tensor &scales, int64_t n_segment, int64_t padding_mode,
+                          bool active_flag) {
+    if (!is_channels_last_dense(input)) return tin_forward_cpu(input, offsets, scales, n_segment, padding_mode, active_flag);
+    TORCH_CHECK(input.device().is_cpu() && offsets.device().is_cpu() && scales.device().is_cpu(), "temporal_interlace_cl_cpu: expected CPU tensors");
+    tin_check(input, offsets, scales, n_segment, padding_mode);
+    const Tensor y = PerClipLearnableClOps::forward().call(input, offsets, n_segment, padding_mode, active_flag);
+    return in_layout_of(y * tin_plane_scales(scales, input), input);
+}
+
+std::tuple<Tensor, Tensor, Tensor> tin_cl_backward_cpu(const Tensor &grad, const Tensor &offsets, const Tensor &scales, const Tensor &input,
+                                                       int64_t n_segment, int64_t padding_mode, bool active_flag) {
+    if (!is_channels_last_dense(input) || !is_channels_last_dense(grad) || grad.sizes() != input.sizes())
+        return tin_backward_cpu(grad, offsets, scales, input, n_segment, padding_mode, active_flag);
+    TORCH_CHECK(grad.device().is_cpu() && input.device().is_cpu() && offsets.device().is_cpu() && scales.device().is_cpu(),
+                "temporal_interlace_cl_cpu: expected CPU tensors");
+    tin_check(input, offsets, scales, n_segment, padding_mode);
+    const Tensor plane = tin_plane_scales(scales, input);
+    const Tensor y = PerClipLearnableClOps::forward().call(input, offsets, n_segment, padding_mode, active_flag);
+    auto shifted = PerClipLearnableClOps::backward().call(grad * plane, offsets, input, n_segment, padding_mode, active_flag);
+    // (the sum autograd forms for the factor of y * plane)
+    const Tensor grad_scales = (grad * y).sum_to_size(plane.sizes()).reshape(scales.sizes()).to(scales.scalar_type());
+    return std::make_tuple(in_layout_of(std::get<0>(shifted), grad), std::get<1>(shifted), grad_scales);
 }
 
 // ---- channels-last per-clip temporal shift: torchshifts_per_clip_cl::temporal_shift_learnable_per_clip_cl / temporal_shift_per_clip_cl --
@@ -2187,21 +2250,40 @@ TORCH_LIBRARY_IMPL(torchshifts_per_clip_cl, CUDA, m) {
 // temporal interlacing (the per-clip shift times a scale per clip, frame and channel): a namespace of its own, so that the op sets
 // of the namespaces above stay
 TORCH_LIBRARY(torchshifts_interlace, m) {
-    m.def("torchshifts_interlace::temporal_interlace(Tensor input, Tensor offsets, Tensor scales, int n_segment, int padding_mode, bool active_flag) -> Tensor", &tin_public);
+    m.def("torchshifts_interlace::temporal_interlace(Tensor input, Tensor offsets, Tensor scales, int n_segment, int padding_mode, bool active_flag) -> Tensor", &tin_public<InterlaceOps>);
     m.def("torchshifts_interlace::_temporal_interlace_forward(Tensor input, Tensor offsets, Tensor scales, int n_segment, int padding_mode, bool active_flag) -> Tensor");
     m.def("torchshifts_interlace::_temporal_interlace_backward(Tensor grad, Tensor offsets, Tensor scales, Tensor input, int n_segment, int padding_mode, bool active_flag) -> (Tensor, Tensor, Tensor)");
 }
 TORCH_LIBRARY_IMPL(torchshifts_interlace, Autograd, m) {
-    m.impl("_temporal_interlace_forward", TORCH_FN(tin_autograd));
-    m.impl("_temporal_interlace_backward", TORCH_FN(tin_autograd_backward));
+    m.impl("_temporal_interlace_forward", TORCH_FN(tin_autograd<InterlaceOps>));
+    m.impl("_temporal_interlace_backward", TORCH_FN(tin_autograd_backward<InterlaceOps>));
 }
 TORCH_LIBRARY_IMPL(torchshifts_interlace, CPU, m) {
     m.impl("_temporal_interlace_forward", TORCH_FN(tin_forward_cpu));
     m.impl("_temporal_interlace_backward", TORCH_FN(tin_backward_cpu));
 }
 TORCH_LIBRARY_IMPL(torchshifts_interlace, CUDA, m) {
-    m.impl("_temporal_interlace_forward", TORCH_FN(tin_forward_hip));
-    m.impl("_temporal_interlace_backward", TORCH_FN(tin_backward_hip));
+    m.impl("_temporal_interlace_forward", TORCH_FN(tin_forward_hip<InterlaceOps>));
+    m.impl("_temporal_interlace_backward", TORCH_FN(tin_backward_hip<InterlaceOps>));
+}
+
+// temporal interlacing with the argument's layout kept: a namespace of its own, so that torchshifts_interlace:: keeps its op set
+TORCH_LIBRARY(torchshifts_interlace_cl, m) {
+    m.def("torchshifts_interlace_cl::temporal_interlace_cl(Tensor input, Tensor offsets, Tensor scales, int n_segment, int padding_mode, bool active_flag) -> Tensor", &tin_public<InterlaceClOps>);
+    m.def("torchshifts_interlace_cl::_temporal_interlace_cl_forward(Tensor input, Tensor offsets, Tensor scales, int n_segment, int padding_mode, bool active_flag) -> Tensor");
+    m.def("torchshifts_interlace_cl::_temporal_interlace_cl_backward(Tensor grad, Tensor offsets, Tensor scales, Tensor input, int n_segment, int padding_mode, bool active_flag) -> (Tensor, Tensor, Tensor)");
+}
+TORCH_LIBRARY_IMPL(torchshifts_interlace_cl, Autograd, m) {
+    m.impl("_temporal_interlace_cl_forward", TORCH_FN(tin_autograd<InterlaceClOps>));
+    m.impl("_temporal_interlace_cl_backward", TORCH_FN(tin_autograd_backward<InterlaceClOps>));
+}
+TORCH_LIBRARY_IMPL(torchshifts_interlace_cl, CPU, m) {
+    m.impl("_temporal_interlace_cl_forward", TORCH_FN(tin_cl_forward_cpu));
+    m.impl("_temporal_interlace_cl_backward", TORCH_FN(tin_cl_backward_cpu));
+}
+TORCH_LIBRARY_IMPL(torchshifts_interlace_cl, CUDA, m) {
+    m.impl("_temporal_interlace_cl_forward", TORCH_FN(tin_forward_hip<InterlaceClOps>));
+    m.impl("_temporal_interlace_cl_backward", TORCH_FN(tin_backward_hip<InterlaceClOps>));
 }
 
 // the in-place temporal shift: its own namespace (the op set of torchshifts:: is pinned)

@@ -28,6 +28,9 @@ CLIP_FRAMES = 0x4000  # SHIFTND_CLIP_FRAMES: with SHIFT_DIM0 -- every tensor is 
 INTERLACE = 0x8000    # SHIFTND_INTERLACE: with SHIFT_DIM0 -- temporal interlacing: the per-clip shift times a scale per (n, t, c) plane; weights /
 #                       grad_w are ONE packed array, [N, C] offsets followed by [N, T, C] scales; segment-major tensors, forward (both
 #                       modes) and backward
+INTERLACE_FRAMES = 0x10000  # SHIFTND_INTERLACE_FRAMES: with SHIFT_DIM0 -- temporal interlacing of dense channels-last tensors (as under
+#                       FRAMES) under the packed table of INTERLACE; the frame kernels serve forward (both modes) and backward, or the
+#                       call is refused
 PATH_NONE, PATH_EMPTY, PATH_PLANE, PATH_STRIDED, PATH_SWEEP, PATH_CL = range(6)
 
 DTYPES = {torch.float32: F32, torch.float64: F64, torch.float16: F16, torch.bfloat16: BF16,
@@ -141,7 +144,7 @@ def check_borders(sizes, user, ndim):
 
 
 def problem(x, pad, active, borders, dtype=None, w=None, shift_dim0=False, frames=False, per_clip=False, stream=False,
-            clip_frames=False, interlace=False):
+            clip_frames=False, interlace=False, interlace_frames=False):
     """w: the weights of the call, if it has float weights -- fp32 weights with an fp16 / bf16 `x` set WEIGHTS_F32 (mixed precision);
     shift_dim0: set SHIFT_DIM0 (the temporal shift: w is [C] and acts on spatial dim 0; x a segment-major view, or, for the
     sparse forward and the quantized forward, a dense channels-last view [N, C, T, M] with strides {T*M*C, 1, M*C, C});
@@ -149,7 +152,8 @@ def problem(x, pad, active, borders, dtype=None, w=None, shift_dim0=False, frame
     per_clip: set PER_CLIP (with shift_dim0: w is [N, C], one row per clip, x a segment-major view);
     stream: set STREAM (with shift_dim0: x is the state viewed as [B, C, D, M], see online_views);
     clip_frames: set CLIP_FRAMES (with shift_dim0: w is [N, C], one row per clip, every tensor a dense channels-last view);
-    interlace: set INTERLACE (with shift_dim0: w is the packed table -- N * C offsets, then N * T * C scales -- x a segment-major view)"""
+    interlace: set INTERLACE (with shift_dim0: w is the packed table -- N * C offsets, then N * T * C scales -- x a segment-major view);
+    interlace_frames: set INTERLACE_FRAMES (with shift_dim0: w is that packed table, every tensor a dense channels-last view)"""
     p = Problem()
     p.ndim = x.dim() - 2
     p.dtype = DTYPES[x.dtype] if dtype is None else dtype
@@ -167,6 +171,8 @@ def problem(x, pad, active, borders, dtype=None, w=None, shift_dim0=False, frame
         p.dtype |= CLIP_FRAMES
     if interlace:
         p.dtype |= INTERLACE
+    if interlace_frames:
+        p.dtype |= INTERLACE_FRAMES
     p.padding_mode = int(pad)
     p.active = int(bool(active))
     for i in range(5):
@@ -187,16 +193,16 @@ def _stream():
 
 
 def forward(x, w, pad, active, borders=None, out=None, shift_dim0=False, frames=False, per_clip=False, clip_frames=False,
-            interlace=False):
+            interlace=False, interlace_frames=False):
     """x, w: device tensors (float dtypes; w of x's dtype, or fp32 with an fp16 / bf16 x).  Returns a new contiguous output (or
     fills `out`).  shift_dim0: the flagged call (w [C]; x and out segment-major views, or -- active False -- both dense
     channels-last views, memory order N, S0, S1, S2, C: pass `out`, a new output is contiguous).  frames: with shift_dim0, the
     channels-last call in both modes (pass `out`).  out=x with shift_dim0 (active False): the in-place call, either dense layout.
     per_clip: with shift_dim0, w is [N, C] and x, out are segment-major views.  clip_frames: with shift_dim0, w is [N, C] and x, out
     are dense channels-last views (pass `out`).  interlace: with shift_dim0, w is the packed table (pack_interlace) and x, out are
-    segment-major views."""
+    segment-major views.  interlace_frames: with shift_dim0, w is the packed table and x, out are dense channels-last views (pass `out`)."""
     p = problem(x, pad, active, borders, w=w, shift_dim0=shift_dim0, frames=frames, per_clip=per_clip, clip_frames=clip_frames,
-                interlace=interlace)
+                interlace=interlace, interlace_frames=interlace_frames)
     if out is None:
         out = _new(out_shape(x, borders), x)
     w = w.contiguous()
@@ -206,27 +212,28 @@ def forward(x, w, pad, active, borders=None, out=None, shift_dim0=False, frames=
 
 
 def backward_workspace(x, pad, active, borders=None, shift_dim0=False, frames=False, per_clip=False, clip_frames=False,
-                       interlace=False):
+                       interlace=False, interlace_frames=False):
     p = problem(x, pad, active, borders, shift_dim0=shift_dim0, frames=frames, per_clip=per_clip, clip_frames=clip_frames,
-                interlace=interlace)
+                interlace=interlace, interlace_frames=interlace_frames)
     return torch.empty(int(lib().shiftnd_backward_workspace_bytes(ctypes.byref(p))), dtype=torch.uint8, device=x.device)
 
 
 def backward(grad_out, w, x, pad, active, borders=None, grad_x=None, grad_w=None, workspace=None, shift_dim0=False, frames=False,
-             per_clip=False, clip_frames=False, interlace=False):
+             per_clip=False, clip_frames=False, interlace=False, interlace_frames=False):
     """grad_w comes back in w's dtype (fp32 for fp32 weights with a 16-bit x).  frames: with shift_dim0, grad_out, x and grad_x are
     dense channels-last views (pass `grad_x`).  per_clip: with shift_dim0, w and grad_w are [N, C].  clip_frames: with shift_dim0,
     both: dense channels-last views (pass `grad_x`), w and grad_w [N, C].  interlace: with shift_dim0, w and grad_w are packed tables
-    (pack_interlace / unpack_interlace)"""
+    (pack_interlace / unpack_interlace).  interlace_frames: with shift_dim0, the packed tables with dense channels-last views (pass
+    `grad_x`)"""
     p = problem(x, pad, active, borders, w=w, shift_dim0=shift_dim0, frames=frames, per_clip=per_clip, clip_frames=clip_frames,
-                interlace=interlace)
+                interlace=interlace, interlace_frames=interlace_frames)
     w = w.contiguous()
     if grad_x is None:
         grad_x = _new(x.shape, x)
     if grad_w is None:
         grad_w = _new(w.shape, w)
     if workspace is None:
-        workspace = backward_workspace(x, pad, active, borders, shift_dim0, frames, per_clip, clip_frames, interlace)
+        workspace = backward_workspace(x, pad, active, borders, shift_dim0, frames, per_clip, clip_frames, interlace, interlace_frames)
     check(lib().shiftnd_backward(ctypes.byref(p), grad_out.data_ptr(), strides5(grad_out), x.data_ptr(), strides5(x),
                                  w.data_ptr(), grad_x.data_ptr(), strides5(grad_x), grad_w.data_ptr(),
                                  workspace.data_ptr(), workspace.numel(), _stream()), "shiftnd_backward")

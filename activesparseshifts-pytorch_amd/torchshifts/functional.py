@@ -337,12 +337,26 @@ def temporal_shift_learnable_per_clip_func(input: Tensor, weights: Tensor, n_seg
 # alone, and the autograd node keeps input, offsets and scales -- no shifted activation of the output's size.  float32 / float64 out
 # and input.grad carry the composition's bits; float16 / bfloat16 are interpolated and scaled in float32 and rounded once; both table
 # gradients are deterministic.  Group tables [N, G] / [N, T, G] (C % G == 0) are expanded here, so autograd sums a group's gradient.
+#
+# memory_format: torch.contiguous_format (the default) is the call above, a contiguous result whatever the input's layout.  With
+# torch.preserve_format a dense channels-last input (as for temporal_shift_func) comes back in its own strides with the same values,
+# and input.grad takes the layout of the incoming gradient when that is dense channels-last too; every other input gives what the
+# default gives.  On HIP tensors the channels-last tensors are served as they lie, one kernel per pass
+# (csrc/shiftnd_interlace_frames.hip), no layout change in either direction, any n_segment; the node keeps input, offsets and scales.
+# The TIN layer's own tables (four channel groups over the fold) make every 16-byte piece of a pixel's channel row uniform, the
+# kernels' fast path; an ungrouped [N, C] table moves channels one by one.
 def temporal_interlace_func(input: Tensor, offsets: Tensor, scales: Tensor, n_segment: int, padding_mode: int = 0,
-                            active_flag: bool = True) -> Tensor:
+                            active_flag: bool = True, memory_format: torch.memory_format = torch.contiguous_format) -> Tensor:
     """Shift the channels of a [N * n_segment, C, ...] tensor (2 to 5 dims) across the frames of each clip by offsets[n, c]
     (out[t] = x[t - w]; interpolated with active_flag, rounded without) and weight frame t of clip n by scales[n, t, c];
-    differentiable in input, offsets and scales.  offsets: [N, C] or [N, G]; scales: [N, n_segment, C] or [N, n_segment, G]."""
+    differentiable in input, offsets and scales.  offsets: [N, C] or [N, G]; scales: [N, n_segment, C] or [N, n_segment, G].
+    memory_format=torch.preserve_format keeps a dense channels-last input's layout; such a call needs N * n_segment * C < 2^31 (the
+    packed table's index, as the default call does) and raises a RuntimeError ("invalid argument") beyond it.  On the GPU it pays
+    in the forward and in memory; for float16 / bfloat16 TRAINING the composition temporal_shift_learnable_per_clip_func(...,
+    memory_format=torch.preserve_format) * scales is currently faster (README)."""
     name = "temporal_interlace_func()"
+    assert memory_format in (torch.contiguous_format, torch.preserve_format), \
+        f"{name} expected memory_format to be torch.contiguous_format or torch.preserve_format, but it is {memory_format}"
     assert offsets.is_floating_point(), f"{name}: expected float offsets, but they are {offsets.dtype}"
     assert scales.is_floating_point(), f"{name}: expected float scales, but they are {scales.dtype}"
     offsets = _per_clip_table(name, input, offsets, n_segment, padding_mode, "offsets")
@@ -357,6 +371,8 @@ def temporal_interlace_func(input: Tensor, offsets: Tensor, scales: Tensor, n_se
     assert scales.dtype == offsets.dtype, f"{name}: expected offsets and scales of one dtype, but they are {offsets.dtype} and {scales.dtype}"
     if scales.shape[2] != channels:
         scales = scales.repeat_interleave(channels // scales.shape[2], dim=2)
+    if memory_format == torch.preserve_format:
+        return torch.ops.torchshifts_interlace_cl.temporal_interlace_cl(input, offsets, scales, n_segment, padding_mode, bool(active_flag))
     return torch.ops.torchshifts_interlace.temporal_interlace(input, offsets, scales, n_segment, padding_mode, bool(active_flag))
 
 

@@ -627,13 +627,19 @@ class TemporalInterlace(nn.Module):
         in_channels (int): C.
         shift_div (int): the first C // shift_div channels are interlaced. Default 1 (all of them).
         padding (str): 'zeros' | 'border' | 'periodic' | 'reflect' | 'symmetric'. Default 'zeros'.
+        memory_format: torch.contiguous_format (default: a contiguous output) or torch.preserve_format (a dense channels-last
+            input comes back channels-last; on the GPU one kernel per pass on the tensor as it lies -- the layer's own tables
+            are the frame kernels' fast path).  A plain attribute, not part of state_dict.
     forward(x) -> output, the tensor alone.
     """
 
-    def __init__(self, n_segment, in_channels, shift_div=1, padding='zeros'):
+    def __init__(self, n_segment, in_channels, shift_div=1, padding='zeros', memory_format=torch.contiguous_format):
         super().__init__()
         assert padding.lower() in paddings_dict.keys(), f'incorrect padding option: {padding}'
         assert int(n_segment) >= 1, 'n_segment must be >= 1'
+        assert memory_format in (torch.contiguous_format, torch.preserve_format), \
+            f'memory_format must be torch.contiguous_format or torch.preserve_format, not {memory_format}'
+        self.memory_format = memory_format
         self.n_segment = int(n_segment)
         self.in_channels = int(in_channels)
         self.shift_div = int(shift_div)
@@ -663,8 +669,9 @@ class TemporalInterlace(nn.Module):
         assert input.shape[1] == self.in_channels and input.shape[0] % self.n_segment == 0, \
             f'expected a [N * {self.n_segment}, {self.in_channels}, ...] tensor, but it is shape is {tuple(input.shape)}'
         offsets, scales = self.tables(input)
-        return temporal_interlace_func(input, offsets, scales, self.n_segment, self.padding, True)
+        return temporal_interlace_func(input, offsets, scales, self.n_segment, self.padding, True, self.memory_format)
 
     def extra_repr(self):
         pad = {v: k for k, v in paddings_dict.items()}[self.padding]
-        return f'n_segment={self.n_segment}, in_channels={self.in_channels}, shift_div={self.shift_div}, padding_method={pad}'
+        fmt = '' if self.memory_format == torch.contiguous_format else f', memory_format={self.memory_format}'
+        return f'n_segment={self.n_segment}, in_channels={self.in_channels}, shift_div={self.shift_div}, padding_method={pad}' + fmt

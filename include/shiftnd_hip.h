@@ -286,6 +286,35 @@ typedef enum shiftnd_dtype {
  */
 #define SHIFTND_INTERLACE 0x8000
 
+/*
+ * Temporal interlacing on CHANNELS-LAST tensors: SHIFTND_INTERLACE's problem and packed table on SHIFTND_FRAMES' layout, under a bit
+ * of its own (SHIFTND_INTERLACE on channels-last strides, and beside any other bit of the family, stays refused).  OR-ed onto a
+ * float dtype TOGETHER WITH SHIFTND_SHIFT_DIM0 (and, for F16 / BF16, optionally SHIFTND_WEIGHTS_F32): the tensors are dense
+ * channels-last exactly as under SHIFTND_FRAMES (memory order N, S0, S1, S2, C; strides {T*M*C, 1, M*C, C}), and `weights` /
+ * `grad_w` are the ONE packed array of SHIFTND_INTERLACE: the N * C offsets [N, C] immediately followed by the N * S0 * C scales
+ * [N, S0, C].  Values and numerics are SHIFTND_INTERLACE's: out and grad_x carry the bits of that call on contiguous copies of the
+ * same data, in every dtype; both gradient tables are fp64 sums in a fixed order, narrowed once, deterministic.
+ *   shiftnd_forward, both values of p->active: frames_interlace_forward / *_ragged (pieces of a pixel's channel row under 16 bytes).
+ *   shiftnd_backward, full form: frames_interlace_backward / *_ragged.  S0 is not bounded: nothing in the kernels is sized by it.
+ *   shiftnd_backward_workspace_bytes, a function of the geometry alone: with M = S1 * S2 pixels a frame, es the element size,
+ *       pieces = ceil(C * es / 16),  rps = pieces < 256 ? 256 / pieces : 1   (integer division),
+ *       steps  = 8, halved while steps > 1 and N * ceil(M / (rps * steps)) < 768,
+ *       chunks = ceil(M / (rps * steps)),
+ *   it answers chunks * N * C * (1 + S0) * 8 bytes: one double per workgroup and offset, and per workgroup, frame and scale;
+ *   sizeof(double) for an empty problem.
+ *   Served calls report SHIFTND_PATH_CL; an empty problem SHIFTND_PATH_EMPTY, with the N * C + N * S0 * C entries of grad_w zeroed.
+ *   Accepted: what SHIFTND_FRAMES accepts (ndim 2 or 3; F32, F64, F16, BF16; every padding mode; the whole window; element-aligned
+ *   bases; its bounds), N * S0 * C below 2^31 (the scales' index), N * chunks below 2^31 and the records below 2^46 bytes.
+ *   Errors, before anything is launched (the workspace query answers 0): a quantized dtype, the bit on shiftnd_forward_quantized or
+ *   on the pooled entry points, and the bit without SHIFTND_SHIFT_DIM0 (an unknown dtype bit, on every entry point):
+ *   SHIFTND_ERR_UNSUPPORTED_DTYPE; the bit beside SHIFTND_FRAMES, SHIFTND_PER_CLIP, SHIFTND_STREAM, SHIFTND_CLIP_FRAMES or
+ *   SHIFTND_INTERLACE, out == x, ndim 1, a cut window, any tensor that is not dense channels-last (segment-major strides), the
+ *   x == NULL form of shiftnd_backward, N * S0 * C of 2^31 or more, a size beyond the bounds: SHIFTND_ERR_INVALID_ARGUMENT; a
+ *   workspace below the plan: SHIFTND_ERR_WORKSPACE_TOO_SMALL.
+ * Without the bit nothing changes.  (0x800 stays unassigned.)
+ */
+#define SHIFTND_INTERLACE_FRAMES 0x10000
+
 typedef enum shiftnd_status {
     SHIFTND_OK = 0,
     SHIFTND_ERR_INVALID_ARGUMENT = -1,
@@ -309,7 +338,7 @@ typedef enum shiftnd_path {
 /* Problem geometry shared by the entry points. */
 typedef struct shiftnd_problem {
     int32_t ndim;          /* spatial dims: 1, 2 or 3 */
-    int32_t dtype;         /* shiftnd_dtype of input/output (and of float weights), optionally | SHIFTND_WEIGHTS_F32 | SHIFTND_SHIFT_DIM0 | SHIFTND_FRAMES | SHIFTND_PER_CLIP | SHIFTND_STREAM | SHIFTND_CLIP_FRAMES | SHIFTND_INTERLACE */
+    int32_t dtype;         /* shiftnd_dtype of input/output (and of float weights), optionally | SHIFTND_WEIGHTS_F32 | SHIFTND_SHIFT_DIM0 | SHIFTND_FRAMES | SHIFTND_PER_CLIP | SHIFTND_STREAM | SHIFTND_CLIP_FRAMES | SHIFTND_INTERLACE | SHIFTND_INTERLACE_FRAMES */
     int32_t padding_mode;  /* 0..4 */
     int32_t active;        /* 0: sparse shift (rounded integer shift); 1: active (interpolated) */
     int64_t sizes[5];      /* input N, C, H, W, D */
