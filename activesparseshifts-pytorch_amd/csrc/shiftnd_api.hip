@@ -424,6 +424,35 @@ int frames_quantized_call(const shiftnd_problem *p, const void *x, const int64_t
     return finish(frames_forward(g, q.dtype, x, wq, wq_dtype, wzp, fill, false, out, static_cast<hipStream_t>(stream)));
 }
 
+// shiftnd_forward_quantized under the flag with an fp32 table: the quantized INTERPOLATING temporal shift (shiftnd_tshift_quant.hip) --
+// I8 / U8 / I32 segment-major tensors, out of place, p->active == 1, the whole window, `wq` the fp32 [C] table (w_zero_point 0).  Served
+// by its one kernel or refused before anything is launched: no other flag bit, no channels-last view; p->active == 0 stays an
+// unsupported table type (the sparse shift is the integer table's call)
+int tshift_quantized_call(const shiftnd_problem *p, const void *x, const int64_t *xs, const void *wq, int64_t wzp, int64_t xzp, void *out,
+                          const int64_t *os, void *stream) {
+    const int flags = SHIFTND_WEIGHTS_F32 | SHIFTND_SHIFT_DIM0 | SHIFTND_FRAMES | SHIFTND_PER_CLIP | SHIFTND_STREAM | SHIFTND_CLIP_FRAMES |
+                      SHIFTND_INTERLACE | SHIFTND_INTERLACE_FRAMES;
+    shiftnd_problem q = *p;
+    q.dtype = p->dtype & ~flags;
+    if (!is_quant_dtype(q.dtype)) return SHIFTND_ERR_UNSUPPORTED_DTYPE;   // (the flag with a float dtype: no quantized dtype)
+    // the sparse shift has no float table: what such a call was answered before this form existed (tests/test_temporal_cl_cpu.py pins it)
+    if (!p->active) return SHIFTND_ERR_UNSUPPORTED_DTYPE;
+    if ((p->dtype & flags) != SHIFTND_SHIFT_DIM0 || wzp != 0) return SHIFTND_ERR_INVALID_ARGUMENT;
+    if (out && out == x) return SHIFTND_ERR_INVALID_ARGUMENT;   // (x and out are __restrict__: there is no in-place form)
+    Geometry g;
+    const int rc = build_geometry(&q, xs, os, nullptr, g);
+    if (rc != SHIFTND_OK) return rc;
+    if (!tshift_quantized_geometry_ok(g, q.dtype, xzp)) return SHIFTND_ERR_INVALID_ARGUMENT;   // (a cut window, ndim 1, the sizes)
+    if (empty_geometry(g)) {
+        g_last_path = SHIFTND_PATH_EMPTY;
+        return SHIFTND_OK;
+    }
+    if (!x || !wq || !out || !aligned_to(wq, sizeof(float))) return SHIFTND_ERR_INVALID_ARGUMENT;
+    if (!tshift_tensor_ok(g, q.dtype, x, g.xs) || !tshift_tensor_ok(g, q.dtype, out, g.os)) return SHIFTND_ERR_INVALID_ARGUMENT;
+    g_last_path = SHIFTND_PATH_PLANE;
+    return finish(tshift_quantized_forward(g, q.dtype, x, wq, xzp, out, static_cast<hipStream_t>(stream)));
+}
+
 // the backward under the flag, both layouts: `frames` (SHIFTND_FRAMES) picks the sizes, the tensor check, the workspace and the kernels
 int tshift_backward_call(const shiftnd_problem *p, const void *go, const int64_t *gos, const void *x, const int64_t *xs, const void *w,
                          void *gx, const int64_t *gxs, void *gw, void *workspace, size_t workspace_bytes, void *stream) {
@@ -738,6 +767,10 @@ int shiftnd_forward_quantized(const shiftnd_problem *p, const void *x, const int
                               int32_t wq_dtype, int64_t w_zero_point, int64_t x_zero_point, void *out,
                               const int64_t out_strides[5], void *stream) {
     if (!p || !x_strides || !out_strides) return SHIFTND_ERR_INVALID_ARGUMENT;
+    // an fp32 table under the flag: the quantized interpolating temporal shift, or its refusal (without the flag a float table
+    // stays an unsupported dtype, below)
+    if ((p->dtype & SHIFTND_SHIFT_DIM0) && wq_dtype == SHIFTND_F32)
+        return tshift_quantized_call(p, x, x_strides, wq, w_zero_point, x_zero_point, out, out_strides, stream);
     // the online step (SHIFTND_STREAM beside the flag; alone it is an unknown dtype bit): SHIFTND_FRAMES / SHIFTND_PER_CLIP beside it
     // are its own refusal, not an unknown dtype
     const bool online = (p->dtype & SHIFTND_SHIFT_DIM0) && (p->dtype & SHIFTND_STREAM);

@@ -231,6 +231,12 @@ size_t tshift_backward_workspace(const Geometry &g, int dtype);
 int tshift_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, bool per_clip, void *gx,
                     void *gw, void *workspace, hipStream_t st);
 
+// ---- the quantized interpolating temporal shift (shiftnd_tshift_quant.hip; shiftnd_forward_quantized under SHIFTND_SHIFT_DIM0 with an
+// fp32 table): tshift_forward's problem on I8 / U8 / I32 segment-major tensors, `w` an fp32 [C] array, `zp` the tensors' zero point.
+// tshift_quantized_geometry_ok: the sizes (fewer than 2^31 - 16 elements) and the zero point's range; the tensors pass tshift_tensor_ok.
+bool tshift_quantized_geometry_ok(const Geometry &g, int dtype, int64_t zp);
+int tshift_quantized_forward(const Geometry &g, int dtype, const void *x, const void *w, int64_t zp, void *out, hipStream_t st);
+
 // ---- temporal interlacing (shiftnd_interlace.hip; SHIFTND_SHIFT_DIM0 | SHIFTND_INTERLACE): the per-clip temporal shift times a scale
 // per (n, t, c) plane.  `w` and `gw` are ONE packed array each: [N, C] offsets followed by [N, S0, C] scales.  The geometry and the
 // tensors pass tshift_geometry_ok / tshift_tensor_ok (which holds N * S0 * C below 2^31: the scales' index and the reduction's entry

@@ -34,7 +34,7 @@
 // ((chunk * N + n) * C + c): `chunks` groups of N * C entries, so that launch_reduce_weight_grads sums per (n, c) -- the same
 // records, the same workspace bytes, a fixed order.  No new kernel, no template parameter.
 //
-// Not built: the quantized form, a cut window, channels-last tensors.
+// Not built: a cut window, channels-last tensors.  (The quantized interpolating forward: shiftnd_tshift_quant.hip.)
 #include "shiftnd_temporal.hpp"
 
 namespace shiftnd {

@@ -25,9 +25,11 @@
 //                 on CPU tensors), a family that writes its argument
 //   online        torchshifts_online::temporal_shift_online_ / temporal_shift_online_quantized_: one frame per call against a cached
 //                 state of the previous frames, both written (composes on CPU tensors); inference only, no Autograd key
+//   quantized learnable  torchshifts_quantized_learnable::temporal_shift_learnable_quantized: the interpolating temporal shift of a
+//                 per-tensor quantized tensor in the integer domain, an fp32 table; inference only, no Autograd key
 //
 // Keys: the Autograd, CUDA and QuantizedCUDA kernels of every family are registered here.  The CPU / QuantizedCPU kernels that
-// compute (shift, fixed, fixed pool, temporal, temporal_shift_quantized) live in torch_cpu_backend.cpp; the ones that compose other
+// compute (shift, fixed, fixed pool, temporal, temporal_shift_quantized, quantized learnable) live in torch_cpu_backend.cpp; the ones that compose other
 // ops (pool, temporal cl, learnable, learnable cl) are registered here.
 //
 // Helpers every family uses: typed_op + one *Ops struct per family (cached dispatcher handles),
@@ -2034,6 +2036,51 @@ Tensor &online_quantized_hip(Tensor &input, Tensor &state, const Tensor &shifts)
     return input;
 }
 
+// ---- quantized interpolating temporal shift: torchshifts_quantized_learnable::temporal_shift_learnable_quantized ------------------
+// temporal_shift_learnable's interpolation on the int_repr of a per-tensor quantized tensor (quint8, qint8, qint32), defined in the
+// integer domain: with q = int_repr, zp the zero point and F = fp32 (8-bit) / fp64 (qint32),
+//     out = clamp(zp + rint(temporal_shift_learnable((q - zp).to(F), weights.to(F), active_flag=True)), the dtype's range)
+// Scale and zero point pass through, the result is contiguous, there is no gradient.  active_flag == False IS temporal_shift_quantized
+// under the same table (which rounds it half to even): that route, nothing new launched.  On HIP tensors ONE flagged
+// shiftnd_forward_quantized call with the fp32 table as it is (shiftnd_tshift_quant.hip): no host sync, nothing allocated but the output.
+// (tslq_check is also called from torch_cpu_backend.cpp)
+void tslq_check(const Tensor &input, const Tensor &weights, int64_t n_segment, int64_t padding_mode) {
+    const char *op_name = "temporal_shift_learnable_quantized";
+    TORCH_CHECK(input.is_quantized(), op_name, ": expected a quantized input");
+    TORCH_CHECK(input.qscheme() == at::kPerTensorAffine, op_name, ": expected a per-tensor quantized input");
+    segment_check(op_name, input, weights, n_segment, padding_mode, "weights", !weights.is_quantized() && weights.scalar_type() == at::kFloat,
+                  "fp32");
+    TORCH_CHECK(!weights.requires_grad(), op_name, ": weights must not require grad (the quantized op has no gradient; pass weights.detach())");
+}
+
+// the kernel counts the tensor's elements in 32 bits and the flagged call has no fallback: refuse a larger tensor before anything is
+// allocated
+void tslq_check_size(const Tensor &input) {
+    TORCH_CHECK(input.numel() + 16 < (1LL << 31), "temporal_shift_learnable_quantized: a tensor of ", input.numel(),
+                " elements is beyond the kernel's limit of 2^31 - 16 units; split the batch");
+}
+
+Tensor tslq_hip(const Tensor &input_, const Tensor &weights, int64_t n_segment, int64_t padding_mode, bool active_flag) {
+    tslq_check(input_, weights, n_segment, padding_mode);   // (first: a table on another device is named as such under either key)
+    TORCH_CHECK(input_.is_cuda(), "temporal_shift_learnable_quantized: expected a CUDA tensor");
+    if (!active_flag) return temporal_quantized_hip(input_, weights, n_segment, padding_mode);
+    c10::DeviceGuard device_guard(input_.device());
+    const int dtype = quant_dtype(input_.scalar_type(), "temporal_shift_learnable_quantized_cuda");
+    tslq_check_size(input_);
+    const Tensor t = is_channels_last_dense(input_) ? channels_last_to_contiguous(input_) : input_.contiguous();   // (a tile transpose of the int_repr)
+    Tensor out = at::_empty_affine_quantized(t.sizes(), t.options().memory_format(at::MemoryFormat::Contiguous), t.q_scale(),
+                                             t.q_zero_point(), c10::nullopt);
+    if (t.numel() == 0) return out;
+    const Tensor w = weights.contiguous();   // ([C] and [C, 1] are the same C floats)
+    shiftnd_problem p;
+    int64_t st[5];
+    segment_problem(p, st, t, n_segment, padding_mode, true, dtype | SHIFTND_SHIFT_DIM0, false, "temporal_shift_learnable_quantized");
+    check_status(shiftnd_forward_quantized(&p, t.data_ptr(), st, w.data_ptr(), SHIFTND_F32, 0, t.q_zero_point(), out.data_ptr(), st,
+                                           current_stream(t)),
+                 "temporal_shift_learnable_quantized (HIP)");
+    return out;
+}
+
 int64_t cuda_version() { return -1; }  // no CUDA toolkit: extension.py only compares when torch.version.cuda is set
 int64_t hip_version() { return HIP_VERSION; }
 
@@ -2308,3 +2355,11 @@ TORCH_LIBRARY_IMPL(torchshifts_online, CPU, m) { m.impl("temporal_shift_online_"
 TORCH_LIBRARY_IMPL(torchshifts_online, CUDA, m) { m.impl("temporal_shift_online_", TORCH_FN(online_hip)); }
 TORCH_LIBRARY_IMPL(torchshifts_online, QuantizedCPU, m) { m.impl("temporal_shift_online_quantized_", TORCH_FN(online_quantized_cpu)); }
 TORCH_LIBRARY_IMPL(torchshifts_online, QuantizedCUDA, m) { m.impl("temporal_shift_online_quantized_", TORCH_FN(online_quantized_hip)); }
+
+// the quantized interpolating temporal shift: its own namespace (the op sets above are pinned).  No Autograd key: an inference op
+// (QuantizedCPU: torch_cpu_backend.cpp)
+TORCH_LIBRARY(torchshifts_quantized_learnable, m) {
+    m.def("torchshifts_quantized_learnable::temporal_shift_learnable_quantized(Tensor input, Tensor weights, int n_segment, int padding_mode, bool active_flag) -> Tensor");
+}
+
+TORCH_LIBRARY_IMPL(torchshifts_quantized_learnable, QuantizedCUDA, m) { m.impl("temporal_shift_learnable_quantized", TORCH_FN(tslq_hip)); }

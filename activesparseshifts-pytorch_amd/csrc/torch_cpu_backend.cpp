@@ -427,6 +427,7 @@ template <int ND> Tensor shift_fixed_pool_backward_cpu(const Tensor &grad, const
 }  // namespace cpu
 void temporal_check(const at::Tensor &input, const at::Tensor &shifts, int64_t n_segment, int64_t padding_mode);   // torch_binding.cpp
 void temporal_quantized_check(const at::Tensor &input, const at::Tensor &shifts, int64_t n_segment, int64_t padding_mode);
+void tslq_check(const at::Tensor &input, const at::Tensor &weights, int64_t n_segment, int64_t padding_mode);
 namespace cpu {
 
 // the planes of a contiguous [N*T, C, plane] tensor, copied or filled; `fill`: the element's bit pattern (0, or a quantized tensor's
@@ -492,6 +493,59 @@ Tensor temporal_quantized_cpu(const Tensor &input, const Tensor &shifts, int64_t
     return out;
 }
 
+// temporal_shift_learnable_quantized: the interpolating temporal shift of a per-tensor quantized tensor in the integer domain
+// (torch_binding.cpp) -- per plane (n, t, c) the two source frames of forward_float's 1-D maps, per element
+// clamp(zp + rint(lerp1(q0 - zp, q1 - zp, dw))) in CT (fp32 for the 8-bit types, fp64 for qint32); a filled frame contributes 0
+template <typename R, typename CT>
+void tslq_planes(const R *x, R *out, int64_t N, int64_t T, int64_t C, int64_t M, const float *w, int pad, int64_t zp_, CT lo, CT hi) {
+    const CT zp = static_cast<CT>(zp_);
+    at::parallel_for(0, N * T, 1, [&](int64_t begin, int64_t end) {
+        for (int64_t nt = begin; nt < end; ++nt) {
+            const int64_t n = nt / T, t = nt % T;
+            for (int64_t c = 0; c < C; ++c) {
+                int64_t iw;
+                CT dw;
+                prep_forward<CT>(static_cast<CT>(w[c]), true, iw, dw);
+                const int64_t s0 = T == 1 ? 0 : pad_index(t - iw, T, pad), s1 = T == 1 ? 0 : pad_index(t + 1 - iw, T, pad);
+                const R *a = s0 >= 0 ? x + ((n * T + s0) * C + c) * M : nullptr, *b = s1 >= 0 ? x + ((n * T + s1) * C + c) * M : nullptr;
+                R *o = out + (nt * C + c) * M;
+                for (int64_t m = 0; m < M; ++m) {
+                    const CT va = a ? static_cast<CT>(a[m]) - zp : CT(0), vb = b ? static_cast<CT>(b[m]) - zp : CT(0);
+                    const CT v = std::nearbyint(lerp1(va, vb, dw)) + zp;
+                    o[m] = static_cast<R>(std::min(std::max(v, lo), hi));
+                }
+            }
+        }
+    });
+}
+
+Tensor tslq_cpu(const Tensor &input, const Tensor &weights, int64_t T, int64_t padding_mode, bool active_flag) {
+    tslq_check(input, weights, T, padding_mode);   // (first: a table on another device is named as such under either key)
+    TORCH_CHECK(input.device().is_cpu() && weights.device().is_cpu(), "temporal_shift_learnable_quantized_cpu: expected CPU tensors");
+    if (!active_flag) return temporal_quantized_cpu(input, weights, T, padding_mode);   // (rint of the table: the sparse shift)
+    const at::ScalarType st = input.scalar_type();
+    TORCH_CHECK(st == at::kQUInt8 || st == at::kQInt8 || st == at::kQInt32, "\"temporal_shift_learnable_quantized_cpu\" not implemented for '",
+                c10::toString(st), "'");
+    const Tensor t = input.contiguous();
+    Tensor out = at::_empty_affine_quantized(t.sizes(), t.options().memory_format(at::MemoryFormat::Contiguous), t.q_scale(),
+                                             t.q_zero_point(), c10::nullopt);
+    if (t.numel() == 0) return out;
+    const int64_t C = t.size(1), N = t.size(0) / T, M = t.numel() / (t.size(0) * C), zp = t.q_zero_point();
+    const Tensor wc = weights.contiguous();
+    const float *w = wc.data_ptr<float>();
+    const int pad = static_cast<int>(padding_mode);
+    if (st == at::kQUInt8)
+        tslq_planes<uint8_t, float>(static_cast<const uint8_t *>(t.data_ptr()), static_cast<uint8_t *>(out.data_ptr()), N, T, C, M, w, pad, zp,
+                                    0.0f, 255.0f);
+    else if (st == at::kQInt8)
+        tslq_planes<int8_t, float>(static_cast<const int8_t *>(t.data_ptr()), static_cast<int8_t *>(out.data_ptr()), N, T, C, M, w, pad, zp,
+                                   -128.0f, 127.0f);
+    else
+        tslq_planes<int32_t, double>(static_cast<const int32_t *>(t.data_ptr()), static_cast<int32_t *>(out.data_ptr()), N, T, C, M, w, pad, zp,
+                                     -2147483648.0, 2147483647.0);
+    return out;
+}
+
 template <int ND> Tensor qshift_forward_cpu(const Tensor &input, const Tensor &weights, const Tensor &borders,
                                             at::IntArrayRef new_size, int64_t padding_mode, bool /*active_flag*/) {
     TORCH_CHECK(input.is_quantized() && weights.is_quantized(), "q_shiftnd_cpu: expected quantized tensors");
@@ -554,4 +608,8 @@ TORCH_LIBRARY_IMPL(torchshifts, QuantizedCPU, m) {
     m.impl("_shift2d_backward", TORCH_FN(qshift_backward_cpu));
     m.impl("_shift3d_forward", TORCH_FN(qshift_forward_cpu<3>));
     m.impl("_shift3d_backward", TORCH_FN(qshift_backward_cpu));
+}
+
+TORCH_LIBRARY_IMPL(torchshifts_quantized_learnable, QuantizedCPU, m) {
+    m.impl("temporal_shift_learnable_quantized", TORCH_FN(tslq_cpu));
 }

@@ -21,6 +21,8 @@ def _default_static_mappings():
 
 tndm_mapping = _default_static_mappings()
 
-from .modules import OnlineTemporalShift, Shift1d, Shift2d, Shift3d, TemporalShift, new_quant_mapping  # noqa: E402,F401
+from .modules import LearnableTemporalShift, OnlineTemporalShift, Shift1d, Shift2d, Shift3d, TemporalShift, interpolating_quant_mapping, new_quant_mapping  # noqa: E402,F401
 
 quant_mapping = {**tndm_mapping, **new_quant_mapping}
+# ... for a net trained with LearnableTemporalShift(active_flag=True): its entry is quantized.LearnableTemporalShift
+quant_mapping_interpolating = {**tndm_mapping, **interpolating_quant_mapping}

@@ -41,6 +41,25 @@ def temporal_shift_quantized(input, shifts, n_segment, padding_mode=0, memory_fo
     return torch.ops.torchshifts.temporal_shift_quantized(input, shifts, int(n_segment), int(padding_mode))
 
 
+def temporal_shift_learnable_quantized(input, weights, n_segment, padding_mode=0, active_flag=True):
+    """The learnable temporal shift (torchshifts.functional.temporal_shift_learnable_func) of a per-tensor quantized
+    [N * n_segment, C, ...] tensor (quint8, qint8, qint32; 2 to 5 dims) under a trained fp32 table `weights` ([n_channels] or
+    [n_channels, 1], not requiring grad).  The result is defined in the integer domain: with q = input.int_repr(), zp the zero point
+    and F = fp32 (8-bit types) or fp64 (qint32),
+
+        out = clamp(zp + rint(temporal_shift_learnable_func((q - zp).to(F), weights.to(F), n_segment, padding_mode, True)))
+
+    rint half to even; zeros padding contributes 0, which is the zero point in the result.  The scale does not enter, nothing is
+    dequantized or requantized: the result has the input's scale, zero point and dtype, and is contiguous (a channels-last input
+    is made contiguous first).  On HIP tensors it is one kernel with the table passed as it is.  active_flag=False is
+    temporal_shift_quantized(input, weights, n_segment, padding_mode): the table rounded half to even.  No gradient."""
+    if not input.is_quantized:
+        raise ValueError("Input to 'temporal_shift_learnable_quantized' must be quantized!")
+    _assert_has_ops()
+    return torch.ops.torchshifts_quantized_learnable.temporal_shift_learnable_quantized(input, weights, int(n_segment), int(padding_mode),
+                                                                                         bool(active_flag))
+
+
 def temporal_shift_quantized_(input, shifts, n_segment, padding_mode=0):
     """temporal_shift_quantized written into `input`, which is returned with its scale, zero point and layout (the in-place
     torchshifts.functional.temporal_shift_func_ of a per-tensor quantized tensor).  On HIP tensors a dense input -- contiguous or

@@ -20,7 +20,7 @@ import torch
 
 import torchshifts.modules.shifts as shifts
 from torchshifts.functional import shift1d_pool_func, shift2d_pool_func, shift3d_pool_func
-from torchshifts.quantized.functional import shift1d_quantized, shift2d_quantized, shift3d_quantized, temporal_shift_quantized, temporal_shift_quantized_, temporal_shift_online_quantized, temporal_shift_online_quantized_
+from torchshifts.quantized.functional import shift1d_quantized, shift2d_quantized, shift3d_quantized, temporal_shift_quantized, temporal_shift_quantized_, temporal_shift_online_quantized, temporal_shift_online_quantized_, temporal_shift_learnable_quantized
 
 _POOL_FUNCS = {1: shift1d_pool_func, 2: shift2d_pool_func, 3: shift3d_pool_func}
 
@@ -171,6 +171,49 @@ class TemporalShift(shifts.TemporalShift):
         qshift = cls(mod.n_segment, mod.in_channels, fold_div=mod.fold_div, shifts=mod.shifts.detach().cpu(), padding=rp_dict[mod.padding],
                      memory_format=mod.memory_format, inplace=mod.inplace)
         return qshift.to(mod.shifts.device)
+
+
+class LearnableTemporalShift(torch.nn.Module):
+    """Quantized learnable Temporal Shift Module: the float LearnableTemporalShift on per-tensor quantized tensors (quint8, qint8,
+    qint32), interpolating in the integer domain (torchshifts.quantized.functional.temporal_shift_learnable_quantized).  `weight`
+    is a persistent fp32 buffer [in_channels, 1] -- the trained shifts as they are, never rounded under active_flag -- so a float
+    LearnableTemporalShift checkpoint's `weight` loads.  The output keeps the input's scale and zero point and is contiguous.
+
+    Arguments:
+        n_segment (int): frames per clip, T.
+        in_channels (int): channels of the input.
+        padding (str): 'zeros' | 'border' | 'periodic' | 'reflect' | 'symmetric'. Default 'zeros'.
+        active_flag (bool): interpolate between two frames. Default True; without it the shift is round(weight), half to even.
+    forward(x) -> output, the tensor alone.  from_float converts a LearnableTemporalShift, active or not, carrying active_flag,
+    padding and n_segment over.
+    """
+
+    def __init__(self, n_segment, in_channels, padding='zeros', active_flag=True):
+        super().__init__()
+        assert padding.lower() in shifts.paddings_dict.keys(), f'incorrect padding option: {padding}'
+        assert int(n_segment) >= 1, 'n_segment must be >= 1'
+        self.padding = shifts.paddings_dict[padding.lower()]
+        self.n_segment = int(n_segment)
+        self.in_channels = in_channels
+        self._active_flag = bool(active_flag)
+        self.register_buffer("weight", torch.zeros(in_channels, 1, dtype=torch.float32))
+
+    def forward(self, input):
+        return temporal_shift_learnable_quantized(input, self.weight, self.n_segment, self.padding, self._active_flag)
+
+    def _get_name(self):
+        return 'QuantizedLearnableTemporalShift'
+
+    def extra_repr(self):
+        return (f'n_segment={self.n_segment}, in_channels={self.in_channels}, padding_method={rp_dict[self.padding]}, '
+                f'Active shift on forward pass: {"Yes" if self._active_flag else "No"}')
+
+    @classmethod
+    def from_float(cls, mod):
+        assert isinstance(mod, shifts.LearnableTemporalShift), 'expected a LearnableTemporalShift module'
+        qshift = cls(mod.n_segment, mod.in_channels, padding=rp_dict[mod.padding], active_flag=mod._active_flag)
+        qshift.weight = mod.weight.detach().to(torch.float32).reshape(mod.in_channels, 1).clone()
+        return qshift
 
 
 class OnlineTemporalShift(shifts.OnlineTemporalShift):

@@ -125,6 +125,22 @@ typedef enum shiftnd_dtype {
  *   Errors, before anything is launched: p->active == 1 on the channels-last layout, x and out in different layouts (channels-last
  *   with segment-major or NCHW-dense), a size beyond the bounds: SHIFTND_ERR_INVALID_ARGUMENT.
  *
+ * Quantized, interpolating (the trained shift of a per-tensor quantized video tensor): shiftnd_forward_quantized under the flag with
+ * wq_dtype == SHIFTND_F32 -- wq is the fp32 [C] table of trained shifts, w_zero_point 0 -- interpolates I8 / U8 / I32 tensors in the
+ * integer domain.  With q the int_repr, zp = x_zero_point and (iw, dw) = (floor(w), w - floor(w)) in F = fp32 (I8 / U8) or fp64 (I32):
+ *     out = clamp(zp + rint((q[pad(t - iw)] - zp) * (1 - dw) + (q[pad(t - iw + 1)] - zp) * dw), the element type's range)
+ * two multiplies and one add in F, rint half to even; a filled frame (zeros padding) contributes 0, which is zp in out.  The scale
+ * does not enter and nothing is dequantized.
+ *   Accepted: p->active == 1; ndim 2 or 3; every padding mode; the whole window; x and out distinct, both dense in memory order
+ *   N, S0, C, S1, S2 at element-aligned bases; x_zero_point inside the element type's range; N, C, S1 * S2 and N * S0 * C below 2^31,
+ *   S0 below 2^30, fewer than 2^31 - 16 elements in the tensor.  Served by csrc/shiftnd_tshift_quant.hip without a fallback
+ *   (shiftnd_last_kernel(): tshift_forward_quantized for every element type and unit width; shiftnd_last_path(): SHIFTND_PATH_PLANE).
+ *   Errors, before anything is launched: a float dtype, and p->active == 0 (the sparse shift is the integer table's call: a float
+ *   table stays what it was there, an unsupported table type): SHIFTND_ERR_UNSUPPORTED_DTYPE; any other flag bit beside
+ *   SHIFTND_SHIFT_DIM0, a nonzero w_zero_point, out == x, channels-last views, a cut window, ndim 1, a size beyond the limits:
+ *   SHIFTND_ERR_INVALID_ARGUMENT.  A float wq_dtype other than SHIFTND_F32, and SHIFTND_F32 without the flag, stay
+ *   SHIFTND_ERR_UNSUPPORTED_DTYPE.
+ *
  * In place (the FIXED temporal shift written into its input): under the flag, out == x -- the same pointer, with identical strides --
  * and p->active == 0 is a call of its own, served by csrc/shiftnd_inplace.hip.  A thread owns one naturally aligned power-of-two
  * piece (at most 16 bytes: the widest that divides the plane's bytes, or the channel row's bytes, and the base) at the same offset in
