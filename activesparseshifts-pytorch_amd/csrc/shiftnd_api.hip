@@ -427,7 +427,9 @@ int frames_quantized_call(const shiftnd_problem *p, const void *x, const int64_t
 // shiftnd_forward_quantized under the flag with an fp32 table: the quantized INTERPOLATING temporal shift (shiftnd_tshift_quant.hip) --
 // I8 / U8 / I32 segment-major tensors, out of place, p->active == 1, the whole window, `wq` the fp32 [C] table (w_zero_point 0).  Served
 // by its one kernel or refused before anything is launched: no other flag bit, no channels-last view; p->active == 0 stays an
-// unsupported table type (the sparse shift is the integer table's call)
+// unsupported table type (the sparse shift is the integer table's call).  With SHIFTND_FRAMES beside the flag (and no further bit)
+// the same call on dense channels-last tensors, served by frames_forward_quantized (shiftnd_frames_quant.hip) or
+// refused: segment-major tensors have no route under the pair
 int tshift_quantized_call(const shiftnd_problem *p, const void *x, const int64_t *xs, const void *wq, int64_t wzp, int64_t xzp, void *out,
                           const int64_t *os, void *stream) {
     const int flags = SHIFTND_WEIGHTS_F32 | SHIFTND_SHIFT_DIM0 | SHIFTND_FRAMES | SHIFTND_PER_CLIP | SHIFTND_STREAM | SHIFTND_CLIP_FRAMES |
@@ -437,17 +439,26 @@ int tshift_quantized_call(const shiftnd_problem *p, const void *x, const int64_t
     if (!is_quant_dtype(q.dtype)) return SHIFTND_ERR_UNSUPPORTED_DTYPE;   // (the flag with a float dtype: no quantized dtype)
     // the sparse shift has no float table: what such a call was answered before this form existed (tests/test_temporal_cl_cpu.py pins it)
     if (!p->active) return SHIFTND_ERR_UNSUPPORTED_DTYPE;
-    if ((p->dtype & flags) != SHIFTND_SHIFT_DIM0 || wzp != 0) return SHIFTND_ERR_INVALID_ARGUMENT;
+    // SHIFTND_FRAMES beside the flag: the same problem on dense channels-last tensors, both of them (shiftnd_frames_quant.hip).  The
+    // explicit bit is required -- channels-last views under the flag alone stay refused -- and takes every such call to that kernel
+    const bool frames = (p->dtype & flags) == (SHIFTND_SHIFT_DIM0 | SHIFTND_FRAMES);
+    if (((p->dtype & flags) != SHIFTND_SHIFT_DIM0 && !frames) || wzp != 0) return SHIFTND_ERR_INVALID_ARGUMENT;
     if (out && out == x) return SHIFTND_ERR_INVALID_ARGUMENT;   // (x and out are __restrict__: there is no in-place form)
     Geometry g;
     const int rc = build_geometry(&q, xs, os, nullptr, g);
     if (rc != SHIFTND_OK) return rc;
-    if (!tshift_quantized_geometry_ok(g, q.dtype, xzp)) return SHIFTND_ERR_INVALID_ARGUMENT;   // (a cut window, ndim 1, the sizes)
+    if (!(frames ? frames_quantized_geometry_ok(g, q.dtype, xzp) : tshift_quantized_geometry_ok(g, q.dtype, xzp)))
+        return SHIFTND_ERR_INVALID_ARGUMENT;   // (a cut window, ndim 1, the sizes, the zero point)
     if (empty_geometry(g)) {
         g_last_path = SHIFTND_PATH_EMPTY;
         return SHIFTND_OK;
     }
     if (!x || !wq || !out || !aligned_to(wq, sizeof(float))) return SHIFTND_ERR_INVALID_ARGUMENT;
+    if (frames) {
+        if (!frames_tensor_ok(g, q.dtype, x, g.xs) || !frames_tensor_ok(g, q.dtype, out, g.os)) return SHIFTND_ERR_INVALID_ARGUMENT;
+        g_last_path = SHIFTND_PATH_CL;
+        return finish(frames_quantized_forward(g, q.dtype, x, wq, xzp, out, static_cast<hipStream_t>(stream)));
+    }
     if (!tshift_tensor_ok(g, q.dtype, x, g.xs) || !tshift_tensor_ok(g, q.dtype, out, g.os)) return SHIFTND_ERR_INVALID_ARGUMENT;
     g_last_path = SHIFTND_PATH_PLANE;
     return finish(tshift_quantized_forward(g, q.dtype, x, wq, xzp, out, static_cast<hipStream_t>(stream)));

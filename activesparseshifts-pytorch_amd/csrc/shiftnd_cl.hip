@@ -94,8 +94,10 @@ __device__ __forceinline__ void corner_rows(int a, int b, const int size[3], con
 }
 
 // ---- SSL / quantized forward: pure gather -------------------------------------------------------------------
+// ONE kernel for the four element sizes (es_log2 is launch-uniform: a scalar branch over four instantiations of the body, as
+// strided_gather_forward is one kernel for its element sizes).  A pure copy, so the element type is its size alone.
 template <int ESIZE>
-__global__ __launch_bounds__(kThreads) void cl_gather_forward(const ClParams p) {
+__device__ __forceinline__ void gather_body(const ClParams &p) {
     using R = typename raw_t<ESIZE>::type;
     int pgrp;
     const Lane l = decode_lane(p, pgrp);
@@ -120,6 +122,15 @@ __global__ __launch_bounds__(kThreads) void cl_gather_forward(const ClParams p) 
             const R v = xrow[rc >= 0 ? rc * p.xs[3] : 0];
             orow[j * p.os[3]] = (rowok && rc >= 0) ? v : fill;
         }
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void cl_gather_forward(const ClParams p, int es_log2) {
+    switch (es_log2) {
+    case 0: gather_body<1>(p); break;
+    case 1: gather_body<2>(p); break;
+    case 2: gather_body<4>(p); break;
+    default: gather_body<8>(p); break;
     }
 }
 
@@ -371,12 +382,8 @@ int cl_forward(const Geometry &g, int dtype, const void *x, const void *w, int w
     const bool gather_only = !g.active || dtype >= SHIFTND_I8;
     note_kernel(gather_only ? "cl_gather_forward" : "cl_active_forward");
     if (gather_only) {
-        switch (dtype_size(dtype)) {
-        case 1: hipLaunchKernelGGL((cl_gather_forward<1>), grid, block, 0, st, p); break;
-        case 2: hipLaunchKernelGGL((cl_gather_forward<2>), grid, block, 0, st, p); break;
-        case 4: hipLaunchKernelGGL((cl_gather_forward<4>), grid, block, 0, st, p); break;
-        default: hipLaunchKernelGGL((cl_gather_forward<8>), grid, block, 0, st, p); break;
-        }
+        const int es = dtype_size(dtype);
+        hipLaunchKernelGGL(cl_gather_forward, grid, block, 0, st, p, es == 1 ? 0 : (es == 2 ? 1 : (es == 4 ? 2 : 3)));
         return SHIFTND_OK;
     }
 #define SHIFTND_CL_ACTIVE(TT) \

@@ -268,6 +268,13 @@ size_t frames_backward_workspace(const Geometry &g, int dtype);
 int frames_backward(const Geometry &g, int dtype, const void *go, const void *x, const void *w, int wkind, bool per_clip, void *gx,
                     void *gw, void *workspace, hipStream_t st);
 
+// ---- the quantized interpolating temporal shift of channels-last tensors (shiftnd_frames_quant.hip; shiftnd_forward_quantized under
+// SHIFTND_SHIFT_DIM0 | SHIFTND_FRAMES with an fp32 table): tshift_quantized_forward's problem on I8 / U8 / I32 tensors in memory order
+// N, S0, S1, S2, C, `w` an fp32 [C] array, `zp` the tensors' zero point.  frames_quantized_geometry_ok: frames_geometry_ok's sizes and
+// the zero point's range; the tensors pass frames_tensor_ok.  No fallback: every such call is served.
+bool frames_quantized_geometry_ok(const Geometry &g, int dtype, int64_t zp);
+int frames_quantized_forward(const Geometry &g, int dtype, const void *x, const void *w, int64_t zp, void *out, hipStream_t st);
+
 // ---- temporal interlacing of channels-last tensors (shiftnd_interlace_frames.hip; SHIFTND_SHIFT_DIM0 | SHIFTND_INTERLACE_FRAMES):
 // the problem of shiftnd_interlace.hip on tensors in memory order N, S0, S1, S2, C, `w` and `gw` the packed arrays ([N, C] offsets
 // followed by [N, S0, C] scales), whole window, both modes; every tensor passes frames_tensor_ok.  frames_interlace_geometry_ok: the

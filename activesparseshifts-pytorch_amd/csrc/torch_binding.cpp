@@ -27,6 +27,7 @@
 //                 state of the previous frames, both written (composes on CPU tensors); inference only, no Autograd key
 //   quantized learnable  torchshifts_quantized_learnable::temporal_shift_learnable_quantized: the interpolating temporal shift of a
 //                 per-tensor quantized tensor in the integer domain, an fp32 table; inference only, no Autograd key
+//   quantized learnable cl  torchshifts_quantized_learnable_cl::temporal_shift_learnable_quantized_cl: ... keeping a channels-last layout
 //
 // Keys: the Autograd, CUDA and QuantizedCUDA kernels of every family are registered here.  The CPU / QuantizedCPU kernels that
 // compute (shift, fixed, fixed pool, temporal, temporal_shift_quantized, quantized learnable) live in torch_cpu_backend.cpp; the ones that compose other
@@ -2044,8 +2045,12 @@ Tensor &online_quantized_hip(Tensor &input, Tensor &state, const Tensor &shifts)
 // under the same table (which rounds it half to even): that route, nothing new launched.  On HIP tensors ONE flagged
 // shiftnd_forward_quantized call with the fp32 table as it is (shiftnd_tshift_quant.hip): no host sync, nothing allocated but the output.
 // (tslq_check is also called from torch_cpu_backend.cpp)
+void tslq_check_as(const char *op_name, const Tensor &input, const Tensor &weights, int64_t n_segment, int64_t padding_mode);
 void tslq_check(const Tensor &input, const Tensor &weights, int64_t n_segment, int64_t padding_mode) {
-    const char *op_name = "temporal_shift_learnable_quantized";
+    tslq_check_as("temporal_shift_learnable_quantized", input, weights, n_segment, padding_mode);
+}
+// ... under the name of the op that refuses (the _cl op takes the same arguments)
+void tslq_check_as(const char *op_name, const Tensor &input, const Tensor &weights, int64_t n_segment, int64_t padding_mode) {
     TORCH_CHECK(input.is_quantized(), op_name, ": expected a quantized input");
     TORCH_CHECK(input.qscheme() == at::kPerTensorAffine, op_name, ": expected a per-tensor quantized input");
     segment_check(op_name, input, weights, n_segment, padding_mode, "weights", !weights.is_quantized() && weights.scalar_type() == at::kFloat,
@@ -2078,6 +2083,50 @@ Tensor tslq_hip(const Tensor &input_, const Tensor &weights, int64_t n_segment, 
     check_status(shiftnd_forward_quantized(&p, t.data_ptr(), st, w.data_ptr(), SHIFTND_F32, 0, t.q_zero_point(), out.data_ptr(), st,
                                            current_stream(t)),
                  "temporal_shift_learnable_quantized (HIP)");
+    return out;
+}
+
+// ---- ... keeping a channels-last layout: torchshifts_quantized_learnable_cl::temporal_shift_learnable_quantized_cl ----------------
+// The values of temporal_shift_learnable_quantized with the layout of the argument kept (memory_format=torch.preserve_format in the
+// Python wrappers): a dense channels-last tensor (is_channels_last_dense) comes back in its own strides with its scale
+// and zero point, every other tensor exactly as the plain op returns it.  On HIP tensors a channels-last tensor is ONE
+// shiftnd_forward_quantized call under SHIFTND_SHIFT_DIM0 | SHIFTND_FRAMES on the tensor as it lies (shiftnd_frames_quant.hip): no
+// contiguous(), no transpose, no host sync, nothing allocated but the output.  active_flag == False IS temporal_shift_quantized_cl
+// under the same table.  On CPU tensors the plain op computes and the result is laid out in the argument's strides.
+Tensor tslq_cl_cpu(const Tensor &input, const Tensor &weights, int64_t n_segment, int64_t padding_mode, bool active_flag) {
+    static auto plain = typed_op<tsl_forward_sig>("temporal_shift_learnable_quantized", "torchshifts_quantized_learnable");
+    tslq_check_as("temporal_shift_learnable_quantized_cl", input, weights, n_segment, padding_mode);   // (the refusals under this op's name)
+    return in_layout_of(plain.call(input, weights, n_segment, padding_mode, active_flag), input);
+}
+
+// the frame kernels' limits (frames_geometry_ok, include/shiftnd_hip.h) and the flagged call has no fallback: refuse a larger tensor
+// before anything is allocated
+void tslq_cl_check_size(const Tensor &t, int64_t T) {
+    const int64_t limit = 1LL << 31, C = t.size(1), M = t.numel() / (t.size(0) * C);
+    const int64_t row_groups = (M + 7) / 8;   // (frames_geometry_ok: a frame kernel's workgroup takes at least eight steps of rows)
+    TORCH_CHECK(T < (1LL << 30) && M < limit && C < limit && t.size(0) < limit && t.size(0) * row_groups < limit &&
+                    t.numel() * static_cast<int64_t>(t.element_size()) <= (1LL << 46),
+                "temporal_shift_learnable_quantized_cl: a tensor of ", t.size(0), " frames of ", M, " pixels and ", C,
+                " channels is beyond the frame kernels' limits (2^31 frames, pixels, channels or row groups, 2^46 bytes); split the batch");
+}
+
+Tensor tslq_cl_hip(const Tensor &input, const Tensor &weights, int64_t n_segment, int64_t padding_mode, bool active_flag) {
+    if (!is_channels_last_dense(input)) return tslq_hip(input, weights, n_segment, padding_mode, active_flag);
+    const char *op_name = "temporal_shift_learnable_quantized_cl";
+    tslq_check_as(op_name, input, weights, n_segment, padding_mode);   // (first: a table on another device is named as such under either key)
+    TORCH_CHECK(input.is_cuda(), op_name, ": expected a CUDA tensor");
+    if (!active_flag) return temporal_quantized_cl_hip(input, weights, n_segment, padding_mode);
+    c10::DeviceGuard device_guard(input.device());
+    const int dtype = quant_dtype(input.scalar_type(), "temporal_shift_learnable_quantized_cl_cuda");
+    tslq_cl_check_size(input, n_segment);
+    Tensor out = empty_with_strides_of(input);   // (a dense channels-last tensor is not empty)
+    const Tensor w = weights.contiguous();       // ([C] and [C, 1] are the same C floats)
+    shiftnd_problem p;
+    int64_t st[5];
+    segment_problem(p, st, input, n_segment, padding_mode, true, dtype | SHIFTND_SHIFT_DIM0 | SHIFTND_FRAMES, true, op_name);
+    check_status(shiftnd_forward_quantized(&p, input.data_ptr(), st, w.data_ptr(), SHIFTND_F32, 0, input.q_zero_point(), out.data_ptr(), st,
+                                           current_stream(input)),
+                 "temporal_shift_learnable_quantized_cl (HIP)");
     return out;
 }
 
@@ -2363,3 +2412,12 @@ TORCH_LIBRARY(torchshifts_quantized_learnable, m) {
 }
 
 TORCH_LIBRARY_IMPL(torchshifts_quantized_learnable, QuantizedCUDA, m) { m.impl("temporal_shift_learnable_quantized", TORCH_FN(tslq_hip)); }
+
+// ... keeping a channels-last layout: its own namespace again (the op set above is pinned too).  No Autograd key.  The QuantizedCPU
+// kernel composes the plain op, so it is registered here
+TORCH_LIBRARY(torchshifts_quantized_learnable_cl, m) {
+    m.def("torchshifts_quantized_learnable_cl::temporal_shift_learnable_quantized_cl(Tensor input, Tensor weights, int n_segment, int padding_mode, bool active_flag) -> Tensor");
+}
+
+TORCH_LIBRARY_IMPL(torchshifts_quantized_learnable_cl, QuantizedCPU, m) { m.impl("temporal_shift_learnable_quantized_cl", TORCH_FN(tslq_cl_cpu)); }
+TORCH_LIBRARY_IMPL(torchshifts_quantized_learnable_cl, QuantizedCUDA, m) { m.impl("temporal_shift_learnable_quantized_cl", TORCH_FN(tslq_cl_hip)); }

@@ -41,7 +41,8 @@ def temporal_shift_quantized(input, shifts, n_segment, padding_mode=0, memory_fo
     return torch.ops.torchshifts.temporal_shift_quantized(input, shifts, int(n_segment), int(padding_mode))
 
 
-def temporal_shift_learnable_quantized(input, weights, n_segment, padding_mode=0, active_flag=True):
+def temporal_shift_learnable_quantized(input, weights, n_segment, padding_mode=0, active_flag=True,
+                                       memory_format=torch.contiguous_format):
     """The learnable temporal shift (torchshifts.functional.temporal_shift_learnable_func) of a per-tensor quantized
     [N * n_segment, C, ...] tensor (quint8, qint8, qint32; 2 to 5 dims) under a trained fp32 table `weights` ([n_channels] or
     [n_channels, 1], not requiring grad).  The result is defined in the integer domain: with q = input.int_repr(), zp the zero point
@@ -52,10 +53,20 @@ def temporal_shift_learnable_quantized(input, weights, n_segment, padding_mode=0
     rint half to even; zeros padding contributes 0, which is the zero point in the result.  The scale does not enter, nothing is
     dequantized or requantized: the result has the input's scale, zero point and dtype, and is contiguous (a channels-last input
     is made contiguous first).  On HIP tensors it is one kernel with the table passed as it is.  active_flag=False is
-    temporal_shift_quantized(input, weights, n_segment, padding_mode): the table rounded half to even.  No gradient."""
+    temporal_shift_quantized(input, weights, n_segment, padding_mode): the table rounded half to even.  No gradient.
+    memory_format=torch.preserve_format: a dense channels-last input (torch.channels_last, torch.channels_last_3d, or
+    [N * n_segment, C, L] with unit channel stride) comes back in its own strides with the same values, bit for bit -- on HIP
+    tensors interpolated as it lies, one kernel, nothing allocated but the output; active_flag=False is then
+    temporal_shift_quantized(..., memory_format=torch.preserve_format).  Every other input, and the default
+    torch.contiguous_format, give the contiguous result."""
     if not input.is_quantized:
         raise ValueError("Input to 'temporal_shift_learnable_quantized' must be quantized!")
     _assert_has_ops()
+    assert memory_format in (torch.contiguous_format, torch.preserve_format), \
+        f"temporal_shift_learnable_quantized expected memory_format to be torch.contiguous_format or torch.preserve_format, but it is {memory_format}"
+    if memory_format == torch.preserve_format:
+        return torch.ops.torchshifts_quantized_learnable_cl.temporal_shift_learnable_quantized_cl(input, weights, int(n_segment),
+                                                                                                  int(padding_mode), bool(active_flag))
     return torch.ops.torchshifts_quantized_learnable.temporal_shift_learnable_quantized(input, weights, int(n_segment), int(padding_mode),
                                                                                          bool(active_flag))
 

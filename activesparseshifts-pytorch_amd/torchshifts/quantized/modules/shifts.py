@@ -184,14 +184,20 @@ class LearnableTemporalShift(torch.nn.Module):
         in_channels (int): channels of the input.
         padding (str): 'zeros' | 'border' | 'periodic' | 'reflect' | 'symmetric'. Default 'zeros'.
         active_flag (bool): interpolate between two frames. Default True; without it the shift is round(weight), half to even.
+        memory_format: torch.contiguous_format (default: a contiguous output) or torch.preserve_format (a dense channels-last
+            input comes back channels-last, on HIP tensors interpolated as it lies in one kernel).  A plain attribute, not part
+            of the state_dict.
     forward(x) -> output, the tensor alone.  from_float converts a LearnableTemporalShift, active or not, carrying active_flag,
-    padding and n_segment over.
+    padding, n_segment and memory_format over.
     """
 
-    def __init__(self, n_segment, in_channels, padding='zeros', active_flag=True):
+    def __init__(self, n_segment, in_channels, padding='zeros', active_flag=True, memory_format=torch.contiguous_format):
         super().__init__()
         assert padding.lower() in shifts.paddings_dict.keys(), f'incorrect padding option: {padding}'
         assert int(n_segment) >= 1, 'n_segment must be >= 1'
+        assert memory_format in (torch.contiguous_format, torch.preserve_format), \
+            f'memory_format must be torch.contiguous_format or torch.preserve_format, not {memory_format}'
+        self.memory_format = memory_format
         self.padding = shifts.paddings_dict[padding.lower()]
         self.n_segment = int(n_segment)
         self.in_channels = in_channels
@@ -199,19 +205,21 @@ class LearnableTemporalShift(torch.nn.Module):
         self.register_buffer("weight", torch.zeros(in_channels, 1, dtype=torch.float32))
 
     def forward(self, input):
-        return temporal_shift_learnable_quantized(input, self.weight, self.n_segment, self.padding, self._active_flag)
+        return temporal_shift_learnable_quantized(input, self.weight, self.n_segment, self.padding, self._active_flag, self.memory_format)
 
     def _get_name(self):
         return 'QuantizedLearnableTemporalShift'
 
     def extra_repr(self):
+        fmt = '' if self.memory_format == torch.contiguous_format else f', memory_format={self.memory_format}'
         return (f'n_segment={self.n_segment}, in_channels={self.in_channels}, padding_method={rp_dict[self.padding]}, '
-                f'Active shift on forward pass: {"Yes" if self._active_flag else "No"}')
+                f'Active shift on forward pass: {"Yes" if self._active_flag else "No"}' + fmt)
 
     @classmethod
     def from_float(cls, mod):
         assert isinstance(mod, shifts.LearnableTemporalShift), 'expected a LearnableTemporalShift module'
-        qshift = cls(mod.n_segment, mod.in_channels, padding=rp_dict[mod.padding], active_flag=mod._active_flag)
+        qshift = cls(mod.n_segment, mod.in_channels, padding=rp_dict[mod.padding], active_flag=mod._active_flag,
+                     memory_format=mod.memory_format)
         qshift.weight = mod.weight.detach().to(torch.float32).reshape(mod.in_channels, 1).clone()
         return qshift
 

@@ -140,6 +140,16 @@ typedef enum shiftnd_dtype {
  *   SHIFTND_SHIFT_DIM0, a nonzero w_zero_point, out == x, channels-last views, a cut window, ndim 1, a size beyond the limits:
  *   SHIFTND_ERR_INVALID_ARGUMENT.  A float wq_dtype other than SHIFTND_F32, and SHIFTND_F32 without the flag, stay
  *   SHIFTND_ERR_UNSUPPORTED_DTYPE.
+ *   ... of channels-last tensors: SHIFTND_SHIFT_DIM0 | SHIFTND_FRAMES on p->dtype with wq_dtype == SHIFTND_F32 is the same call --
+ *   the same table, the same arithmetic, the same result bit for bit -- on x and out that are BOTH dense channels-last views (memory
+ *   order N, S0, S1, S2, C: strides {S0*M*C, 1, M*C, C} for sizes {N, C, S0, M}) at element-aligned bases.  The flag pair is required:
+ *   such views under SHIFTND_SHIFT_DIM0 alone stay refused.  Accepted: p->active == 1; ndim 2 or 3; every padding mode; the whole
+ *   window; x and out distinct; w_zero_point 0; x_zero_point inside the element type's range; the bounds of the channels-last sparse
+ *   shift above (N, C, S1 * S2 and N * S0 below 2^31, S0 below 2^30, 2^46 bytes).  Served by csrc/shiftnd_frames_quant.hip without a
+ *   fallback (shiftnd_last_kernel(): frames_forward_quantized, or frames_forward_quantized_ragged where a channel row or a base is
+ *   not a multiple of 16 bytes; shiftnd_last_path(): SHIFTND_PATH_CL).  Errors, before anything is launched: p->active == 0 and a
+ *   float dtype: SHIFTND_ERR_UNSUPPORTED_DTYPE; any further flag bit, a nonzero w_zero_point, out == x, segment-major tensors, a cut
+ *   window, ndim 1, a size beyond the limits: SHIFTND_ERR_INVALID_ARGUMENT.
  *
  * In place (the FIXED temporal shift written into its input): under the flag, out == x -- the same pointer, with identical strides --
  * and p->active == 0 is a call of its own, served by csrc/shiftnd_inplace.hip.  A thread owns one naturally aligned power-of-two

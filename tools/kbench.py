@@ -48,6 +48,8 @@ def main():
     ap.add_argument("--cut", default="", help="cut amounts per dim, e.g. '1,1;1,1' (default: the workload's, bench.py CUTS)")
     ap.add_argument("--libs", default="", help="comma-separated variants/<name>.so builds timed interleaved in THIS process "
                                                "(same tensors, same physical pages); 'tree' = the in-tree library")
+    ap.add_argument("--channels-last", action="store_true", help="x and out dense channels-last (2-D / 3-D shapes); with --policy 4 "
+                                                                 "the channel-fastest kernels of csrc/shiftnd_cl.hip")
     a = ap.parse_args()
     extra = {  # tuning-only variants of the bench workloads
         "c2a": (2, (64, 256, 224, 224), "float32", True, "Shift2d active N64 C256 224x224 fp32"),
@@ -84,6 +86,9 @@ def main():
     if quant:
         x = (x * 255).to(torch.uint8)
         wq = (w.float().round() + 128).to(torch.uint8)
+    if a.channels_last:
+        fmt = torch.channels_last if nd == 2 else torch.channels_last_3d
+        x, go = x.contiguous(memory_format=fmt), go.contiguous(memory_format=fmt)
     out, gx, gw = torch.empty_like(go), torch.empty_like(x), torch.empty_like(w)
     elems, oelems, es = x.numel(), go.numel(), x.element_size()
     knobs = []
