@@ -23,9 +23,9 @@ PKG = os.path.join(HERE, "torchshifts")
 OBJ = os.path.join(HERE, "build")
 INC = os.path.join(ROOT, "include")
 
-HIP_SOURCES = ["shiftnd_api.hip", "shiftnd_strided.hip", "shiftnd_plane.hip", "shiftnd_sweep.hip", "shiftnd_slide.hip", "shiftnd_step.hip", "shiftnd_step_fwd.hip", "shiftnd_walk3.hip", "shiftnd_walk.hip", "shiftnd_span.hip", "shiftnd_flat.hip", "shiftnd_bytes.hip", "shiftnd_small.hip", "shiftnd_rows.hip", "shiftnd_qpool.hip", "shiftnd_cl.hip", "shiftnd_cl_tiled.hip", "shiftnd_cl_tiled3.hip", "shiftnd_transpose.hip", "shiftnd_gradx.hip", "shiftnd_segment.hip", "shiftnd_tshift.hip", "shiftnd_tshift_quant.hip", "shiftnd_interlace.hip", "shiftnd_frames.hip", "shiftnd_frames_learn.hip", "shiftnd_frames_quant.hip", "shiftnd_interlace_frames.hip", "shiftnd_inplace.hip", "shiftnd_stream.hip"]
+HIP_SOURCES = ["shiftnd_api.hip", "shiftnd_strided.hip", "shiftnd_plane.hip", "shiftnd_sweep.hip", "shiftnd_slide.hip", "shiftnd_step.hip", "shiftnd_step_fwd.hip", "shiftnd_walk3.hip", "shiftnd_walk.hip", "shiftnd_span.hip", "shiftnd_flat.hip", "shiftnd_bytes.hip", "shiftnd_small.hip", "shiftnd_rows.hip", "shiftnd_qpool.hip", "shiftnd_cl.hip", "shiftnd_cl_tiled.hip", "shiftnd_cl_tiled3.hip", "shiftnd_transpose.hip", "shiftnd_gradx.hip", "shiftnd_segment.hip", "shiftnd_tshift.hip", "shiftnd_tshift_quant.hip", "shiftnd_interlace.hip", "shiftnd_interlace_quant.hip", "shiftnd_frames.hip", "shiftnd_frames_learn.hip", "shiftnd_frames_quant.hip", "shiftnd_interlace_frames.hip", "shiftnd_inplace.hip", "shiftnd_stream.hip"]
 CPP_SOURCES = ["torch_binding.cpp", "torch_cpu_backend.cpp"]
-HEADERS = [os.path.join(CSRC, h) for h in ("shiftnd_common.hpp", "shiftnd_dispatch.hpp", "shiftnd_launch.hpp", "shiftnd_stage.hpp", "shiftnd_step.hpp", "shiftnd_temporal.hpp", "shiftnd_frames_learn.hpp", "shiftnd_transpose_tile.inc")] + [
+HEADERS = [os.path.join(CSRC, h) for h in ("shiftnd_common.hpp", "shiftnd_dispatch.hpp", "shiftnd_launch.hpp", "shiftnd_stage.hpp", "shiftnd_step.hpp", "shiftnd_temporal.hpp", "shiftnd_quant_unit.hpp", "shiftnd_frames_learn.hpp", "shiftnd_transpose_tile.inc")] + [
     os.path.join(INC, "shiftnd_hip.h")]
 
 # -ffp-contract=off: interpolation must be mul+mul+add like the reference's x86-64 CPU build

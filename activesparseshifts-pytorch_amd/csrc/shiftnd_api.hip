@@ -464,6 +464,38 @@ int tshift_quantized_call(const shiftnd_problem *p, const void *x, const int64_t
     return finish(tshift_quantized_forward(g, q.dtype, x, wq, xzp, out, static_cast<hipStream_t>(stream)));
 }
 
+// shiftnd_forward_quantized under the flag with an fp32 table and SHIFTND_PER_CLIP or SHIFTND_INTERLACE beside it: the quantized
+// per-clip temporal shift (`wq` the fp32 [N, C] table) and quantized temporal interlacing (`wq` the packed fp32 table, N * C offsets
+// followed by N * S0 * C scales), shiftnd_interlace_quant.hip -- I8 / U8 / I32 segment-major tensors, out of place, the
+// whole window, p->active 0 or 1 (the sparse shift rounds the offset half to even and still applies the scale), w_zero_point 0.
+// Served by its one kernel or refused before anything is launched: exactly one of the two bits and no further one, no channels-last
+// view
+int interlace_quantized_call(const shiftnd_problem *p, const void *x, const int64_t *xs, const void *wq, int64_t wzp, int64_t xzp,
+                             void *out, const int64_t *os, void *stream) {
+    const int flags = SHIFTND_WEIGHTS_F32 | SHIFTND_SHIFT_DIM0 | SHIFTND_FRAMES | SHIFTND_PER_CLIP | SHIFTND_STREAM | SHIFTND_CLIP_FRAMES |
+                      SHIFTND_INTERLACE | SHIFTND_INTERLACE_FRAMES;
+    shiftnd_problem q = *p;
+    q.dtype = p->dtype & ~flags;
+    if (!is_quant_dtype(q.dtype)) return SHIFTND_ERR_UNSUPPORTED_DTYPE;   // (the bits with a float dtype: no quantized dtype)
+    const int bits = p->dtype & flags;
+    const bool scaled = bits == (SHIFTND_SHIFT_DIM0 | SHIFTND_INTERLACE);
+    if ((!scaled && bits != (SHIFTND_SHIFT_DIM0 | SHIFTND_PER_CLIP)) || wzp != 0) return SHIFTND_ERR_INVALID_ARGUMENT;
+    if (out && out == x) return SHIFTND_ERR_INVALID_ARGUMENT;   // (x and out are __restrict__: there is no in-place form)
+    Geometry g;
+    const int rc = build_geometry(&q, xs, os, nullptr, g);
+    if (rc != SHIFTND_OK) return rc;
+    // a cut window, ndim 1, the sizes (N * S0 * C < 2^31 bounds the offsets' and the scales' index), the zero point
+    if (!tshift_quantized_geometry_ok(g, q.dtype, xzp) || !per_clip_table_ok(g)) return SHIFTND_ERR_INVALID_ARGUMENT;
+    if (empty_geometry(g)) {
+        g_last_path = SHIFTND_PATH_EMPTY;
+        return SHIFTND_OK;
+    }
+    if (!x || !wq || !out || !aligned_to(wq, sizeof(float))) return SHIFTND_ERR_INVALID_ARGUMENT;
+    if (!tshift_tensor_ok(g, q.dtype, x, g.xs) || !tshift_tensor_ok(g, q.dtype, out, g.os)) return SHIFTND_ERR_INVALID_ARGUMENT;
+    g_last_path = SHIFTND_PATH_PLANE;
+    return finish(tinterlace_quantized_forward(g, q.dtype, x, wq, scaled, xzp, out, static_cast<hipStream_t>(stream)));
+}
+
 // the backward under the flag, both layouts: `frames` (SHIFTND_FRAMES) picks the sizes, the tensor check, the workspace and the kernels
 int tshift_backward_call(const shiftnd_problem *p, const void *go, const int64_t *gos, const void *x, const int64_t *xs, const void *w,
                          void *gx, const int64_t *gxs, void *gw, void *workspace, size_t workspace_bytes, void *stream) {
@@ -780,6 +812,9 @@ int shiftnd_forward_quantized(const shiftnd_problem *p, const void *x, const int
     if (!p || !x_strides || !out_strides) return SHIFTND_ERR_INVALID_ARGUMENT;
     // an fp32 table under the flag: the quantized interpolating temporal shift, or its refusal (without the flag a float table
     // stays an unsupported dtype, below)
+    // ... with SHIFTND_PER_CLIP or SHIFTND_INTERLACE beside the flag: the quantized per-clip shift / quantized temporal interlacing
+    if ((p->dtype & SHIFTND_SHIFT_DIM0) && wq_dtype == SHIFTND_F32 && (p->dtype & (SHIFTND_PER_CLIP | SHIFTND_INTERLACE)))
+        return interlace_quantized_call(p, x, x_strides, wq, w_zero_point, x_zero_point, out, out_strides, stream);
     if ((p->dtype & SHIFTND_SHIFT_DIM0) && wq_dtype == SHIFTND_F32)
         return tshift_quantized_call(p, x, x_strides, wq, w_zero_point, x_zero_point, out, out_strides, stream);
     // the online step (SHIFTND_STREAM beside the flag; alone it is an unknown dtype bit): SHIFTND_FRAMES / SHIFTND_PER_CLIP beside it

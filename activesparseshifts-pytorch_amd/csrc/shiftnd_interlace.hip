@@ -27,8 +27,8 @@
 // Units, the ragged names and the 32-bit limits are those of shiftnd_tshift.hip; T is unbounded (nothing is sized by it).  No LDS
 // beyond block_sum's, no scratch.  Two kernels in all: the element type is a launch-uniform switch inside each.
 //
-// Not built: the quantized / in-place / online forms, group expansion inside the kernel.  (Channels-last tensors: since built,
-// shiftnd_interlace_frames.hip.)
+// Not built: the in-place / online forms, group expansion inside the kernel.  (Channels-last tensors: since built,
+// shiftnd_interlace_frames.hip; the quantized forward: shiftnd_interlace_quant.hip.)
 #include "shiftnd_temporal.hpp"
 
 namespace shiftnd {

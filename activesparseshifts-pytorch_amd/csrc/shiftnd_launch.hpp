@@ -237,6 +237,13 @@ int tshift_backward(const Geometry &g, int dtype, const void *go, const void *x,
 bool tshift_quantized_geometry_ok(const Geometry &g, int dtype, int64_t zp);
 int tshift_quantized_forward(const Geometry &g, int dtype, const void *x, const void *w, int64_t zp, void *out, hipStream_t st);
 
+// ---- quantized temporal interlacing / the quantized per-clip temporal shift (shiftnd_interlace_quant.hip; shiftnd_forward_quantized
+// under SHIFTND_SHIFT_DIM0 | SHIFTND_PER_CLIP or SHIFTND_SHIFT_DIM0 | SHIFTND_INTERLACE with an fp32 table): `w` is the fp32 [N, C]
+// table, or (`scaled`) the packed one, N * C offsets followed by N * S0 * C scales; g.active as the caller gave it.  The geometry
+// passes tshift_quantized_geometry_ok and the tensors tshift_tensor_ok.
+int tinterlace_quantized_forward(const Geometry &g, int dtype, const void *x, const void *w, bool scaled, int64_t zp, void *out,
+                                 hipStream_t st);
+
 // ---- temporal interlacing (shiftnd_interlace.hip; SHIFTND_SHIFT_DIM0 | SHIFTND_INTERLACE): the per-clip temporal shift times a scale
 // per (n, t, c) plane.  `w` and `gw` are ONE packed array each: [N, C] offsets followed by [N, S0, C] scales.  The geometry and the
 // tensors pass tshift_geometry_ok / tshift_tensor_ok (which holds N * S0 * C below 2^31: the scales' index and the reduction's entry

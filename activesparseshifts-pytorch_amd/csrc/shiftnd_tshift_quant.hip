@@ -25,10 +25,11 @@
 // kernel (scalar branches), as the unit is in tshift_forward.  No LDS, no scratch; nothing outside x, the table and out is touched:
 // a source unit lies at the output unit's offset inside another plane of x.
 //
-// Not built: channels-last tensors, a cut window, per-clip tables, an in-place or online form, requantization to another scale.
+// Not built: channels-last tensors, a cut window, an in-place or online form, requantization to another scale.  (Per-clip tables and
+// temporal interlacing: shiftnd_interlace_quant.hip.)
 #include <type_traits>
 
-#include "shiftnd_temporal.hpp"
+#include "shiftnd_quant_unit.hpp"   // QUnit, load_qunit / store_qunit, blend_bytes / blend_words
 
 namespace shiftnd {
 namespace {
@@ -43,59 +44,6 @@ struct QTShiftParams {
     uint32_t flip;                   // I8: 0x80808080 (the bytes are handled as q + 128), else 0
     int32_t zp;                      // the zero point (I8: + 128, so 0..255 for both one-byte types)
 };
-
-// a unit of V bytes as dwords (V < 4: the low bytes of one)
-template <int V> struct QUnit { uint32_t d[V >= 4 ? V / 4 : 1]; };
-
-template <int V> __device__ __forceinline__ QUnit<V> load_qunit(const char *p) {
-    typedef typename vec_of<V>::type vec_t;
-    const vec_t v = __builtin_nontemporal_load(reinterpret_cast<const vec_t *>(p));
-    QUnit<V> u;
-    if constexpr (V >= 4) __builtin_memcpy(u.d, &v, V);
-    else u.d[0] = v;
-    return u;
-}
-template <int V> __device__ __forceinline__ void store_qunit(char *p, const QUnit<V> &u) {
-    typedef typename vec_of<V>::type vec_t;
-    vec_t v;
-    if constexpr (V >= 4) __builtin_memcpy(&v, u.d, V);
-    else v = static_cast<vec_t>(u.d[0]);
-    __builtin_nontemporal_store(v, reinterpret_cast<vec_t *>(p));
-}
-
-// one-byte elements, as unsigned bytes (I8 flipped by the caller); zp in 0..255
-template <int V> __device__ __forceinline__ QUnit<V> blend_bytes(const QUnit<V> &a, const QUnit<V> &b, float d, float zp) {
-    QUnit<V> r;
-    const float keep = 1.0f - d;   // lerp1's (1 - x), once per unit
-#pragma unroll
-    for (int i = 0; i < (V >= 4 ? V / 4 : 1); ++i) {
-        uint32_t packed = 0;
-#pragma unroll
-        for (int e = 0; e < (V >= 4 ? 4 : V); ++e) {
-            const float va = static_cast<float>((a.d[i] >> (8 * e)) & 0xffu) - zp;
-            const float vb = static_cast<float>((b.d[i] >> (8 * e)) & 0xffu) - zp;
-            const float v = va * keep + vb * d;
-            packed = __builtin_amdgcn_cvt_pk_u8_f32(rintf(v) + zp, e, packed);   // saturates to 0..255
-        }
-        r.d[i] = packed;
-    }
-    return r;
-}
-
-// I32 elements in fp64
-template <int V> __device__ __forceinline__ QUnit<V> blend_words(const QUnit<V> &a, const QUnit<V> &b, double d, double zp) {
-    QUnit<V> r;
-    const double keep = 1.0 - d;
-#pragma unroll
-    for (int i = 0; i < V / 4; ++i) {
-        const double va = static_cast<double>(static_cast<int32_t>(a.d[i])) - zp;
-        const double vb = static_cast<double>(static_cast<int32_t>(b.d[i])) - zp;
-        double v = rint(va * keep + vb * d) + zp;
-        v = v < -2147483648.0 ? -2147483648.0 : (v > 2147483647.0 ? 2147483647.0 : v);
-        r.d[i] = static_cast<uint32_t>(static_cast<int32_t>(v));
-    }
-    return r;
-}
 
 constexpr int64_t kFill = -1, kPast = -2;
 

@@ -27,10 +27,12 @@
 //                 state of the previous frames, both written (composes on CPU tensors); inference only, no Autograd key
 //   quantized learnable  torchshifts_quantized_learnable::temporal_shift_learnable_quantized: the interpolating temporal shift of a
 //                 per-tensor quantized tensor in the integer domain, an fp32 table; inference only, no Autograd key
+//   quantized interlace  torchshifts_quantized_interlace::temporal_interlace_quantized: temporal interlacing (scales None: the
+//                 per-clip temporal shift) of a per-tensor quantized tensor in the integer domain; inference only, no Autograd key
 //   quantized learnable cl  torchshifts_quantized_learnable_cl::temporal_shift_learnable_quantized_cl: ... keeping a channels-last layout
 //
 // Keys: the Autograd, CUDA and QuantizedCUDA kernels of every family are registered here.  The CPU / QuantizedCPU kernels that
-// compute (shift, fixed, fixed pool, temporal, temporal_shift_quantized, quantized learnable) live in torch_cpu_backend.cpp; the ones that compose other
+// compute (shift, fixed, fixed pool, temporal, temporal_shift_quantized, quantized learnable, quantized interlace) live in torch_cpu_backend.cpp; the ones that compose other
 // ops (pool, temporal cl, learnable, learnable cl) are registered here.
 //
 // Helpers every family uses: typed_op + one *Ops struct per family (cached dispatcher handles),
@@ -2130,6 +2132,67 @@ Tensor tslq_cl_hip(const Tensor &input, const Tensor &weights, int64_t n_segment
     return out;
 }
 
+// ---- quantized temporal interlacing: torchshifts_quantized_interlace::temporal_interlace_quantized --------------------------------
+// temporal_interlace (scales given) and temporal_shift_learnable_per_clip (scales None) on the int_repr of a per-tensor quantized
+// tensor (quint8, qint8, qint32), defined in the integer domain: with q = int_repr, zp the zero point and F = fp32
+// (8-bit) / fp64 (qint32),
+//     out = clamp(zp + rint(temporal_interlace((q - zp).to(F), offsets.to(F), scales.to(F), active_flag)), the dtype's range)
+// The tensor's scale and zero point pass through (a scale entry above 1 can saturate: the clamp is part of the definition), the
+// result is contiguous, there is no gradient; both values of active_flag are this op's own.  On HIP tensors ONE flagged
+// shiftnd_forward_quantized call (shiftnd_interlace_quant.hip) -- SHIFTND_PER_CLIP under the [N, C] table as it is, SHIFTND_INTERLACE
+// under the packed table (one cat of the two small tables): no host sync, nothing else allocated but the output.
+// (tiq_check is also called from torch_cpu_backend.cpp)
+void tiq_check(const Tensor &input, const Tensor &offsets, const c10::optional<Tensor> &scales, int64_t n_segment, int64_t padding_mode) {
+    const char *op_name = "temporal_interlace_quantized";
+    TORCH_CHECK(input.is_quantized(), op_name, ": expected a quantized input");
+    TORCH_CHECK(input.qscheme() == at::kPerTensorAffine, op_name, ": expected a per-tensor quantized input");
+    // (the padding mode is looked at after both tables, below: segment_check sees a valid one)
+    segment_check(op_name, input, offsets, n_segment, 0, "offsets", !offsets.is_quantized() && offsets.scalar_type() == at::kFloat, "fp32",
+                  true);
+    if (scales.has_value()) {
+        const Tensor &sc = *scales;
+        TORCH_CHECK(sc.dim() == 3 && sc.size(0) == offsets.size(0) && sc.size(1) == n_segment && sc.size(2) == input.size(1), op_name,
+                    ": scales must have shape [N, T, C] = [", offsets.size(0), ", ", n_segment, ", ", input.size(1), "]");
+        TORCH_CHECK(sc.device() == input.device(), op_name, ": scales must be on the input's device");
+        TORCH_CHECK(!sc.is_quantized() && sc.scalar_type() == at::kFloat, op_name, ": scales must be fp32");
+    }
+    TORCH_CHECK(padding_mode >= 0 && padding_mode <= 4, op_name, ": padding_mode must be 0..4");
+    TORCH_CHECK(!offsets.requires_grad(), op_name, ": offsets must not require grad (the quantized op has no gradient; pass offsets.detach())");
+    TORCH_CHECK(!scales.has_value() || !scales->requires_grad(), op_name,
+                ": scales must not require grad (the quantized op has no gradient; pass scales.detach())");
+}
+
+// the kernel counts the tensor's elements in 32 bits and the flagged call has no fallback: refuse a larger tensor before anything is
+// allocated
+void tiq_check_size(const Tensor &input) {
+    TORCH_CHECK(input.numel() + 16 < (1LL << 31), "temporal_interlace_quantized: a tensor of ", input.numel(),
+                " elements is beyond the kernel's limit of 2^31 - 16 units; split the batch");
+}
+
+Tensor tiq_hip(const Tensor &input_, const Tensor &offsets, const c10::optional<Tensor> &scales, int64_t n_segment, int64_t padding_mode,
+               bool active_flag) {
+    tiq_check(input_, offsets, scales, n_segment, padding_mode);   // (first: a table on another device is named as such under either key)
+    TORCH_CHECK(input_.is_cuda(), "temporal_interlace_quantized: expected a CUDA tensor");
+    c10::DeviceGuard device_guard(input_.device());
+    const int dtype = quant_dtype(input_.scalar_type(), "temporal_interlace_quantized_cuda");
+    tiq_check_size(input_);
+    const Tensor t = is_channels_last_dense(input_) ? channels_last_to_contiguous(input_) : input_.contiguous();   // (a tile transpose of the int_repr)
+    Tensor out = at::_empty_affine_quantized(t.sizes(), t.options().memory_format(at::MemoryFormat::Contiguous), t.q_scale(),
+                                             t.q_zero_point(), c10::nullopt);
+    if (t.numel() == 0) return out;
+    // the [N, C] table as it is, or the packed one: N * C offsets followed by N * T * C scales
+    const Tensor w = scales.has_value() ? at::cat({offsets.reshape({-1}), scales->reshape({-1})}) : offsets.contiguous();
+    shiftnd_problem p;
+    int64_t st[5];
+    segment_problem(p, st, t, n_segment, padding_mode, active_flag,
+                    dtype | SHIFTND_SHIFT_DIM0 | (scales.has_value() ? SHIFTND_INTERLACE : SHIFTND_PER_CLIP), false,
+                    "temporal_interlace_quantized");
+    check_status(shiftnd_forward_quantized(&p, t.data_ptr(), st, w.data_ptr(), SHIFTND_F32, 0, t.q_zero_point(), out.data_ptr(), st,
+                                           current_stream(t)),
+                 "temporal_interlace_quantized (HIP)");
+    return out;
+}
+
 int64_t cuda_version() { return -1; }  // no CUDA toolkit: extension.py only compares when torch.version.cuda is set
 int64_t hip_version() { return HIP_VERSION; }
 
@@ -2421,3 +2484,11 @@ TORCH_LIBRARY(torchshifts_quantized_learnable_cl, m) {
 
 TORCH_LIBRARY_IMPL(torchshifts_quantized_learnable_cl, QuantizedCPU, m) { m.impl("temporal_shift_learnable_quantized_cl", TORCH_FN(tslq_cl_cpu)); }
 TORCH_LIBRARY_IMPL(torchshifts_quantized_learnable_cl, QuantizedCUDA, m) { m.impl("temporal_shift_learnable_quantized_cl", TORCH_FN(tslq_cl_hip)); }
+
+// quantized temporal interlacing / the quantized per-clip temporal shift (scales None): a namespace of its own.  No Autograd key: an
+// inference op (QuantizedCPU: torch_cpu_backend.cpp)
+TORCH_LIBRARY(torchshifts_quantized_interlace, m) {
+    m.def("torchshifts_quantized_interlace::temporal_interlace_quantized(Tensor input, Tensor offsets, Tensor? scales, int n_segment, int padding_mode, bool active_flag) -> Tensor");
+}
+
+TORCH_LIBRARY_IMPL(torchshifts_quantized_interlace, QuantizedCUDA, m) { m.impl("temporal_interlace_quantized", TORCH_FN(tiq_hip)); }

@@ -428,6 +428,8 @@ template <int ND> Tensor shift_fixed_pool_backward_cpu(const Tensor &grad, const
 void temporal_check(const at::Tensor &input, const at::Tensor &shifts, int64_t n_segment, int64_t padding_mode);   // torch_binding.cpp
 void temporal_quantized_check(const at::Tensor &input, const at::Tensor &shifts, int64_t n_segment, int64_t padding_mode);
 void tslq_check(const at::Tensor &input, const at::Tensor &weights, int64_t n_segment, int64_t padding_mode);
+void tiq_check(const at::Tensor &input, const at::Tensor &offsets, const c10::optional<at::Tensor> &scales, int64_t n_segment,
+               int64_t padding_mode);
 namespace cpu {
 
 // the planes of a contiguous [N*T, C, plane] tensor, copied or filled; `fill`: the element's bit pattern (0, or a quantized tensor's
@@ -546,6 +548,64 @@ Tensor tslq_cpu(const Tensor &input, const Tensor &weights, int64_t T, int64_t p
     return out;
 }
 
+// temporal_interlace_quantized: temporal interlacing (scales nullptr: the per-clip temporal shift) of a per-tensor quantized tensor in
+// the integer domain (torch_binding.cpp) -- tslq_planes under clip n's row of the offsets, `active` as given (the sparse
+// shift: the offset rounded half to even, fraction 0), and per plane (n, t, c) ONE multiply by its scale after the lerp:
+// clamp(zp + rint(lerp1(q0 - zp, q1 - zp, dw) * s)) in CT (fp32 for the 8-bit types, fp64 for qint32); a filled frame contributes 0
+template <typename R, typename CT>
+void tiq_planes(const R *x, R *out, int64_t N, int64_t T, int64_t C, int64_t M, const float *offsets, const float *scales, bool active,
+                int pad, int64_t zp_, CT lo, CT hi) {
+    const CT zp = static_cast<CT>(zp_);
+    at::parallel_for(0, N * T, 1, [&](int64_t begin, int64_t end) {
+        for (int64_t nt = begin; nt < end; ++nt) {
+            const int64_t n = nt / T, t = nt % T;
+            for (int64_t c = 0; c < C; ++c) {
+                int64_t iw;
+                CT dw;
+                prep_forward<CT>(static_cast<CT>(offsets[n * C + c]), active, iw, dw);
+                const CT sc = scales ? static_cast<CT>(scales[nt * C + c]) : CT(1);
+                const int64_t s0 = T == 1 ? 0 : pad_index(t - iw, T, pad), s1 = T == 1 ? 0 : pad_index(t + 1 - iw, T, pad);
+                const R *a = s0 >= 0 ? x + ((n * T + s0) * C + c) * M : nullptr, *b = s1 >= 0 ? x + ((n * T + s1) * C + c) * M : nullptr;
+                R *o = out + (nt * C + c) * M;
+                for (int64_t m = 0; m < M; ++m) {
+                    const CT va = a ? static_cast<CT>(a[m]) - zp : CT(0), vb = b ? static_cast<CT>(b[m]) - zp : CT(0);
+                    const CT y = active ? lerp1(va, vb, dw) : va;
+                    const CT v = std::nearbyint(y * sc) + zp;
+                    o[m] = static_cast<R>(std::min(std::max(v, lo), hi));
+                }
+            }
+        }
+    });
+}
+
+Tensor tiq_cpu(const Tensor &input, const Tensor &offsets, const c10::optional<Tensor> &scales, int64_t T, int64_t padding_mode,
+               bool active_flag) {
+    tiq_check(input, offsets, scales, T, padding_mode);   // (first: a table on another device is named as such under either key)
+    TORCH_CHECK(input.device().is_cpu() && offsets.device().is_cpu() && (!scales.has_value() || scales->device().is_cpu()),
+                "temporal_interlace_quantized_cpu: expected CPU tensors");
+    const at::ScalarType st = input.scalar_type();
+    TORCH_CHECK(st == at::kQUInt8 || st == at::kQInt8 || st == at::kQInt32, "\"temporal_interlace_quantized_cpu\" not implemented for '",
+                c10::toString(st), "'");
+    const Tensor t = input.contiguous();
+    Tensor out = at::_empty_affine_quantized(t.sizes(), t.options().memory_format(at::MemoryFormat::Contiguous), t.q_scale(),
+                                             t.q_zero_point(), c10::nullopt);
+    if (t.numel() == 0) return out;
+    const int64_t C = t.size(1), N = t.size(0) / T, M = t.numel() / (t.size(0) * C), zp = t.q_zero_point();
+    const Tensor oc = offsets.contiguous(), sc = scales.has_value() ? scales->contiguous() : Tensor();
+    const float *o = oc.data_ptr<float>(), *s = scales.has_value() ? sc.data_ptr<float>() : nullptr;
+    const int pad = static_cast<int>(padding_mode);
+    if (st == at::kQUInt8)
+        tiq_planes<uint8_t, float>(static_cast<const uint8_t *>(t.data_ptr()), static_cast<uint8_t *>(out.data_ptr()), N, T, C, M, o, s,
+                                   active_flag, pad, zp, 0.0f, 255.0f);
+    else if (st == at::kQInt8)
+        tiq_planes<int8_t, float>(static_cast<const int8_t *>(t.data_ptr()), static_cast<int8_t *>(out.data_ptr()), N, T, C, M, o, s,
+                                  active_flag, pad, zp, -128.0f, 127.0f);
+    else
+        tiq_planes<int32_t, double>(static_cast<const int32_t *>(t.data_ptr()), static_cast<int32_t *>(out.data_ptr()), N, T, C, M, o, s,
+                                    active_flag, pad, zp, -2147483648.0, 2147483647.0);
+    return out;
+}
+
 template <int ND> Tensor qshift_forward_cpu(const Tensor &input, const Tensor &weights, const Tensor &borders,
                                             at::IntArrayRef new_size, int64_t padding_mode, bool /*active_flag*/) {
     TORCH_CHECK(input.is_quantized() && weights.is_quantized(), "q_shiftnd_cpu: expected quantized tensors");
@@ -612,4 +672,8 @@ TORCH_LIBRARY_IMPL(torchshifts, QuantizedCPU, m) {
 
 TORCH_LIBRARY_IMPL(torchshifts_quantized_learnable, QuantizedCPU, m) {
     m.impl("temporal_shift_learnable_quantized", TORCH_FN(tslq_cpu));
+}
+
+TORCH_LIBRARY_IMPL(torchshifts_quantized_interlace, QuantizedCPU, m) {
+    m.impl("temporal_interlace_quantized", TORCH_FN(tiq_cpu));
 }

@@ -268,13 +268,16 @@ def backward_input(grad_out, w, input_shape, pad, borders=None, grad_x=None, wor
     return grad_x
 
 
-def forward_quantized(xq, wq, w_zero_point, x_zero_point, pad, borders=None, out=None, shift_dim0=False, active=False, frames=False):
+def forward_quantized(xq, wq, w_zero_point, x_zero_point, pad, borders=None, out=None, shift_dim0=False, active=False, frames=False,
+                      per_clip=False, interlace=False):
     """xq: int8/uint8/int32 device tensor (int_repr); wq: int8/uint8/int32 device tensor [C, nd].  shift_dim0: the flagged call
     (wq [C]; xq and `out` dense channels-last views, memory order N, S0, S1, S2, C; out=xq: the in-place call, which also takes
     the segment-major layout).  active: p->active -- with shift_dim0 and an fp32 [C] table `wq` (w_zero_point 0) the quantized
     interpolating temporal shift of segment-major views xq and `out`; frames: set FRAMES beside it -- the same call on dense
-    channels-last views xq and `out` (strides {T*M*C, 1, M*C, C})."""
-    p = problem(xq, pad, active, borders, shift_dim0=shift_dim0, frames=frames)
+    channels-last views xq and `out` (strides {T*M*C, 1, M*C, C}).  per_clip / interlace: set PER_CLIP / INTERLACE beside shift_dim0 --
+    with an fp32 `wq` (w_zero_point 0) the quantized per-clip temporal shift (wq [N, C]) / quantized temporal interlacing (wq the
+    packed table, pack_interlace) of segment-major views xq and `out`, `active` 0 or 1."""
+    p = problem(xq, pad, active, borders, shift_dim0=shift_dim0, frames=frames, per_clip=per_clip, interlace=interlace)
     if out is None:
         out = _new(out_shape(xq, borders), xq)
     wq = wq.contiguous()

@@ -21,8 +21,11 @@ def _default_static_mappings():
 
 tndm_mapping = _default_static_mappings()
 
-from .modules import LearnableTemporalShift, OnlineTemporalShift, Shift1d, Shift2d, Shift3d, TemporalShift, interpolating_quant_mapping, new_quant_mapping  # noqa: E402,F401
+from .modules import LearnablePerClipTemporalShift, LearnableTemporalShift, OnlineTemporalShift, Shift1d, Shift2d, Shift3d, TemporalInterlace, TemporalShift, interlacing_quant_mapping, interpolating_quant_mapping, new_quant_mapping  # noqa: E402,F401
 
 quant_mapping = {**tndm_mapping, **new_quant_mapping}
 # ... for a net trained with LearnableTemporalShift(active_flag=True): its entry is quantized.LearnableTemporalShift
 quant_mapping_interpolating = {**tndm_mapping, **interpolating_quant_mapping}
+# ... plus PerClipTemporalShift / LearnablePerClipTemporalShift / TemporalInterlace -> quantized.LearnablePerClipTemporalShift /
+# quantized.TemporalInterlace (set offset_net.qconfig = weight_net.qconfig = None on a TemporalInterlace: its nets stay float)
+quant_mapping_interlacing = {**tndm_mapping, **interlacing_quant_mapping}

@@ -71,6 +71,52 @@ def temporal_shift_learnable_quantized(input, weights, n_segment, padding_mode=0
                                                                                          bool(active_flag))
 
 
+def _expand_groups(table, channels):
+    """a group table [..., G] (C % G == 0) as [..., C], entry g serving the C // G consecutive channels of group g; every other
+    table as it is (the op names what is wrong with it)"""
+    groups = table.shape[-1] if table.dim() >= 2 else 0
+    if groups >= 1 and groups != channels and channels % groups == 0:
+        return table.repeat_interleave(channels // groups, dim=table.dim() - 1)
+    return table
+
+
+def temporal_interlace_quantized(input, offsets, scales, n_segment, padding_mode=0, active_flag=True):
+    """Temporal interlacing (torchshifts.functional.temporal_interlace_func, the TIN layer's core) of a per-tensor quantized
+    [N * n_segment, C, ...] tensor (quint8, qint8, qint32; 2 to 5 dims) under fp32 tables that do not require grad: offsets [N, C]
+    (or [N, G], C % G == 0) and scales [N, n_segment, C] (or [N, n_segment, G]); scales=None is the per-clip shift alone, equal to
+    scales of ones.  The result is defined in the integer domain: with q = input.int_repr(), zp the zero point and F = fp32 (8-bit
+    types) or fp64 (qint32),
+
+        out = clamp(zp + rint(temporal_interlace_func((q - zp).to(F), offsets.to(F), scales.to(F), n_segment, padding_mode, active_flag)))
+
+    rint half to even; the interpolation is the float op's (two multiplies, one add), then ONE multiply by the plane's scale; zeros
+    padding contributes 0, which is the zero point in the result under any finite scale.  The tensor's scale does not enter, nothing
+    is dequantized or requantized: the result has the input's scale, zero point and dtype, and is contiguous (a channels-last input
+    is made contiguous first).  A scale entry above 1 can therefore SATURATE -- the clamp to the dtype's range is part of the
+    definition; TIN's WeightNet yields weights in (0, 2), so choose the activation's quantization range with that headroom.
+    active_flag=False rounds the offsets half to even and still applies the scales.  Offsets and scales must be finite (not
+    validated: no host synchronisation).  On HIP tensors it is one kernel.  No gradient."""
+    if not input.is_quantized:
+        raise ValueError("Input to 'temporal_interlace_quantized' must be quantized!")
+    _assert_has_ops()
+    channels = input.shape[1] if input.dim() >= 2 else 0
+    offsets = _expand_groups(offsets, channels)
+    if scales is not None:
+        scales = _expand_groups(scales, channels)
+    return torch.ops.torchshifts_quantized_interlace.temporal_interlace_quantized(input, offsets, scales, int(n_segment), int(padding_mode),
+                                                                                  bool(active_flag))
+
+
+def temporal_shift_learnable_per_clip_quantized(input, weights, n_segment, padding_mode=0, active_flag=True):
+    """The per-clip temporal shift (torchshifts.functional.temporal_shift_learnable_per_clip_func) of a per-tensor quantized
+    [N * n_segment, C, ...] tensor under an fp32 table `weights` [N, C] (or [N, G], C % G == 0), one row per clip:
+    temporal_interlace_quantized without scales -- the same integer-domain definition, the same kernel, nothing saturates.
+    active_flag=False rounds the table half to even (the fixed per-clip shift, PerClipTemporalShift).  No gradient."""
+    if not input.is_quantized:
+        raise ValueError("Input to 'temporal_shift_learnable_per_clip_quantized' must be quantized!")
+    return temporal_interlace_quantized(input, weights, None, n_segment, padding_mode, active_flag)
+
+
 def temporal_shift_quantized_(input, shifts, n_segment, padding_mode=0):
     """temporal_shift_quantized written into `input`, which is returned with its scale, zero point and layout (the in-place
     torchshifts.functional.temporal_shift_func_ of a per-tensor quantized tensor).  On HIP tensors a dense input -- contiguous or

@@ -14,13 +14,14 @@ Differences from the reference:
     the kernel ignores the scale.  Here the scale is always 1; weights that do not fit quint8 around zero point 128
     (|round(w)| > 127) become qint32 with zero point 0, which both backends accept.
 """
+import copy
 import warnings
 
 import torch
 
 import torchshifts.modules.shifts as shifts
 from torchshifts.functional import shift1d_pool_func, shift2d_pool_func, shift3d_pool_func
-from torchshifts.quantized.functional import shift1d_quantized, shift2d_quantized, shift3d_quantized, temporal_shift_quantized, temporal_shift_quantized_, temporal_shift_online_quantized, temporal_shift_online_quantized_, temporal_shift_learnable_quantized
+from torchshifts.quantized.functional import shift1d_quantized, shift2d_quantized, shift3d_quantized, temporal_shift_quantized, temporal_shift_quantized_, temporal_shift_online_quantized, temporal_shift_online_quantized_, temporal_shift_learnable_quantized, temporal_interlace_quantized, temporal_shift_learnable_per_clip_quantized
 
 _POOL_FUNCS = {1: shift1d_pool_func, 2: shift2d_pool_func, 3: shift3d_pool_func}
 
@@ -222,6 +223,135 @@ class LearnableTemporalShift(torch.nn.Module):
                      memory_format=mod.memory_format)
         qshift.weight = mod.weight.detach().to(torch.float32).reshape(mod.in_channels, 1).clone()
         return qshift
+
+
+class LearnablePerClipTemporalShift(torch.nn.Module):
+    """Quantized per-clip Temporal Shift Module: the float LearnablePerClipTemporalShift / PerClipTemporalShift on per-tensor
+    quantized tensors (quint8, qint8, qint32), in the integer domain
+    (torchshifts.quantized.functional.temporal_shift_learnable_per_clip_quantized).  Like the float modules it has no parameter and
+    no buffer: the table comes from the caller -- a float net that looks at the clip, or per-clip jitter -- and is converted to
+    fp32 (detached: the op has no gradient).  The output keeps the input's scale and zero point and is contiguous.
+
+    Arguments:
+        n_segment (int): frames per clip, T.
+        padding (str): 'zeros' | 'border' | 'periodic' | 'reflect' | 'symmetric'. Default 'zeros'.
+        active_flag (bool): interpolate between two frames. Default True; without it the shift is round(table), half to even.
+    forward(x, table) -> output, the tensor alone.  table: [N, C], or [N, G] with C % G == 0.  from_float converts a
+    LearnablePerClipTemporalShift (its active_flag) or a PerClipTemporalShift (active_flag=False: its integer table).
+    """
+
+    def __init__(self, n_segment, padding='zeros', active_flag=True):
+        super().__init__()
+        assert padding.lower() in shifts.paddings_dict.keys(), f'incorrect padding option: {padding}'
+        assert int(n_segment) >= 1, 'n_segment must be >= 1'
+        self.padding = shifts.paddings_dict[padding.lower()]
+        self.n_segment = int(n_segment)
+        self._active_flag = bool(active_flag)
+
+    def forward(self, input, table):
+        return temporal_shift_learnable_per_clip_quantized(input, table.detach().to(torch.float32), self.n_segment, self.padding,
+                                                           self._active_flag)
+
+    def _get_name(self):
+        return 'QuantizedLearnablePerClipTemporalShift'
+
+    def extra_repr(self):
+        return (f'n_segment={self.n_segment}, padding_method={rp_dict[self.padding]}, '
+                f'Active shift on forward pass: {"Yes" if self._active_flag else "No"}, per-clip weights')
+
+    @classmethod
+    def from_float(cls, mod):
+        assert isinstance(mod, (shifts.LearnablePerClipTemporalShift, shifts.PerClipTemporalShift)), \
+            'expected a LearnablePerClipTemporalShift or a PerClipTemporalShift module'
+        active = bool(mod._active_flag) if isinstance(mod, shifts.LearnablePerClipTemporalShift) else False
+        return cls(mod.n_segment, padding=rp_dict[mod.padding], active_flag=active)
+
+
+class TemporalInterlace(torch.nn.Module):
+    """Quantized Temporal Interlacing layer (TIN): the float TemporalInterlace on per-tensor quantized tensors (quint8, qint8,
+    qint32).  The OffsetNet and the WeightNet stay FLOAT -- they see a [N, fold, T] descriptor, not the activation -- under the
+    float module's names, so a float TemporalInterlace checkpoint loads as it is.  The descriptor is formed from the integers: the
+    int_repr of the first fold channels summed per (n, t, c) plane in integers, then (sum / M - zero_point) * scale in fp32 -- no
+    float tensor of the activation's size is made.  The layer is ONE temporal_interlace_quantized call
+    (torchshifts.quantized.functional): the output keeps the input's scale and zero point and is contiguous.  The WeightNet's
+    weights lie in (0, 2) and the tensor's scale is kept, so values above half the quantization range saturate (the clamp is part
+    of the op's definition): calibrate the activation with that headroom.
+
+    Arguments:
+        n_segment (int): frames per clip, T.
+        in_channels (int): C.
+        shift_div (int): the first C // shift_div channels are interlaced. Default 1 (all of them).
+        padding (str): 'zeros' | 'border' | 'periodic' | 'reflect' | 'symmetric'. Default 'zeros'.
+    forward(x) -> output, the tensor alone.  from_float converts a TemporalInterlace whose nets are still float: keep them out
+    of the conversion with `layer.offset_net.qconfig = layer.weight_net.qconfig = None` before prepare (from_float raises a
+    ValueError when convert has already quantized their layers).
+    """
+
+    def __init__(self, n_segment, in_channels, shift_div=1, padding='zeros'):
+        super().__init__()
+        assert padding.lower() in shifts.paddings_dict.keys(), f'incorrect padding option: {padding}'
+        assert int(n_segment) >= 1, 'n_segment must be >= 1'
+        self.n_segment = int(n_segment)
+        self.in_channels = int(in_channels)
+        self.shift_div = int(shift_div)
+        self.fold = self.in_channels // self.shift_div
+        assert self.fold >= 4 and self.fold % 4 == 0, \
+            f'in_channels // shift_div ({self.fold}) must be a positive multiple of 4: the fold holds four channel groups'
+        self.padding = shifts.paddings_dict[padding.lower()]
+        self.offset_net = shifts.OffsetNet(self.fold, self.n_segment)
+        self.weight_net = shifts.WeightNet(self.fold)
+
+    def descriptor(self, input):
+        """the clip descriptor [N, fold, T] of a quantized input: the dequantized spatial mean of the first fold channels, from an
+        integer sum per plane"""
+        T, fold = self.n_segment, self.fold
+        N = input.shape[0] // T
+        q = input[:, :fold].int_repr().reshape(N, T, fold, -1)
+        total = q.sum(3, dtype=torch.int64)   # exact
+        mean = total.to(torch.float32) / q.shape[3]
+        return ((mean - input.q_zero_point()) * input.q_scale()).permute(0, 2, 1)
+
+    def tables(self, input):
+        """offsets [N, C] and scales [N, T, C] of the one call (fp32, detached), from the nets' [N, 2] and [N, T, 2]: the float
+        module's expansion, the negated offset included"""
+        T, C, fold = self.n_segment, self.in_channels, self.fold
+        N = input.shape[0] // T
+        desc = self.descriptor(input).to(self.offset_net.conv.weight.dtype)
+        with torch.no_grad():
+            o, w = self.offset_net(desc), self.weight_net(desc)
+        table, weight = torch.cat((o, -o), 1), torch.cat((w, w), 2)          # [N, 4], [N, T, 4]
+        offsets = (-table).repeat_interleave(fold // 4, dim=1)               # (the op's sign: out[t] = x[t - w])
+        scales = weight.repeat_interleave(fold // 4, dim=2)
+        if fold < C:
+            offsets = torch.cat((offsets, offsets.new_zeros(N, C - fold)), 1)
+            scales = torch.cat((scales, scales.new_ones(N, T, C - fold)), 2)
+        return offsets.detach().to(torch.float32), scales.detach().to(torch.float32)
+
+    def forward(self, input):
+        assert input.shape[1] == self.in_channels and input.shape[0] % self.n_segment == 0, \
+            f'expected a [N * {self.n_segment}, {self.in_channels}, ...] tensor, but it is shape is {tuple(input.shape)}'
+        offsets, scales = self.tables(input)
+        return temporal_interlace_quantized(input, offsets, scales, self.n_segment, self.padding, True)
+
+    def _get_name(self):
+        return 'QuantizedTemporalInterlace'
+
+    def extra_repr(self):
+        return (f'n_segment={self.n_segment}, in_channels={self.in_channels}, shift_div={self.shift_div}, '
+                f'padding_method={rp_dict[self.padding]}')
+
+    @classmethod
+    def from_float(cls, mod):
+        assert isinstance(mod, shifts.TemporalInterlace), 'expected a TemporalInterlace module'
+        layers = ((mod.offset_net.conv, torch.nn.Conv1d), (mod.offset_net.fc1, torch.nn.Linear), (mod.offset_net.fc2, torch.nn.Linear),
+                  (mod.weight_net.conv, torch.nn.Conv1d))
+        if any(type(layer) is not kind for layer, kind in layers):
+            raise ValueError("quantized TemporalInterlace keeps a float OffsetNet / WeightNet, but their layers are no longer float "
+                             "nn.Conv1d / nn.Linear: set `layer.offset_net.qconfig = layer.weight_net.qconfig = None` before prepare")
+        qmod = cls(mod.n_segment, mod.in_channels, shift_div=mod.shift_div, padding=rp_dict[mod.padding])
+        qmod.offset_net = copy.deepcopy(mod.offset_net)
+        qmod.weight_net = copy.deepcopy(mod.weight_net)
+        return qmod
 
 
 class OnlineTemporalShift(shifts.OnlineTemporalShift):

@@ -150,6 +150,24 @@ typedef enum shiftnd_dtype {
  *   not a multiple of 16 bytes; shiftnd_last_path(): SHIFTND_PATH_CL).  Errors, before anything is launched: p->active == 0 and a
  *   float dtype: SHIFTND_ERR_UNSUPPORTED_DTYPE; any further flag bit, a nonzero w_zero_point, out == x, segment-major tensors, a cut
  *   window, ndim 1, a size beyond the limits: SHIFTND_ERR_INVALID_ARGUMENT.
+ *   ... under a per-clip table, and interlaced: SHIFTND_SHIFT_DIM0 plus exactly ONE of SHIFTND_PER_CLIP / SHIFTND_INTERLACE on p->dtype
+ *   with wq_dtype == SHIFTND_F32 and w_zero_point 0, on segment-major tensors (csrc/shiftnd_interlace_quant.hip).
+ *     SHIFTND_PER_CLIP:  wq is the fp32 [N, C] table, one row per clip: clip n is shifted by w = wq[n * C + c]; s = 1.
+ *     SHIFTND_INTERLACE: wq is the packed fp32 array of the float interlace call -- the N * C offsets followed by the N * S0 * C
+ *                        scales: w = wq[n * C + c], s = wq[N * C + (n * S0 + t) * C + c].
+ *     out = clamp(zp + rint(((q[pad(t - iw)] - zp) * (1 - dw) + (q[pad(t - iw + 1)] - zp) * dw) * s), the element type's range)
+ *   the interpolation above, then ONE multiply by the plane's scale in F, rint half to even; a filled frame contributes 0, which is zp
+ *   in out under any finite scale.  The tensor's scale does not enter, so a scale entry above 1 can saturate: the clamp is part of the
+ *   definition.  p->active == 0 is served too: (iw, dw) = (rint(w) half to even, 0), the scale still applied.  Offsets and scales
+ *   must be finite (not validated).
+ *   Accepted: p->active 0 or 1; ndim 2 or 3; every padding mode; the whole window; x and out distinct, both dense in memory order
+ *   N, S0, C, S1, S2 at element-aligned bases; wq aligned to 4 bytes; x_zero_point inside the element type's range; the limits of the
+ *   [C]-table call above (N * S0 * C below 2^31 bounds both table indices; fewer than 2^31 - 16 elements).  Served without a fallback
+ *   (shiftnd_last_kernel(): tinterlace_forward_quantized for every element type, unit width and both bits; shiftnd_last_path():
+ *   SHIFTND_PATH_PLANE); no workspace (shiftnd_backward_workspace_bytes: 0).  Errors, before anything is launched: a float dtype:
+ *   SHIFTND_ERR_UNSUPPORTED_DTYPE; both bits together, any further flag bit, a nonzero w_zero_point, out == x, channels-last views, a
+ *   cut window, ndim 1, a size beyond the limits, a misaligned table: SHIFTND_ERR_INVALID_ARGUMENT.  An integer wq_dtype under either
+ *   bit stays what it was, SHIFTND_ERR_UNSUPPORTED_DTYPE.
  *
  * In place (the FIXED temporal shift written into its input): under the flag, out == x -- the same pointer, with identical strides --
  * and p->active == 0 is a call of its own, served by csrc/shiftnd_inplace.hip.  A thread owns one naturally aligned power-of-two
@@ -213,7 +231,10 @@ typedef enum shiftnd_dtype {
  *   N * C below 2^31.  The same kernels serve the call -- the table's row stride is a run-time field of theirs -- so
  *   shiftnd_last_kernel() reports tshift_forward[_ragged] / tshift_backward[_ragged] and shiftnd_last_path() SHIFTND_PATH_PLANE.
  *   An empty problem: SHIFTND_PATH_EMPTY, with the N * C entries of grad_w zeroed.
- *   Errors, before anything is launched: a quantized dtype, the bit on shiftnd_forward_quantized or on the pooled entry points, and
+ *   On shiftnd_forward_quantized with wq_dtype == SHIFTND_F32 the bit selects the quantized per-clip shift ("Quantized,
+ *   interpolating ... under a per-clip table" above: I8 / U8 / I32 tensors, wq the fp32 [N, C] table, p->active 0 or 1).
+ *   Errors, before anything is launched: a quantized dtype on shiftnd_forward / shiftnd_backward, the bit on
+ *   shiftnd_forward_quantized with an integer table or on the pooled entry points, and
  *   the bit without SHIFTND_SHIFT_DIM0 (an unknown dtype bit): SHIFTND_ERR_UNSUPPORTED_DTYPE; together with SHIFTND_FRAMES, out == x
  *   (the in-place form), channels-last tensors, the x == NULL && grad_w == NULL form of shiftnd_backward, N * C of 2^31 or more,
  *   and whatever SHIFTND_SHIFT_DIM0 refuses: SHIFTND_ERR_INVALID_ARGUMENT.  The workspace query answers 0 for a refused problem.
@@ -303,7 +324,10 @@ typedef enum shiftnd_dtype {
  *   Served by csrc/shiftnd_interlace.hip without a fallback: shiftnd_last_kernel() reports tinterlace_forward / tinterlace_backward
  *   (*_ragged for planes that are not whole 16-byte pieces or bases off the 16-byte grid), shiftnd_last_path() SHIFTND_PATH_PLANE.  An
  *   empty problem: SHIFTND_PATH_EMPTY, with the N * C + N * S0 * C entries of grad_w zeroed.
- *   Errors, before anything is launched (the workspace query answers 0): a quantized dtype, the bit on shiftnd_forward_quantized or
+ *   On shiftnd_forward_quantized with wq_dtype == SHIFTND_F32 the bit selects quantized temporal interlacing ("Quantized,
+ *   interpolating ... interlaced" above: I8 / U8 / I32 tensors, wq the packed fp32 table, p->active 0 or 1, no workspace).
+ *   Errors, before anything is launched (the workspace query answers 0): a quantized dtype on shiftnd_forward / shiftnd_backward, the
+ *   bit on shiftnd_forward_quantized with an integer table or
  *   on the pooled entry points, and the bit without SHIFTND_SHIFT_DIM0 (an unknown dtype bit, on every entry point):
  *   SHIFTND_ERR_UNSUPPORTED_DTYPE; the bit beside SHIFTND_FRAMES, SHIFTND_PER_CLIP, SHIFTND_STREAM or SHIFTND_CLIP_FRAMES, out == x,
  *   channels-last tensors, ndim 1, a cut window, the x == NULL form of shiftnd_backward, a size beyond the bounds:
